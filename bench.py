@@ -31,10 +31,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The HIP runtime maps streams onto 4 hardware queues by default; the lanes of concurrent callers (proofs64: 8 caller threads
-# per rank) want one each.  Read once at HIP initialisation, so it has to be in the environment before torch touches the GPU
-# (measured on proofs64, 8 callers: 97.7 -> 104 proofs/s).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np  # noqa: E402
 
@@ -120,6 +116,18 @@ class SclkSampler:
                 "cards_sampled": len(self.paths)}
 
 
+def u64_words(a):
+    """uint64 limbs -> float64 array of their 32-bit halves, low half first: exact, so two dumps compare bit for bit."""
+    return np.ascontiguousarray(a, dtype=np.uint64).view(np.uint32).astype(np.float64)
+
+
+def dump_outputs(out_dir, aff):
+    """--dump-outputs: the last timed step's MSM result normalised to affine (Montgomery x words, y words, infinity flag).  Not the
+    G1Projective record the caller receives: two runs with the same arguments return the same point in different projective coordinates."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result_affine.npy"), np.concatenate([u64_words(aff["x"]), u64_words(aff["y"]), [float(aff["infinity"])]]))
+
+
 def load_profile_json(name):
     try:
         with open(os.path.join(ROOT, "profiles", name)) as f:
@@ -165,7 +173,10 @@ def main():
                                                              "rows stateless / SNARKVM_HIP_BASE_CACHE=16 / resident")
     ap.add_argument("--ffi-threads", type=int, default=4, help="--ffi-only: caller threads that issue the commitments of a round (the reference's rayon workers)")
     ap.add_argument("--proof1-all-at-once", action="store_true", help="proof1: make the everything-enqueued-at-once replay (an order no Fiat-Shamir prover can use) the headline again")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="default workload: write the MSM result of the last timed step (rank 0, affine) to DIR/msm_result_affine.npy, float64 of its 32-bit words")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "msm":
+        ap.error("--dump-outputs is implemented for the default workload (--workload msm) only")
 
     import torch
     import torch.distributed as dist
@@ -334,6 +345,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     pairs_per_s = world * n * args.steps / dt
     want_affine = check_results(res, scalars, "timed_msm", shifts)  # outside the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, to_affine(res[-1:])[0])
     del d_step
     # ---- the same K pipelined steps on the OTHER distribution (rank 0, N = 1): SURVEY.md 8(d) config 2 names witness-like scalars as the second one
     other = None

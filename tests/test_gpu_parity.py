@@ -1092,6 +1092,32 @@ def test_bench_two_rank_path_on_one_gpu():
         assert len(d["duplicate_devices"]) == 1 and sorted(d["duplicate_devices"][0]["ranks"]) == [0, 1]
 
 
+def test_bench_dump_outputs_is_the_last_step_and_repeats(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same array, and it is the LAST timed step's MSM
+    (step k's scalars are the seeded vector rotated by k * 999983 positions) against the oracle's closed form."""
+    import subprocess
+    import sys
+
+    steps, lg = 3, 16
+    dumps = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(util.ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--lg-msm", str(lg), "--lg-ntt", "16",
+               "--ntt-steps", "2", "--no-extra-legs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=util.ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        assert sorted(os.listdir(tmp_path / run)) == ["msm_result_affine.npy"]
+        dumps.append(np.load(tmp_path / run / "msm_result_affine.npy"))
+    a, b = dumps
+    assert a.dtype == np.float64 and a.shape == (25,) and np.array_equal(a, b)
+    n = 1 << lg
+    last = np.roll(synthetic.random_fr_integers(n, synthetic.SEED_MSM_LARGE), ((steps - 1) * 999983) % n, axis=0)
+    k = util.weighted_sum_mod_r(last, start=1)
+    want = oracle.g1_to_affine(oracle.g1_mul(util.g1_generator_affine(), np.array([(k >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)))[0]
+    words = a[:24].astype(np.uint64)
+    limbs = words[0::2] | (words[1::2] << np.uint64(32))
+    assert np.array_equal(limbs[:6], want["x"]) and np.array_equal(limbs[6:], want["y"]) and a[24] == float(want["infinity"]) == 0.0
+
+
 def test_bench_proofs64_two_rank_lockstep_on_one_gpu():
     """bench.py --workload proofs64 with two ranks sharing this GPU over gloo: the proofs are sharded over the ranks (strong scaling),
     every rank replays its share in lock step and by concurrent callers, the modes are compared, rank 0 checks one whole proof

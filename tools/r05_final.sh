@@ -40,7 +40,6 @@ python - > $O/r05_proof1_without_g2.txt 2> $O/proof1_nog2.err <<'PY'
 import sys, time
 sys.path.insert(0, ".")
 import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from snarkvm_amd import _lib, proofs
 torch.cuda.set_device(0)
@@ -75,7 +74,7 @@ timeout 150 python tools/bench_g2.py > $O/g2.md 2> $O/g2.err; cut -c1-75 $O/g2.m
 SNARKVM_HIP_TUNING=pair2=0 timeout 150 python tools/bench_g2.py > $O/g2_pair0.md 2> $O/g2_pair0.err; cut -c1-75 $O/g2_pair0.md | tail -4
 timeout 120 tools/exp/mfma_reduction > $O/r05_mfma_reduction.txt 2>&1; cat $O/r05_mfma_reduction.txt
 timeout 200 python tools/tables1_cliff.py > $O/r05_tables1_cliff.md 2> $O/tables1_cliff.err; cat $O/r05_tables1_cliff.md
-g++ -std=c++17 -O2 -pthread -I include -I /opt/rocm/include -D__HIP_PLATFORM_AMD__ tools/bench_callers.cpp -o /tmp/bench_callers -L snarkvm_amd/lib -lsnarkvm_hip -L /opt/rocm/lib -lamdhip64 -Wl,-rpath,$PWD/snarkvm_amd/lib -Wl,-rpath,/opt/rocm/lib -Wl,-rpath-link,/opt/rocm/lib && GPU_MAX_HW_QUEUES=8 timeout 120 /tmp/bench_callers 1 8 32 > $O/callers.md 2> $O/callers.err; cat $O/callers.md
+g++ -std=c++17 -O2 -pthread -I include -I /opt/rocm/include -D__HIP_PLATFORM_AMD__ tools/bench_callers.cpp -o /tmp/bench_callers -L snarkvm_amd/lib -lsnarkvm_hip -L /opt/rocm/lib -lamdhip64 -Wl,-rpath,$PWD/snarkvm_amd/lib -Wl,-rpath,/opt/rocm/lib -Wl,-rpath-link,/opt/rocm/lib && timeout 120 /tmp/bench_callers 1 8 32 > $O/callers.md 2> $O/callers.err; cat $O/callers.md
 python - <<'PY'
 import sys
 sys.path.insert(0, ".")
@@ -84,9 +83,9 @@ open("/tmp/g2pts.bin", "wb").write(synthetic.g2_points(1 << 16).tobytes())
 PY
 g++ -std=c++17 -O2 -pthread -I include -I /opt/rocm/include -D__HIP_PLATFORM_AMD__ tools/bench_proof_callers.cpp -o /tmp/bench_proof_callers -L snarkvm_amd/lib -lsnarkvm_hip -L /opt/rocm/lib -lamdhip64 -Wl,-rpath,$PWD/snarkvm_amd/lib -Wl,-rpath,/opt/rocm/lib -Wl,-rpath-link,/opt/rocm/lib && {
   for mode in "" "--scope" "--scope-await" "--scope-await-in-stream" "--scope-sync"; do
-    GPU_MAX_HW_QUEUES=8 timeout 200 /tmp/bench_proof_callers - $mode 1 8 16 > "$O/proof_callers_nog2$mode.md" 2> "$O/proof_callers_nog2$mode.err"; cat "$O/proof_callers_nog2$mode.md"
+    timeout 200 /tmp/bench_proof_callers - $mode 1 8 16 > "$O/proof_callers_nog2$mode.md" 2> "$O/proof_callers_nog2$mode.err"; cat "$O/proof_callers_nog2$mode.md"
   done
-  GPU_MAX_HW_QUEUES=8 timeout 200 /tmp/bench_proof_callers /tmp/g2pts.bin --scope-sync 1 8 16 > "$O/proof_callers_g2--scope-sync.md" 2>&1; cat "$O/proof_callers_g2--scope-sync.md"
+  timeout 200 /tmp/bench_proof_callers /tmp/g2pts.bin --scope-sync 1 8 16 > "$O/proof_callers_g2--scope-sync.md" 2>&1; cat "$O/proof_callers_g2--scope-sync.md"
 }
 ls $O
 bash tools/logical_devices.sh r05 > $O/logical_devices.log 2>&1; tail -8 $O/logical_devices.log; cp gpurun_out/r05_logical/*.log $O/ 2>/dev/null

@@ -3,7 +3,7 @@
 # the same call list through the reference's own three symbols), the G2 tail sweep, the group NTT timing, rocprofv3 statistics and PMC passes, the soak.
 # Every step runs under its own `timeout`: a hung step costs its limit, not the lease.
 O=gpurun_out/r06_final; mkdir -p $O
-export TMPDIR=/tmp GPU_MAX_HW_QUEUES=8
+export TMPDIR=/tmp
 timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_driver_command.json 2> $O/bench_driver_command.err; echo "bench rc=$?"
 python - <<'PY'
 import json

@@ -55,7 +55,6 @@ def main():
         print(exe)
         return
     env = dict(os.environ)
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")
     if args.tsan:
         # The HIP / HSA runtimes are not instrumented: their internal synchronisation (own atomics, futexes, doorbells) is invisible to the tool, so every
         # heap word they recycle between their threads looks like a race.  Reports whose racing access sits INSIDE those libraries are suppressed; what stays
