@@ -65,17 +65,33 @@ RustError snarkvm_msm(void *out, const void *points_with_infinity, size_t npoint
  * previous one); the per-chunk partial results are combined on the host.
  * Ownership: like the reference's symbol the call is STATELESS - `points_with_infinity` and `scalars` are only read during the
  * call and nothing about them is retained after return.
- * Opt-in extension (off unless SNARKVM_HIP_BASE_CACHE=1/2/4/8/16 is set in the environment): a host base range passed a SECOND
+ * Opt-in extension (off unless SNARKVM_HIP_BASE_CACHE is set in the environment): a host base range passed a SECOND
  * time with the same address and length is kept in HBM (converted, with precomputed tables - 17 x 15-bit below 2^18 points,
  * 16 x 16, 13 x 20 from 2^21, 12 x 22 from 2^24 - on every device) and later calls whose bases are a slice of it skip upload
  * and conversion - the reference's callers always pass slices of one long-lived `powers_of_beta_g` vector
- * (kzg10/mod.rs:117-119).  By setting the variable the caller promises that such vectors are immutable while the process
- * uses them (a hit is verified against raw copies of every 64th point of the slice, which cannot catch every mutation);
- * host memory is only read inside the slice the current call passed.  SNARKVM_HIP_BASE_CACHE_MB caps the HBM bytes per device
- * (default 65536).  Code that can be changed should call snarkvm_hip_register_bases* + snarkvm_hip_msm_registered*.
- * snarkvm_hip_set_base_cache(tables) is the API form of the variable (0, 1, 2, 4, 8 or 16; overrides the environment from then on; 0 also drops
- * every cached range) - for a host that cannot set the environment before the library is loaded. */
+ * (kzg10/mod.rs:117-119).  Host memory is only read inside the slice the current call passed.  Two modes:
+ *  - sampled (SNARKVM_HIP_BASE_CACHE=1/2/4/8/16): by setting the variable the caller promises that such vectors are immutable
+ *    while the process uses them (a hit is verified against raw copies of every 64th point of the slice, which cannot catch
+ *    every mutation);
+ *  - verified (SNARKVM_HIP_BASE_CACHE=verified, the 16-table geometry, or verified:1/2/4/8/16): the registering call also
+ *    copies the 97 payload bytes of every point (x, y, infinity flag; never the padding) into a host shadow, and every hit
+ *    compares all npoints x 97 bytes of its slice with it on a small host pool (SNARKVM_HIP_VERIFY_THREADS, default 4, 1..16)
+ *    while the device computes; on any difference the entry is dropped and the call is computed stateless, so the result
+ *    always reflects the bytes passed in and the caller promises nothing.  SNARKVM_HIP_BASE_CACHE_HOST_MB caps the shadow
+ *    bytes (default 4096).
+ * SNARKVM_HIP_BASE_CACHE_MB caps the HBM bytes per device (default 65536); least recently used ranges go first.  Switching
+ * between the modes drops every cached range.  Code that can be changed should call snarkvm_hip_register_bases* +
+ * snarkvm_hip_msm_registered*.
+ * snarkvm_hip_set_base_cache(tables) / snarkvm_hip_set_base_cache_verified(tables) are the API forms of the variable (0, 1, 2, 4, 8 or
+ * 16; they override the environment from then on and need no device; 0 means off and also drops every cached range) - for a host
+ * that cannot set the environment before the library is loaded. */
 RustError snarkvm_hip_set_base_cache(int tables);
+RustError snarkvm_hip_set_base_cache_verified(int tables);
+/* What the base cache of snarkvm_msm did since the last reset: out[8] = {lookups, hits (results served from the cached tables; in
+ * verified mode only after the comparison agreed), registrations, verification mismatches, bytes compared, microseconds callers
+ * waited for their comparison after their device result was ready, tables in effect (0: off), verified mode (0 / 1)}; reset != 0
+ * clears the first six. */
+void snarkvm_hip_base_cache_stats(uint64_t *out, int reset);
 
 /* ---------------------------------------------------------------------------------------------
  * Part 2 - extension ABI (device-resident data, SRS registration, instrumentation)

@@ -70,6 +70,21 @@ inline Projective msm(const Affine* points, size_t npoints_available, const Scal
     return ret;
 }
 
+// Opt-in base cache of msm() (snarkvm_hip.h: snarkvm_hip_set_base_cache*): tables 0 (off), 1, 2, 4, 8 or 16; verified = every byte of
+// every hit is compared with a host copy taken at registration.
+inline void set_base_cache(int tables, bool verified = false) {
+    check(verified ? snarkvm_hip_set_base_cache_verified(tables) : snarkvm_hip_set_base_cache(tables));
+}
+// {lookups, hits, registrations, verification mismatches, bytes compared, microseconds waited for a comparison, tables, verified}
+struct BaseCacheStats {
+    uint64_t v[8];
+};
+inline BaseCacheStats base_cache_stats(bool reset = false) {
+    BaseCacheStats s{};
+    snarkvm_hip_base_cache_stats(s.v, reset ? 1 : 0);
+    return s;
+}
+
 // ---- extensions (part 2 of rust/snarkvm-algorithms-hip/src/lib.rs: `resident`) -------------------------------------------
 // Deferred-synchronisation scope (snarkvm_hip.h: snarkvm_hip_scope_begin / _end): device-resident calls of this thread between
 // construction and destruction are enqueued on one stream and waited for once.  Not copyable; end() reports errors, the

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("SNARKVM_HIP_LIB") or os.path.join(_HERE, "lib", "libs
 
 # every symbol include/snarkvm_hip.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
-    "snarkvm_ntt", "snarkvm_polymul", "snarkvm_msm", "snarkvm_hip_set_base_cache",
+    "snarkvm_ntt", "snarkvm_polymul", "snarkvm_msm", "snarkvm_hip_set_base_cache", "snarkvm_hip_set_base_cache_verified", "snarkvm_hip_base_cache_stats",
     "snarkvm_hip_device_count", "snarkvm_hip_batch_lanes", "snarkvm_hip_set_device", "snarkvm_hip_set_devices", "snarkvm_hip_num_devices",
     "snarkvm_hip_malloc", "snarkvm_hip_free", "snarkvm_hip_memcpy_h2d", "snarkvm_hip_memcpy_d2h", "snarkvm_hip_memcpy_d2d", "snarkvm_hip_memset", "snarkvm_hip_ntt_device", "snarkvm_hip_ntt_device_batch",
     "snarkvm_hip_scope_begin", "snarkvm_hip_scope_end", "snarkvm_hip_scope_begin_ex", "snarkvm_hip_scope_collect", "snarkvm_hip_scope_set_flags", "snarkvm_hip_scope_stream", "snarkvm_hip_alloc_stats",
@@ -65,7 +65,7 @@ def lib():
             except ImportError:
                 pass
         L = ctypes.CDLL(LIB_PATH)
-        err_fns = ["snarkvm_ntt", "snarkvm_polymul", "snarkvm_msm", "snarkvm_hip_set_base_cache", "snarkvm_hip_set_device", "snarkvm_hip_set_devices",
+        err_fns = ["snarkvm_ntt", "snarkvm_polymul", "snarkvm_msm", "snarkvm_hip_set_base_cache", "snarkvm_hip_set_base_cache_verified", "snarkvm_hip_set_device", "snarkvm_hip_set_devices",
                    "snarkvm_hip_malloc", "snarkvm_hip_free", "snarkvm_hip_memcpy_h2d", "snarkvm_hip_memcpy_d2h", "snarkvm_hip_memcpy_d2d", "snarkvm_hip_memset", "snarkvm_hip_ntt_device", "snarkvm_hip_ntt_device_batch",
                    "snarkvm_hip_scope_begin", "snarkvm_hip_scope_end", "snarkvm_hip_scope_begin_ex", "snarkvm_hip_scope_collect", "snarkvm_hip_scope_set_flags",
                    "snarkvm_hip_register_bases", "snarkvm_hip_register_bases_tables", "snarkvm_hip_register_bases_windowed", "snarkvm_hip_msm_registered", "snarkvm_hip_msm_g2", "snarkvm_hip_msm_registered_ex", "snarkvm_hip_msm_registered_batch", "snarkvm_hip_msm_registered_batch_ex", "snarkvm_hip_g1_to_affine", "snarkvm_hip_fr_mul_device",
@@ -98,12 +98,14 @@ def lib():
         L.snarkvm_hip_free_bases_g2.restype = None
         L.snarkvm_hip_set_profiling.restype = None
         L.snarkvm_hip_coalescer_stats.restype = None
+        L.snarkvm_hip_base_cache_stats.restype = None
         L.snarkvm_hip_alloc_stats.restype = None
         L.snarkvm_hip_scope_stream.restype = ctypes.c_void_p
         L.snarkvm_hip_scope_begin_ex.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.snarkvm_hip_scope_set_flags.argtypes = [ctypes.c_uint32]
         L.snarkvm_hip_alloc_stats.argtypes = [ctypes.c_void_p, ctypes.c_int]  # (without argtypes a bare Python int address would travel as a 32-bit C int)
         L.snarkvm_hip_coalescer_stats.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.snarkvm_hip_base_cache_stats.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.snarkvm_hip_malloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_int]
         L.snarkvm_hip_free.argtypes = [ctypes.c_void_p]
         L.snarkvm_hip_memcpy_h2d.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "msm", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -73,3 +73,23 @@ def msm(points, scalars):
                                  ctypes.c_size_t(G1_AFFINE.itemsize))
     _lib.check(err)
     return ret
+
+
+BASE_CACHE_STATS = ("lookups", "hits", "registrations", "mismatches", "bytes_compared", "wait_us", "tables", "verified")
+
+
+def set_base_cache(tables, verified=False):
+    """Extension: the API form of SNARKVM_HIP_BASE_CACHE for `msm` (snarkvm_hip_set_base_cache / _verified).  tables 0 (off, drops every
+    cached range), 1, 2, 4, 8 or 16; verified=True compares every byte of every hit with a host copy taken at registration, so the
+    caller need not promise that its base vector never changes.  Overrides the environment; needs no device."""
+    L = _lib.lib()
+    fn = L.snarkvm_hip_set_base_cache_verified if verified else L.snarkvm_hip_set_base_cache
+    _lib.check(fn(ctypes.c_int(int(tables))))
+
+
+def base_cache_stats(reset=False):
+    """Extension: what the base cache of `msm` did since the last reset (snarkvm_hip_base_cache_stats) as a dict with the keys of
+    BASE_CACHE_STATS; reset=True clears the counters (not `tables` / `verified`, the mode in effect)."""
+    v = (ctypes.c_uint64 * 8)()
+    _lib.lib().snarkvm_hip_base_cache_stats(v, 1 if reset else 0)
+    return dict(zip(BASE_CACHE_STATS, (int(x) for x in v)))
