@@ -42,8 +42,9 @@ enum NTTType { Standard = 0, Coset = 1 };                    /* lib.rs:36-40 */
 /* lib.rs:43-49 / snarkvm_api.cu:53-62.  In-place NTT of 2^lg_domain_size Fr elements (32 B each,
  * Montgomery form, host memory).  NN/Forward/Standard == EvaluationDomain::fft_in_place;
  * Inverse includes the 1/n scaling; Forward+Coset multiplies x[j] by 22^j first; Inverse+Coset
- * multiplies the result by 22^-j (fft/domain.rs:201-206, 403-443).  Returns an error for
- * lg_domain_size > 26 (the caller then uses its CPU path). */
+ * multiplies the result by 22^-j (fft/domain.rs:201-206, 403-443).  Domains up to 2^28 (the SRS maximum);
+ * lg_domain_size > 28 returns hipErrorMemoryAllocation (the caller then uses its CPU path), and so does a
+ * device allocation that fails. */
 RustError snarkvm_ntt(void *inout, uint32_t lg_domain_size, enum NTTInputOutputOrder ntt_order,
                       enum NTTDirection ntt_direction, enum NTTType ntt_type);
 
@@ -51,7 +52,8 @@ RustError snarkvm_ntt(void *inout, uint32_t lg_domain_size, enum NTTInputOutputO
  * `ecount` evaluation-form vectors over the 2^lg_domain_size domain (PolyMultiplier::multiply,
  * fft/polynomial/multiplier.rs:70-134).  `polynomials` / `evaluations` are arrays of pointers to Fr
  * vectors, `plens` / `elens` their lengths (size_t); every elens[i] must equal the domain size.
- * `out` holds 2^lg_domain_size elements.  Corner cases follow snarkvm.cu:196-210. */
+ * `out` holds 2^lg_domain_size elements.  Corner cases follow snarkvm.cu:196-210.  lg_domain_size <= 28, as for snarkvm_ntt; the
+ * device holds four vectors of the domain (8 GiB each at 2^28). */
 RustError snarkvm_polymul(void *out, size_t pcount, const void *polynomials, const void *plens, size_t ecount,
                           const void *evaluations, const void *elens, uint32_t lg_domain_size);
 
@@ -130,14 +132,15 @@ RustError snarkvm_hip_memcpy_d2h(void *dst, const void *d_src, size_t bytes);
 RustError snarkvm_hip_memcpy_d2d(void *d_dst, const void *d_src, size_t bytes);
 RustError snarkvm_hip_memset(void *d_dst, int value, size_t bytes);
 
-/* Same as snarkvm_ntt but `d_inout` is device memory (the call runs on the device that owns it). */
+/* Same as snarkvm_ntt but `d_inout` is device memory (the call runs on the device that owns it).  lg_domain_size <= 28. */
 RustError snarkvm_hip_ntt_device(void *d_inout, uint32_t lg_domain_size, int ntt_order, int ntt_direction,
                                  int ntt_type);
 /* `count` independent in-place transforms of 2^lg_domain_size elements over device vectors on one device: one enqueue, ONE
  * synchronisation (the iNTTs of a prover round, e.g. z_a, z_b, z_c: algorithms/src/snark/varuna/ahp/prover/round_functions/
  * second.rs:104-113).  ntt_directions / ntt_types: one value per vector, or NULL for all forward / all standard.  A vector
  * listed twice is transformed twice, in list order.  Consecutive distinct vectors with the same direction and type share ONE
- * kernel launch per pass (up to 48 vectors). */
+ * kernel launch per pass (up to 48 vectors; 24 at 2^27 and 12 at 2^28, so that the scratch stays within 48 vectors of 2^26).
+ * lg_domain_size <= 28. */
 RustError snarkvm_hip_ntt_device_batch(void *const *d_inouts, size_t count, uint32_t lg_domain_size, int ntt_order,
                                        const int *ntt_directions, const int *ntt_types);
 
@@ -422,6 +425,19 @@ RustError snarkvm_hip_devtest_g2_tail_repeat(const void *points, size_t npoints,
  * to nine butterfly stages without a canonical form in between, the closing product, the bare reduction and the folded table
  * form.  0 = identical; > 0: first differing butterfly; < 0: a closing-step case. */
 int snarkvm_hip_selftest_fr_signed(uint64_t seed, int iters);
+/* The NTT's planner, power tables and index maps (csrc/ntt.hip.h) run on the host through the kernels' own __host__ __device__ code.
+ * ntt_plan: out[4] = the pass radices (log2) of the 2^lg plan; returns the number of passes, -1 when lg > 28. */
+int snarkvm_hip_selftest_ntt_plan(uint32_t lg, int32_t *out);
+/* kind 0: out[i] = the closing twiddle pass `pass` of the 2^lg transform multiplies by for inner * k = x[i] (pass = -1: W^x[i] with W the
+ * primitive 2^28-th root); kind 1: out[i] = g^x[i], g = 22.  inverse = 1: of W^-1 / g^-1.  n values of 32 bytes, memory Montgomery form.
+ * 0, or -1 when an argument or exponent is out of range. */
+int snarkvm_hip_selftest_ntt_twiddle(int kind, uint32_t lg, int pass, int inverse, const uint64_t *x, size_t n, void *out);
+/* The tile addressing of every pass and the last pass' output index map of the 2^lg plan (plan = NULL: the backend's; else npass forced
+ * radices), indices only: returns the number of positions read or written twice, or holding another coefficient than NN order puts there. */
+int snarkvm_hip_selftest_ntt_index(uint32_t lg, const int32_t *plan, int npass);
+/* The whole NN transform of 2^lg <= 2^16 elements (memory form, in place) computed on the host pass by pass in exact arithmetic over the
+ * kernels' addressing, twiddles, coset powers and output map (plan = NULL: the backend's plan; else npass forced radices).  0, or -1. */
+int snarkvm_hip_selftest_ntt_host(void *inout, uint32_t lg, const int32_t *plan, int npass, int dir, int type);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 

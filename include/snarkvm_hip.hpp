@@ -27,7 +27,7 @@ inline void check(RustError e) {
     }
 }
 
-// lib.rs:77-97
+// lib.rs:77-97.  Domains up to 2^28; a larger one throws Error with code hipErrorMemoryAllocation (the caller's CPU path).
 template <class T>
 inline void NTT(size_t domain_size, T* inout, NTTInputOutputOrder order, NTTDirection direction, NTTType type) {
     static_assert(sizeof(T) == 32, "the NTT operates on 32-byte Fr elements (fft/domain.rs:377)");
@@ -37,7 +37,7 @@ inline void NTT(size_t domain_size, T* inout, NTTInputOutputOrder order, NTTDire
     check(snarkvm_ntt(inout, lg, order, direction, type));
 }
 
-// lib.rs:100-145: returns a vector of `domain` elements pre-filled with `zero`
+// lib.rs:100-145: returns a vector of `domain` elements pre-filled with `zero`; domains up to 2^28, as for NTT
 template <class T>
 inline std::vector<T> polymul(size_t domain, const std::vector<std::vector<T>>& polynomials,
                               const std::vector<std::vector<T>>& evaluations, const T& zero) {

@@ -8,7 +8,7 @@ extern "C" {
 
 // ---- NTT -------------------------------------------------------------------------------------
 static void check_ntt_args(uint32_t lg, int order, int dir, int type) {
-    if (lg > (uint32_t)NTT_LG_MAX) throw hip_failure{hipErrorMemoryAllocation, "ntt: lg_domain_size > 26 is not supported by this backend", __LINE__};
+    if (lg > (uint32_t)NTT_LG_MAX) throw hip_failure{hipErrorMemoryAllocation, "ntt: lg_domain_size > 28 is not supported by this backend", __LINE__};
     if (order < 0 || order > 3 || dir < 0 || dir > 1 || type < 0 || type > 1) throw hip_failure{hipErrorInvalidValue, "ntt: bad enum value", __LINE__};
 }
 RustError snarkvm_ntt(void* inout, uint32_t lg, enum NTTInputOutputOrder order, enum NTTDirection dir, enum NTTType type) {
@@ -63,13 +63,15 @@ RustError snarkvm_hip_ntt_device_batch(void* const* d_inouts, size_t count, uint
     // (blockIdx.y = vector; tuning ntt_batch=0: one launch sequence per vector).  List order is preserved between runs, so a
     // vector listed twice is still transformed twice, in order.
     const bool can_batch = tuning().ntt_batch && order == NTT_NN && lg > 8;
+    // a run's scratch (run length x 2^lg elements) stays within that of NTT_BATCH_MAX vectors of 2^26: 24 vectors at 2^27, 12 at 2^28
+    const size_t run_max = lg <= (uint32_t)NTT_TW_LG ? (size_t)NTT_BATCH_MAX : ((size_t)NTT_BATCH_MAX << NTT_TW_LG) >> lg;
     std::vector<std::pair<size_t, size_t>> runs;
     size_t max_run = 1;
     for (size_t k = 0; k < count;) {
         const int dir = dirs ? dirs[k] : 0, type = types ? types[k] : 0;
         size_t e = k + 1;
         if (can_batch) {
-            while (e < count && e - k < (size_t)NTT_BATCH_MAX && (dirs ? dirs[e] : 0) == dir && (types ? types[e] : 0) == type) {
+            while (e < count && e - k < run_max && (dirs ? dirs[e] : 0) == dir && (types ? types[e] : 0) == type) {
                 bool dup = false;
                 for (size_t q = k; q < e && !dup; q++) dup = d_inouts[q] == d_inouts[e];
                 if (dup) break;
@@ -640,4 +642,219 @@ int snarkvm_hip_selftest_fr_signed(uint64_t seed, int iters) {
     return 0;
 }
 
+// ---- test hooks: the NTT's plan, twiddle / coset-power composition and index maps, on the host --------------------------------------
+// Every function below calls the same __host__ __device__ code as ntt_pass_kernel_v2 and the driver (ntt.hip.h).
+// the pass radices of the 2^lg plan -> out[0 .. 3]; returns the number of passes, -1 when lg is rejected
+int snarkvm_hip_selftest_ntt_plan(uint32_t lg, int32_t* out) {
+    const ntt_plan_t pl = ntt_make_plan(lg > 1024 ? -1 : (int)lg);
+    for (int i = 0; i < NTT_MAX_PASSES; i++) out[i] = pl.a[i];
+    return pl.npass ? pl.npass : -1;
+}
+
+// the device's tables, built on the host by the set-up code of the kernels
+static const ntt_tables_t& ntt_host_tables() {
+    static std::vector<fr_mem_t> mem;
+    static ntt_tables_t tb{};
+    static std::once_flag once;
+    std::call_once(once, [] {
+        mem.resize(8 * NTT_TW_SIZE + 2 * NTT_LOCAL + 4 * NTT_TOP + 32 + 8);
+        size_t off = 0;
+        auto take = [&](size_t n) {
+            fr_mem_t* r = mem.data() + off;
+            off += n;
+            return r;
+        };
+        for (int d = 0; d < 2; d++) {
+            tb.pow_lo[d] = take(NTT_TW_SIZE);
+            tb.pow_hi[d] = take(NTT_TW_SIZE);
+            tb.g_lo[d] = take(NTT_TW_SIZE);
+            tb.g_hi[d] = take(NTT_TW_SIZE);
+            tb.local[d] = take(NTT_LOCAL);
+            tb.pow_top[d] = take(NTT_TOP);
+            tb.g_top[d] = take(NTT_TOP);
+        }
+        tb.size_inv = take(32);
+        tb.consts = take(8);
+        ntt_setup_consts_on(tb);
+        for (int i = 0; i < NTT_TW_SIZE; i++) ntt_fill_tables_at(tb, i);
+    });
+    return tb;
+}
+static bool ntt_plan_from(uint32_t lg, const int32_t* plan, int npass, ntt_plan_t& pl) {
+    if (lg > (uint32_t)NTT_LG_MAX) return false;
+    if (!plan) {
+        pl = ntt_make_plan((int)lg);
+        return pl.npass > 0;
+    }
+    if (npass < 1 || npass > NTT_MAX_PASSES) return false;
+    int sum = 0;
+    for (int i = 0; i < NTT_MAX_PASSES; i++) {
+        pl.a[i] = i < npass ? plan[i] : 0;
+        if (i < npass && (pl.a[i] < 1 || pl.a[i] > NTT_MAX_RADIX_LG) && !(npass == 1 && pl.a[i] == 0)) return false;
+        sum += pl.a[i];
+    }
+    pl.npass = npass;
+    return sum == (int)lg;
+}
+
+// kind 0: out[i] = the closing twiddle of pass `pass` of the 2^lg transform for inner * k = x[i], i.e. W28^(x[i] << tw_shift)
+//         (pass = -1: W28^x[i] itself), inverse: of W28^-1;
+// kind 1: out[i] = g^x[i] (inverse: g^-x[i]).  Values in memory Montgomery form.  0, or -1: an argument or exponent out of range.
+int snarkvm_hip_selftest_ntt_twiddle(int kind, uint32_t lg, int pass, int inverse, const uint64_t* x, size_t n, void* out) {
+    const ntt_tables_t& tb = ntt_host_tables();
+    int shift = 0;
+    if (kind == 0 && pass >= 0) {
+        ntt_plan_t pl;
+        if (!ntt_plan_from(lg, nullptr, 0, pl) || pass >= pl.npass - 1) return -1;
+        shift = ntt_pass_geometry(pl, (int)lg, pass).tw_shift;
+    }
+    if ((kind != 0 && kind != 1) || (inverse != 0 && inverse != 1)) return -1;
+    fr_mem_t* o = (fr_mem_t*)out;
+    for (size_t i = 0; i < n; i++) {
+        if (x[i] >= ((uint64_t)1 << (NTT_LG_MAX - shift))) return -1;
+        const uint32_t e = (uint32_t)(x[i] << shift);
+        const fr_t w = kind == 0 ? ntt_twiddle(tb, inverse, e) : ntt_coset_pow(tb, inverse, e);
+        w.to_mem_mont().store(&o[i]);
+    }
+    return 0;
+}
+
+// Index maps of the 2^lg plan (plan = NULL: the driver's; else npass forced radices), indices only.  Every non-last pass must read and
+// write each position once and put its output digit at the position the next passes read it from; the last pass must write every
+// output index once, and the value it writes at index f must be the transform's coefficient f: the digits the earlier passes left in
+// its input position (leading digit first) followed by the last pass' own digit.  Returns the number of violations (saturated), -1: bad
+// arguments.
+int snarkvm_hip_selftest_ntt_index(uint32_t lg, const int32_t* plan, int npass) {
+    ntt_plan_t pl;
+    if (!ntt_plan_from(lg, plan, npass, pl)) return -1;
+    const size_t n = (size_t)1 << lg;
+    size_t bad = 0;
+    std::vector<uint8_t> seen_in(n), seen_out(n);
+    int consumed = 0;
+    for (int k = 0; k < pl.npass; k++) {
+        ntt_pass_t p = ntt_pass_geometry(pl, (int)lg, k);
+        std::fill(seen_in.begin(), seen_in.end(), 0);
+        std::fill(seen_out.begin(), seen_out.end(), 0);
+        const int R = 1 << p.a;
+        if (!p.last) {
+            p.lgT = ntt_tile_lg(p.a, p.s, (int)lg);
+            const size_t tiles = n >> (p.a + p.lgT);
+            const int digit_at = (int)lg - consumed - p.a;  // where the next passes read this pass' digit
+            for (size_t t = 0; t < tiles; t++) {
+                const ntt_inner_tile_t it = ntt_inner_tile(p, t);
+                for (int col = 0; col < (1 << p.lgT); col++)
+                    for (int row = 0; row < R; row++) {
+                        const size_t in = it.in_base + ((size_t)row << p.s) + col;
+                        const uint32_t d = bitrev32((uint32_t)row, p.a);
+                        const size_t o = it.in_base + ((size_t)d << p.s) + col;
+                        if (in >= n || o >= n || seen_in[in]++ || seen_out[o]++) {
+                            bad++;
+                            continue;
+                        }
+                        const size_t mask = (size_t)(R - 1) << digit_at;
+                        if (((o & mask) >> digit_at) != d || (o & ~mask) != (in & ~mask)) bad++;
+                    }
+            }
+        } else {
+            p.lgT = ntt_tile_lg(p.a, p.a1, (int)lg);
+            const size_t tiles = n >> (p.a + p.lgT);
+            const size_t col_stride = (size_t)1 << (lg - p.a1);
+            for (size_t t = 0; t < tiles; t++) {
+                const ntt_last_tile_t lt = ntt_last_tile(p, t);
+                for (int col = 0; col < (1 << p.lgT); col++)
+                    for (int row = 0; row < R; row++) {
+                        const size_t in = lt.in_base + row + col * col_stride;
+                        const size_t o = ntt_last_out_index(p, t, row, col);
+                        if (in >= n || o >= n || seen_in[in]++ || seen_out[o]++) {
+                            bad++;
+                            continue;
+                        }
+                        // the coefficient this slot holds: the earlier digits in memory (leading first) + the last pass' digit
+                        size_t f = 0;
+                        int at = 0, top = (int)lg;
+                        for (int i = 0; i + 1 < pl.npass; i++) {
+                            top -= pl.a[i];
+                            f |= ((in >> top) & (((size_t)1 << pl.a[i]) - 1)) << at;
+                            at += pl.a[i];
+                        }
+                        if ((in & (((size_t)1 << top) - 1)) != (size_t)row) bad++;  // the row is the last pass' input digit
+                        f |= (size_t)bitrev32((uint32_t)row, p.a) << at;
+                        if (f != o) bad++;
+                    }
+            }
+        }
+        consumed += p.a;
+    }
+    return bad > 0x7fffffff ? 0x7fffffff : (int)bad;
+}
+
+// The whole NN transform of 2^lg (<= 2^16) elements on the host in exact arithmetic, pass by pass as ntt_run_nn schedules it (plan = NULL:
+// the driver's plan; else npass forced radices): every pass a plain DFT of its radix over the kernels' tile addressing, the kernels'
+// closing twiddles, coset powers and output index map.  inout: memory Montgomery form.  0, or -1: bad arguments.
+int snarkvm_hip_selftest_ntt_host(void* inout, uint32_t lg, const int32_t* plan, int npass, int dir, int type) {
+    ntt_plan_t pl;
+    if (lg > 16 || !ntt_plan_from(lg, plan, npass, pl) || dir < 0 || dir > 1 || type < 0 || type > 1) return -1;
+    if (lg == 0) return 0;
+    const ntt_tables_t& tb = ntt_host_tables();
+    const size_t n = (size_t)1 << lg;
+    std::vector<fr_t> cur(n), nxt(n);
+    fr_mem_t* io = (fr_mem_t*)inout;
+    for (size_t i = 0; i < n; i++) cur[i] = fr_t::load(&io[i]).from_mem_mont();
+    for (int k = 0; k < pl.npass; k++) {
+        ntt_pass_t p = ntt_pass_geometry(pl, (int)lg, k);
+        const int R = 1 << p.a;
+        std::vector<fr_t> x(R);
+        // powers of this pass' own root w_(2^a) = W28^(2^(28 - a))
+        std::vector<fr_t> wr(R);
+        for (int e = 0; e < R; e++) wr[e] = ntt_twiddle(tb, dir, (uint32_t)e << (NTT_LG_MAX - p.a));
+        auto dft = [&](int d) {
+            fr_t acc = fr_t::zero();
+            for (int j = 0; j < R; j++) acc = acc + x[j] * wr[(j * d) & (R - 1)];
+            return acc;
+        };
+        if (!p.last) {
+            p.lgT = ntt_tile_lg(p.a, p.s, (int)lg);
+            for (size_t t = 0; t < (n >> (p.a + p.lgT)); t++) {
+                const ntt_inner_tile_t it = ntt_inner_tile(p, t);
+                for (int col = 0; col < (1 << p.lgT); col++) {
+                    for (int j = 0; j < R; j++) {
+                        const size_t g = it.in_base + ((size_t)j << p.s) + col;
+                        x[j] = cur[g];
+                        if (k == 0 && dir == NTT_FORWARD && type == NTT_COSET) x[j] = x[j] * ntt_coset_pow(tb, 0, (uint32_t)g);
+                    }
+                    for (int row = 0; row < R; row++) {
+                        const uint32_t d = bitrev32((uint32_t)row, p.a);
+                        const uint32_t expo = (uint32_t)(((it.inner0 + col) * (size_t)d) << p.tw_shift);
+                        nxt[it.in_base + ((size_t)d << p.s) + col] = dft((int)d) * ntt_twiddle(tb, dir, expo);
+                    }
+                }
+            }
+        } else {
+            p.lgT = ntt_tile_lg(p.a, p.a1, (int)lg);
+            const size_t col_stride = (size_t)1 << (lg - p.a1);
+            for (size_t t = 0; t < (n >> (p.a + p.lgT)); t++) {
+                const ntt_last_tile_t lt = ntt_last_tile(p, t);
+                for (int col = 0; col < (1 << p.lgT); col++) {
+                    for (int j = 0; j < R; j++) {
+                        const size_t g = lt.in_base + j + col * col_stride;
+                        x[j] = cur[g];
+                        if (pl.npass == 1 && dir == NTT_FORWARD && type == NTT_COSET) x[j] = x[j] * ntt_coset_pow(tb, 0, (uint32_t)g);
+                    }
+                    for (int row = 0; row < R; row++) {
+                        const size_t g = ntt_last_out_index(p, t, row, col);
+                        fr_t y = dft((int)bitrev32((uint32_t)row, p.a));
+                        if (dir == NTT_INVERSE) y = y * fr_t::load(&tb.size_inv[lg]);
+                        if (dir == NTT_INVERSE && type == NTT_COSET) y = y * ntt_coset_pow(tb, 1, (uint32_t)g);
+                        nxt[g] = y;
+                    }
+                }
+            }
+        }
+        cur.swap(nxt);
+    }
+    for (size_t i = 0; i < n; i++) cur[i].to_mem_mont().store(&io[i]);
+    return 0;
+}
+
 }  // extern "C"
+

@@ -4,12 +4,12 @@
 // algorithms/cuda/cuda/snarkvm.cu:154-186 and polynomial.cuh:104-266, and the CPU transforms of
 // algorithms/src/fft/domain.rs:374-443 (in_order_fft / ifft / coset_ifft), :691-773 (io/oi helpers).
 //
-// Structure (MI355X-first): a 2^lg transform is split into at most three passes of radix <= 2^8
-// ("four-step" decomposition applied recursively).  One workgroup stages a [2^a rows] x [T columns]
+// Structure (MI355X-first): a 2^lg transform is split into at most three passes of radix <= 2^9 up to 2^27, four passes of radix 2^7
+// at 2^28 ("four-step" decomposition applied recursively).  One workgroup stages a [2^a rows] x [T columns]
 // tile of 32-byte elements in LDS (<= 64 KiB), runs the a radix-2 DIF stages there with __syncthreads
 // between stages, and writes the tile back:
 //   * non-last pass: in place (same addresses), each element multiplied by the inter-pass twiddle
-//     w_L^(inner*k) looked up from a two-level power table (2 x 4096 entries, L2-resident);
+//     w_L^(inner*k) looked up from a two-level power table (2 x 8192 entries, L2-resident);
 //   * last pass: rows are contiguous; the output index is digit-reversed so the result lands in
 //     natural (NN) order.  This pass is out-of-place (another workgroup still needs the slots it
 //     would overwrite), hence the ping-pong with a scratch buffer in ntt_run().
@@ -17,6 +17,10 @@
 // passes * 2 * 32 * n bytes (algorithmic minimum 2 * 32 * n: SURVEY.md 8d).  Twiddles are never
 // streamed from HBM: per-stage twiddles come from a 256-entry table of w_512 powers staged in LDS.
 //
+// Exponents: a twiddle exponent is counted in powers of W28 (primitive 2^28-th root, e < 2^28).  The two-level tables hold powers
+// of W26 = W28^4 and cover e >> 2; a four-entry table W28^(0..3) covers e & 3.  That last factor is only ever != 1 in 2^27 and 2^28
+// transforms, so every smaller transform reads the same table words with the same products as before.  Coset powers g^j likewise:
+// j & 8191, (j >> 13) & 8191 from the two-level tables, g^(2^26 (j >> 26)) from a four-entry table.
 // Data stays in the reference's memory form (Montgomery, R = 2^256) throughout; see ff.hip.h for why the
 // 29-bit-limb arithmetic needs no conversion on this (linear) path.
 #pragma once
@@ -30,10 +34,13 @@
 
 namespace sv {
 
-static constexpr int NTT_LG_MAX = 26;     // two-level tables cover exponents < 2^26 (2 GiB vectors; larger domains: the caller's CPU path)
+static constexpr int NTT_LG_MAX = 28;     // the SRS maximum (8 GiB vectors); larger domains: the caller's CPU path
+static constexpr int NTT_TW_LG = 26;      // the two-level tables hold powers of W26 = W28^4: exponents < 2^26
 static constexpr int NTT_TW_BITS = 13;    // w^e = hi[e >> 13] * lo[e & 8191]
 static constexpr int NTT_TW_SIZE = 1 << NTT_TW_BITS;
-static constexpr int NTT_MAX_RADIX_LG = 9;  // passes of radix <= 2^8 up to 2^24; 2^25 / 2^26 use radix-2^9 passes on narrower tiles
+static constexpr int NTT_TOP = 1 << (NTT_LG_MAX - NTT_TW_LG);  // entries of the top tables: W28^t, g^(2^26 t)
+static constexpr int NTT_MAX_PASSES = 4;
+static constexpr int NTT_MAX_RADIX_LG = 9;  // passes of radix <= 2^8 up to 2^24; 2^25 - 2^27 use radix-2^9 passes on narrower tiles
 static constexpr int NTT_LOCAL = 1 << (NTT_MAX_RADIX_LG - 1);  // per-stage twiddles: powers of w_512 staged in LDS
 
 // order / direction / type enums: algorithms/cuda/src/lib.rs:22-40
@@ -43,31 +50,46 @@ enum { NTT_STANDARD = 0, NTT_COSET = 1 };
 
 // Device-resident tables (internal Montgomery form, packed 32 B per entry).
 struct ntt_tables_t {
-    fr_mem_t* pow_lo[2];   // [dir][4096]  W^(+-i)          W = primitive 2^24-th root of unity
-    fr_mem_t* pow_hi[2];   // [dir][4096]  W^(+-4096 i)
+    fr_mem_t* pow_lo[2];   // [dir][8192]  W26^(+-i)        W26 = primitive 2^26-th root of unity
+    fr_mem_t* pow_hi[2];   // [dir][8192]  W26^(+-8192 i)
+    fr_mem_t* pow_top[2];  // [dir][4]     W28^(+-t)        W28 = primitive 2^28-th root, W28^4 = W26
     fr_mem_t* local[2];    // [dir][NTT_LOCAL]   w_512^(+-i)
     fr_mem_t* g_lo[2];     // [0]: g^i  [1]: g^-i          g = 22 (fr.rs:126-135)
-    fr_mem_t* g_hi[2];     //      g^(+-4096 i)
-    fr_mem_t* size_inv;    // [25]  (2^lg)^-1
+    fr_mem_t* g_hi[2];     //      g^(+-8192 i)
+    fr_mem_t* g_top[2];    //      g^(+-2^26 t)
+    fr_mem_t* size_inv;    // [NTT_LG_MAX + 1]  (2^lg)^-1
     fr_mem_t* consts;      // scratch for the set-up kernels
 };
 
-// TWO_ADIC_ROOT_OF_UNITY (fr.rs:115-120), memory form (a * 2^256), 32-bit words
-__device__ static const uint32_t FR_TWO_ADIC_ROOT_MEM[8] = {0xda3ad648u, 0xaf80da4du, 0xfc381dacu, 0x5e223adbu,
-                                                             0xb2f92525u, 0x03ba0666u, 0x3befb0ceu, 0x0f906c5bu};
+// TWO_ADIC_ROOT_OF_UNITY (fr.rs:115-120), memory form (a * 2^256), 32-bit words -> primitive 2^lg-th root, internal form
+SV_HD fr_t ntt_root_of_unity(int lg) {
+    const uint32_t FR_TWO_ADIC_ROOT_MEM[8] = {0xda3ad648u, 0xaf80da4du, 0xfc381dacu, 0x5e223adbu,
+                                              0xb2f92525u, 0x03ba0666u, 0x3befb0ceu, 0x0f906c5bu};
+    fr_t w = fr_t::unpack(FR_TWO_ADIC_ROOT_MEM).from_mem_mont();  // 2^47-th root
+    for (int i = 0; i < 47 - lg; i++) w = w.sqr();
+    return w;
+}
 
-// consts[0] = W, [1] = W^-1, [2] = g, [3] = g^-1, then size_inv[0..24]
-static __global__ void ntt_setup_consts(ntt_tables_t t) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint32_t w8[8];
-    for (int i = 0; i < 8; i++) w8[i] = FR_TWO_ADIC_ROOT_MEM[i];
-    fr_t w = fr_t::unpack(w8).from_mem_mont();          // 2^47-th root, internal form
-    for (int i = 0; i < 47 - NTT_LG_MAX; i++) w = w.sqr();  // -> primitive 2^NTT_LG_MAX-th root
+// The table set-up, shared by the device (ntt_setup_consts / ntt_fill_tables) and the host self-test (snarkvm_hip_selftest_ntt_twiddle).
+// consts[0] = W26, [1] = W26^-1, [2] = g, [3] = g^-1; the top tables and size_inv[0..NTT_LG_MAX]
+SV_HD void ntt_setup_consts_on(const ntt_tables_t& t) {
+    const fr_t w28 = ntt_root_of_unity(NTT_LG_MAX);
+    fr_t w = w28;
+    for (int i = 0; i < NTT_LG_MAX - NTT_TW_LG; i++) w = w.sqr();  // -> W26
     fr_t g = fr_t::from_u32(22);
     w.store(&t.consts[0]);
     w.inverse().store(&t.consts[1]);
     g.store(&t.consts[2]);
     g.inverse().store(&t.consts[3]);
+    const fr_t w28i = w28.inverse(), g26 = g.pow_u64((uint64_t)1 << NTT_TW_LG), g26i = g26.inverse();
+    fr_t p[4] = {fr_t::one(), fr_t::one(), fr_t::one(), fr_t::one()};
+    for (int i = 0; i < NTT_TOP; i++) {
+        p[0].store(&t.pow_top[0][i]);
+        p[1].store(&t.pow_top[1][i]);
+        p[2].store(&t.g_top[0][i]);
+        p[3].store(&t.g_top[1][i]);
+        p[0] = p[0] * w28, p[1] = p[1] * w28i, p[2] = p[2] * g26, p[3] = p[3] * g26i;
+    }
     fr_t half = fr_t::from_u32(2).inverse();
     fr_t cur = fr_t::one();
     for (int lg = 0; lg <= NTT_LG_MAX; lg++) {
@@ -75,19 +97,50 @@ static __global__ void ntt_setup_consts(ntt_tables_t t) {
         cur = cur * half;
     }
 }
-// lo[i] = b^i, hi[i] = b^(4096 i) for the four bases; local[dir][i] = (W^+-1)^(65536 i)
-static __global__ void ntt_fill_tables(ntt_tables_t t) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= NTT_TW_SIZE) return;
+// lo[i] = b^i, hi[i] = b^(8192 i) for the four bases; local[dir][i] = (W26^+-1)^(2^17 i)
+SV_HD void ntt_fill_tables_at(const ntt_tables_t& t, int i) {
     for (int which = 0; which < 4; which++) {
         fr_t b = fr_t::load(&t.consts[which]);
         fr_mem_t* lo = which < 2 ? t.pow_lo[which] : t.g_lo[which - 2];
         fr_mem_t* hi = which < 2 ? t.pow_hi[which] : t.g_hi[which - 2];
         b.pow_u64((uint64_t)i).store(&lo[i]);
         b.pow_u64((uint64_t)i << NTT_TW_BITS).store(&hi[i]);
-        if (which < 2 && i < NTT_LOCAL) b.pow_u64((uint64_t)i << (NTT_LG_MAX - NTT_MAX_RADIX_LG)).store(&t.local[which][i]);
+        if (which < 2 && i < NTT_LOCAL) b.pow_u64((uint64_t)i << (NTT_TW_LG - NTT_MAX_RADIX_LG)).store(&t.local[which][i]);
     }
 }
+static __global__ void ntt_setup_consts(ntt_tables_t t) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    ntt_setup_consts_on(t);
+}
+static __global__ void ntt_fill_tables(ntt_tables_t t) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= NTT_TW_SIZE) return;
+    ntt_fill_tables_at(t, i);
+}
+
+// ---- twiddle and coset-power composition (host and device) ----
+// W28^e, e < 2^28: lo[(e >> 2) & 8191] * hi[e >> 15] * top[e & 3]; a factor whose index is 0 (the value one) is skipped, so an
+// exponent that is a multiple of 4 and below 2^15 costs no product at all
+struct ntt_pow_idx_t {
+    uint32_t lo, hi, top;
+};
+SV_HD ntt_pow_idx_t ntt_tw_index(uint32_t e) {
+    const uint32_t e26 = e >> (NTT_LG_MAX - NTT_TW_LG);
+    return ntt_pow_idx_t{e26 & (NTT_TW_SIZE - 1), e26 >> NTT_TW_BITS, e & (NTT_TOP - 1)};
+}
+// g^j, j < 2^28: lo[j & 8191] * hi[(j >> 13) & 8191] * top[j >> 26]
+SV_HD ntt_pow_idx_t ntt_coset_index(uint32_t j) {
+    return ntt_pow_idx_t{j & (NTT_TW_SIZE - 1), (j >> NTT_TW_BITS) & (NTT_TW_SIZE - 1), j >> NTT_TW_LG};
+}
+SV_HD fr_t ntt_pow_compose(const fr_mem_t* lo, const fr_mem_t* hi, const fr_mem_t* top, ntt_pow_idx_t x) {
+    fr_t w = fr_t::load(&lo[x.lo]);
+    if (x.hi) w = w * fr_t::load(&hi[x.hi]);
+    if (x.top) w = w * fr_t::load(&top[x.top]);
+    return w;
+}
+// W28^(+-e) (dir) and g^(+-j) (inv) from the device's tables
+SV_HD fr_t ntt_twiddle(const ntt_tables_t& tb, int dir, uint32_t e) { return ntt_pow_compose(tb.pow_lo[dir], tb.pow_hi[dir], tb.pow_top[dir], ntt_tw_index(e)); }
+SV_HD fr_t ntt_coset_pow(const ntt_tables_t& tb, int inv, uint32_t j) { return ntt_pow_compose(tb.g_lo[inv], tb.g_hi[inv], tb.g_top[inv], ntt_coset_index(j)); }
 
 struct ntt_pass_t {
     const fr_mem_t* in;
@@ -98,23 +151,66 @@ struct ntt_pass_t {
     int lgT;         // log2 tile width
     int last;        // 1: last pass
     int a1;          // last pass: log2 size of the leading digit (tile dimension); 0 for a single-pass transform
-    int lg_mid;      // last pass: log2 size of the middle digit (three-pass transforms), else 0
+    int lg_mid;      // last pass: log2 size of the middle digits (three- and four-pass transforms), else 0
+    int mid_lo;      // last pass of a four-pass transform: log2 size of the second middle digit (the lower one in memory), else 0
     int dir;         // NTT_FORWARD / NTT_INVERSE
     int coset_pre;   // multiply input j by g^j        (forward coset, first pass)
     int scale_post;  // last pass: 0 none, 1 * n^-1, 2 * g^-k n^-1   (inverse / coset inverse)
-    int tw_shift;    // non-last: twiddle exponent = (inner * k) << tw_shift
+    int tw_shift;    // non-last: twiddle exponent (in powers of W28) = (inner * k) << tw_shift
     const fr_mem_t* tw_full;  // non-last, optional: the closing twiddles of this pass, tw_full[(k << s) + inner] (one product instead of two)
     int reduce_only; // last pass: the previous pass' closing table already carries 2^261 (and n^-1 when inverse): the final
                      // multiplication by one / n^-1 shrinks to a bare Montgomery reduction
 };
 
-__device__ __forceinline__ uint32_t bitrev32(uint32_t x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0u; }
+SV_HD uint32_t bitrev32(uint32_t x, int bits) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return bits ? (__brev(x) >> (32 - bits)) : 0u;
+#else
+    uint32_t r = 0;
+    for (int i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
+    return r;
+#endif
+}
 
-__device__ __forceinline__ fr_t tw_lookup(const fr_mem_t* lo, const fr_mem_t* hi, uint32_t e) {
-    fr_t a = fr_t::load(&lo[e & (NTT_TW_SIZE - 1)]);
-    uint32_t h = e >> NTT_TW_BITS;
-    if (h == 0) return a;
-    return a * fr_t::load(&hi[h]);
+// ---- a non-last pass' tile (host and device): columns inner0 .. inner0 + 2^lgT - 1 of block `outer`; row j of column c is read from
+// in_base + (j << s) + c, and output digit k is stored at in_base + (k << s) + c
+struct ntt_inner_tile_t {
+    size_t inner0, in_base;
+};
+SV_HD ntt_inner_tile_t ntt_inner_tile(const ntt_pass_t& p, size_t tile) {
+    const size_t tiles_per_outer = (size_t)1 << (p.s - p.lgT);
+    const size_t outer = tile / tiles_per_outer;
+    ntt_inner_tile_t t;
+    t.inner0 = (tile % tiles_per_outer) << p.lgT;
+    t.in_base = (outer << (p.a + p.s)) + t.inner0;
+    return t;
+}
+
+// ---- the last pass' index map (host and device) ----
+// After the passes before it, position (k0 << (lg - a1)) + (mid << a) + j holds the partial sums of output digits k0 (the first pass'),
+// the middle digits `mid` and input row j of the last pass.  Three passes: mid = k1.  Four passes: mid = k1 * 2^mid_lo + k2 in memory,
+// and the output wants k1 + k2 * 2^(lg_mid - mid_lo).  Output index = k0 + (mid' + k * 2^lg_mid) * 2^a1 with k = bitrev_a(row).
+struct ntt_last_tile_t {
+    size_t d1_0;     // first leading digit (column 0) of the tile
+    size_t in_base;  // input position of (row 0, column 0)
+    size_t mid_out;  // the middle digits in output order
+};
+SV_HD ntt_last_tile_t ntt_last_tile(const ntt_pass_t& p, size_t tile) {
+    const size_t tiles_per_mid = (size_t)1 << (p.a1 - p.lgT);
+    const size_t mid = tile / tiles_per_mid;
+    ntt_last_tile_t t;
+    t.d1_0 = (tile % tiles_per_mid) << p.lgT;
+    t.in_base = (t.d1_0 << (p.lg_n - p.a1)) + (mid << p.a);
+    const size_t k2 = mid & (((size_t)1 << p.mid_lo) - 1);
+    t.mid_out = (mid >> p.mid_lo) + (k2 << (p.lg_mid - p.mid_lo));
+    return t;
+}
+SV_HD size_t ntt_last_out(const ntt_pass_t& p, const ntt_last_tile_t& t, int col, uint32_t k) {
+    return (t.d1_0 + col) + ((t.mid_out + ((size_t)k << p.lg_mid)) << p.a1);
+}
+// (tile, row, column) -> output index, row = the tile row after the pass' DIF stages
+SV_HD size_t ntt_last_out_index(const ntt_pass_t& p, size_t tile, int row, int col) {
+    return ntt_last_out(p, ntt_last_tile(p, tile), col, bitrev32((uint32_t)row, p.a));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -275,19 +371,17 @@ __global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tabl
 
     // ---- addressing (as in v1)
     size_t in_base, in_rho_stride, in_col_stride;
-    size_t inner0 = 0, d1_0 = 0, mid = 0;
+    size_t inner0 = 0;
+    ntt_last_tile_t lt{};
     if (!p.last) {
-        const size_t tiles_per_outer = (size_t)1 << (p.s - p.lgT);
-        const size_t outer = tile / tiles_per_outer;
-        inner0 = (tile % tiles_per_outer) << p.lgT;
-        in_base = (outer << (p.a + p.s)) + inner0;
+        const ntt_inner_tile_t it = ntt_inner_tile(p, tile);
+        inner0 = it.inner0;
+        in_base = it.in_base;
         in_rho_stride = (size_t)1 << p.s;
         in_col_stride = 1;
     } else {
-        const size_t tiles_per_mid = (size_t)1 << (p.a1 - p.lgT);
-        mid = tile / tiles_per_mid;
-        d1_0 = (tile % tiles_per_mid) << p.lgT;
-        in_base = (d1_0 << (p.lg_n - p.a1)) + (mid << p.a);
+        lt = ntt_last_tile(p, tile);
+        in_base = lt.in_base;
         in_rho_stride = 1;
         in_col_stride = (size_t)1 << (p.lg_n - p.a1);
     }
@@ -329,7 +423,7 @@ __global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tabl
                 if (first) {
                     const size_t g = in_base + row * in_rho_stride + col * in_col_stride;
                     fr_t xin = load_fr_global(&p.in[g]);
-                    if (p.coset_pre) xin = xin * tw_lookup(tb.g_lo[0], tb.g_hi[0], (uint32_t)g);
+                    if (p.coset_pre) xin = xin * ntt_coset_pow(tb, 0, (uint32_t)g);
                     x[m] = A::from_canonical(xin);
                 } else {
                     x[m] = L.get<elem>(row * T + col);
@@ -356,21 +450,19 @@ __global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tabl
                     if (p.tw_full) {
                         y = A::mul(x[m], fr_t::load(&p.tw_full[((size_t)k << p.s) + inner0 + col]));  // the table holds the arithmetic's own form
                     } else {
-                        // composed on the fly from the two-level power tables (no table fits: the first pass of a 2^26 transform)
+                        // composed on the fly from the power tables (no table fits: the first pass of a 2^26 - 2^28 transform)
                         const uint32_t expo = (uint32_t)(((inner0 + col) * (size_t)k) << p.tw_shift);
-                        fr_t w = fr_t::load(&tb.pow_lo[p.dir][expo & (NTT_TW_SIZE - 1)]);
-                        const uint32_t h = expo >> NTT_TW_BITS;
-                        if (h) w = w * fr_t::load(&tb.pow_hi[p.dir][h]);
-                        y = A::mul(x[m], A::tw(w));
+                        y = A::mul(x[m], A::tw(ntt_twiddle(tb, p.dir, expo)));
                     }
                 } else {
-                    g = (d1_0 + col) + (((size_t)mid + ((size_t)k << p.lg_mid)) << p.a1);
+                    g = ntt_last_out(p, lt, col, k);
                     y = x[m];
                     if (!p.reduce_only) y = A::mul(y, p.scale_post == 0 ? A::one() : A::tw(fr_t::load(&tb.size_inv[p.lg_n])));
-                    if (p.scale_post == 2) {
-                        y = A::mul(y, A::tw(fr_t::load(&tb.g_lo[1][(uint32_t)g & (NTT_TW_SIZE - 1)])));
-                        const uint32_t h = (uint32_t)g >> NTT_TW_BITS;
-                        if (h) y = A::mul(y, A::tw(fr_t::load(&tb.g_hi[1][h])));
+                    if (p.scale_post == 2) {  // times 22^-g for output index g: one closing product per table factor
+                        const ntt_pow_idx_t gi = ntt_coset_index((uint32_t)g);
+                        y = A::mul(y, A::tw(fr_t::load(&tb.g_lo[1][gi.lo])));
+                        if (gi.hi) y = A::mul(y, A::tw(fr_t::load(&tb.g_hi[1][gi.hi])));
+                        if (gi.top) y = A::mul(y, A::tw(fr_t::load(&tb.g_top[1][gi.top])));
                     }
                     if (p.reduce_only) y = A::reduce_only(y);
                 }
@@ -431,27 +523,52 @@ static __global__ void fr_to_bigint_kernel(fr_mem_t* out, const fr_mem_t* in, si
 // ------------------------------------------------------------------------------------------
 struct ntt_plan_t {
     int npass;
-    int a[3];
+    int a[NTT_MAX_PASSES];
 };
-static inline ntt_plan_t ntt_make_plan(int lg) {
+// npass = 0: lg is out of range
+SV_HD ntt_plan_t ntt_make_plan(int lg) {
     ntt_plan_t pl;
     constexpr int R8 = 8;  // preferred pass radix: a [2^8 x 8] tile is 72 KiB of LDS, two workgroups per CU
-    if (lg <= R8) {
+    pl.npass = 0;
+    for (int i = 0; i < NTT_MAX_PASSES; i++) pl.a[i] = 0;
+    if (lg < 0 || lg > NTT_LG_MAX) {
+        return pl;
+    } else if (lg <= R8) {
         pl.npass = 1;
         pl.a[0] = lg;
-        pl.a[1] = pl.a[2] = 0;
     } else if (lg <= 2 * R8) {
         pl.npass = 2;
         pl.a[0] = lg / 2;
         pl.a[1] = lg - pl.a[0];
-        pl.a[2] = 0;
-    } else {  // up to 3 * 9 = 27 bits; 2^25 and 2^26 get one or two radix-2^9 passes
+    } else if (lg <= 3 * NTT_MAX_RADIX_LG) {  // up to 3 * 9 = 27 bits; 2^25 - 2^27 get one to three radix-2^9 passes
         pl.npass = 3;
         pl.a[0] = lg / 3;
         pl.a[1] = (lg - pl.a[0]) / 2;
         pl.a[2] = lg - pl.a[0] - pl.a[1];
+    } else {  // 2^28: 7 + 7 + 7 + 7 (the lazy bound and tile shapes of the 2^21 plan; a radix-2^10 pass would break the bound)
+        pl.npass = 4;
+        for (int i = 0; i < 4; i++) pl.a[i] = (lg + i) / 4;
     }
     return pl;
+}
+// the geometry of pass k of plan `pl` for a 2^lg transform (everything but the buffers, the tile width and the direction / type fields)
+SV_HD ntt_pass_t ntt_pass_geometry(const ntt_plan_t& pl, int lg, int k) {
+    ntt_pass_t p{};
+    p.lg_n = lg;
+    p.a = pl.a[k];
+    p.last = (k == pl.npass - 1);
+    int consumed = 0;
+    for (int i = 0; i < k; i++) consumed += pl.a[i];
+    if (!p.last) {
+        p.s = lg - consumed - p.a;
+        p.tw_shift = NTT_LG_MAX - (p.a + p.s);  // W28^(x << tw_shift) = w_(2^(a + s))^x
+    } else {
+        p.a1 = (pl.npass >= 2) ? pl.a[0] : 0;
+        p.lg_mid = 0;
+        for (int i = 1; i + 1 < pl.npass; i++) p.lg_mid += pl.a[i];
+        p.mid_lo = (pl.npass == 4) ? pl.a[2] : 0;
+    }
+    return p;
 }
 // tile width (log2) of a pass of radix 2^a whose tile dimension offers `avail` bits: [2^a x 2^lgT] elements of 36 bytes must
 // fit the 96 KiB the pass kernel may use
@@ -484,7 +601,7 @@ struct ntt_tw_entry {
     int users = 0;
 };
 struct ntt_tw_cache_t {
-    ntt_tw_entry ptr[2][NTT_MAX_RADIX_LG + 1][NTT_LG_MAX + 1];
+    ntt_tw_entry ptr[2][NTT_MAX_RADIX_LG + 1][NTT_LG_MAX + 1];  // [dir][a][a + s]
     // the table of the pass BEFORE the last one, with 2^261 (forward) or 2^261 / n (inverse) folded in, per transform size:
     // the last pass then ends with Fp::mont_reduce_lazy() instead of a product by one / by n^-1
     ntt_tw_entry prelast[2][NTT_LG_MAX + 1];
@@ -511,11 +628,12 @@ struct ntt_ctx_t {
 // fold: 0 plain, 1 times 2^261, 2 times 2^261 * size_inv (size_inv points at the Montgomery form of n^-1)
 // arith_signed: the table serves frs.hip.h (R = 2^290): plain entries carry 2^290 instead of 2^261, folded ones 2^580 instead of 2^522
 static __global__ void ntt_fill_full_tw_kernel(fr_mem_t* __restrict__ out, int a, int s, int tw_shift, const fr_mem_t* __restrict__ lo,
-                                        const fr_mem_t* __restrict__ hi, int fold, const fr_mem_t* __restrict__ size_inv, int arith_signed) {
+                                        const fr_mem_t* __restrict__ hi, const fr_mem_t* __restrict__ top, int fold, const fr_mem_t* __restrict__ size_inv,
+                                        int arith_signed) {
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= ((size_t)1 << (a + s))) return;
     const uint32_t k = (uint32_t)(idx >> s), inner = (uint32_t)(idx & (((size_t)1 << s) - 1));
-    fr_t t = tw_lookup(lo, hi, (inner * k) << tw_shift);
+    fr_t t = ntt_pow_compose(lo, hi, top, ntt_tw_index((inner * k) << tw_shift));
     if (fold) {
         t = t * fr_t::from_table(arith_signed ? FrS::C580 : FrP::R2);  // Montgomery form of (2^261 mod r): the stored word becomes t * 2^522 (signed: t * 2^580)
         if (fold == 2) t = t * fr_t::load(size_inv);
@@ -563,7 +681,7 @@ static inline const fr_mem_t* ntt_get_full_tw(const ntt_ctx_t& cx, int a, int s,
         cache.bytes += need;
         const int fold = !prelast_lg ? 0 : (dir == NTT_INVERSE ? 2 : 1);
         hipLaunchKernelGGL(ntt_fill_full_tw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cx.st, slot.p, a, s, tw_shift, cx.tb->pow_lo[dir],
-                           cx.tb->pow_hi[dir], fold, (const fr_mem_t*)(cx.tb->size_inv + (prelast_lg ? prelast_lg : 0)), tuning().ntt_signed ? 1 : 0);
+                           cx.tb->pow_hi[dir], cx.tb->pow_top[dir], fold, (const fr_mem_t*)(cx.tb->size_inv + (prelast_lg ? prelast_lg : 0)), tuning().ntt_signed ? 1 : 0);
         (void)hipStreamSynchronize(cx.st);  // other streams may use the table from now on
     }
     slot.last_use = ++cache.tick;
@@ -613,31 +731,22 @@ static inline void ntt_run_nn(const ntt_ctx_t& cx, fr_mem_t* data, fr_mem_t* scr
     }
     const int scale_post = (dir == NTT_INVERSE) ? (type == NTT_COSET ? 2 : 1) : 0;
     const int coset_pre = (dir == NTT_FORWARD && type == NTT_COSET) ? 1 : 0;
-    int consumed = 0;
     bool folded = false;  // the pass before the last one used a table with 2^261 [/ n] folded in
     for (int k = 0; k < pl.npass; k++) {
-        ntt_pass_t p;
-        p.lg_n = lg;
-        p.a = pl.a[k];
+        ntt_pass_t p = ntt_pass_geometry(pl, lg, k);
         p.dir = dir;
         p.coset_pre = (k == 0) ? coset_pre : 0;
-        p.last = (k == pl.npass - 1);
         p.scale_post = p.last ? scale_post : 0;
-        p.a1 = p.lg_mid = p.s = p.tw_shift = 0;
         p.tw_full = nullptr;
         p.reduce_only = 0;
         if (!p.last) {
-            p.s = lg - consumed - p.a;
             p.lgT = ntt_tile_lg(p.a, p.s, lg, nvec);
-            p.tw_shift = NTT_LG_MAX - (p.a + p.s);
             const bool prelast = (k == pl.npass - 2);
             bool f = false;
             p.tw_full = ntt_get_full_tw(cx, p.a, p.s, p.tw_shift, dir, prelast ? lg : 0, &f);
             folded = f;
         } else {
             p.reduce_only = folded ? 1 : 0;
-            p.a1 = (pl.npass >= 2) ? pl.a[0] : 0;
-            p.lg_mid = (pl.npass == 3) ? pl.a[1] : 0;
             p.lgT = ntt_tile_lg(p.a, p.a1, lg, nvec);
         }
         if (pl.npass == 1) {
@@ -660,7 +769,6 @@ static inline void ntt_run_nn(const ntt_ctx_t& cx, fr_mem_t* data, fr_mem_t* scr
         } else {
             ntt_launch_pass(st, p, tb);
         }
-        consumed += p.a;
     }
     if (pl.npass == 1)
         (void)hipMemcpyAsync(data, scratch, sizeof(fr_mem_t) << lg, hipMemcpyDeviceToDevice, st);

@@ -106,7 +106,12 @@ struct dev_buf {
             (void)hipGetLastError();
             p = nullptr;
             sv_drain_frees();
-            HIP_TRY(hipMalloc(&p, want));
+            const hipError_t e = hipMalloc(&p, want);
+            if (e != hipSuccess) {  // still out of memory: the call fails, the lane stays usable (no error left behind for its next call)
+                (void)hipGetLastError();
+                p = nullptr;
+                throw hip_failure{e, "hipMalloc", __LINE__};
+            }
         }
         cap = want;
     }
@@ -274,8 +279,9 @@ struct device_t {
             HIP_TRY(hipStreamCreateWithFlags(&lane[l].alt, hipStreamNonBlocking));
             for (auto& e : lane[l].ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        // tables: 4 x (lo + hi) x NTT_TW_SIZE + 2 x NTT_LOCAL + size_inv[27] + 4 constants, 32 B each
-        const size_t entries = 8 * NTT_TW_SIZE + 2 * NTT_LOCAL + 32 + 8;
+        // tables: 4 x (lo + hi) x NTT_TW_SIZE + 2 x NTT_LOCAL + 4 x NTT_TOP + size_inv[NTT_LG_MAX + 1] + 4 constants, 32 B each
+        static_assert(NTT_LG_MAX + 1 <= 32, "size_inv");
+        const size_t entries = 8 * NTT_TW_SIZE + 2 * NTT_LOCAL + 4 * NTT_TOP + 32 + 8;
         tables_mem.ensure(entries * sizeof(fr_mem_t));
         fr_mem_t* base = tables_mem.as<fr_mem_t>();
         size_t off = 0;
@@ -290,6 +296,8 @@ struct device_t {
             tb.g_lo[d] = take(NTT_TW_SIZE);
             tb.g_hi[d] = take(NTT_TW_SIZE);
             tb.local[d] = take(NTT_LOCAL);
+            tb.pow_top[d] = take(NTT_TOP);
+            tb.g_top[d] = take(NTT_TOP);
         }
         tb.size_inv = take(32);
         tb.consts = take(8);
