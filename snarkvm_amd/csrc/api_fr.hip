@@ -112,6 +112,8 @@ RustError snarkvm_polymul(void* out, size_t pcount, const void* polynomials, con
     const size_t* el = (const size_t*)elens;
     if (pcount + ecount == 0) return ok();
     if (pcount + ecount == 1 && pcount == 1) {
+        // `out` holds 2^lg elements: a longer polynomial would be copied past its end
+        if (lg < 64 && pl[0] > ((size_t)1 << lg)) return fail((int)hipErrorInvalidValue, "snarkvm_hip: polymul: polynomial longer than the domain");
         memcpy(out, polys[0], sizeof(fr_mem_t) * pl[0]);
         return ok();
     }

@@ -93,6 +93,22 @@ def test_polymul_host_only_corner_cases():
     assert np.array_equal(out[:3], p) and not out[3:].any()
 
 
+def test_polymul_single_polynomial_longer_than_domain():
+    """`out` holds 2^lg elements: a single polynomial longer than that is rejected, not copied past the end of `out`
+    (the caller's buffer here is large enough that an unchecked copy stays inside it and shows up as a change)"""
+    p = np.arange(9 * 4, dtype=np.uint64).reshape(9, 4) + 1
+    out = np.full((16, 4), 7, dtype=np.uint64)
+    pp = (ctypes.c_void_p * 1)(p.ctypes.data)
+    for lg, plen in ((3, 9), (0, 2)):
+        pl = (ctypes.c_size_t * 1)(plen)
+        with pytest.raises(_lib.HipError) as e:
+            _lib.check(_lib.lib().snarkvm_polymul(ctypes.c_void_p(out.ctypes.data), ctypes.c_size_t(1), pp, pl, ctypes.c_size_t(0), None, None, ctypes.c_uint32(lg)))
+        assert e.value.code == 1 and (out == 7).all(), lg  # hipErrorInvalidValue
+    pl = (ctypes.c_size_t * 1)(8)  # exactly the domain: copied
+    _lib.check(_lib.lib().snarkvm_polymul(ctypes.c_void_p(out.ctypes.data), ctypes.c_size_t(1), pp, pl, ctypes.c_size_t(0), None, None, ctypes.c_uint32(3)))
+    assert np.array_equal(out[:8], p[:8]) and (out[8:] == 7).all()
+
+
 def test_argument_validation_raises_before_ffi():
     from snarkvm_amd import plugin
     from snarkvm_amd.layout import G1_AFFINE

@@ -158,9 +158,12 @@ def test_ntt_2_26_round_trip():
     assert np.array_equal(y, x)
 
 
-def test_ntt_rejects_oversized_domain():
-    with pytest.raises(_lib.HipError):
+def test_ntt_rejects_null_buffer():
+    """a null buffer at a valid size (lg 27 since the 2^27 / 2^28 plans) is hipErrorInvalidValue; lg 29 is rejected in
+    test_gpu_ntt_large.py"""
+    with pytest.raises(_lib.HipError) as e:
         _lib.check(_lib.lib().snarkvm_ntt(None, ctypes.c_uint32(27), 0, 0, 0))
+    assert e.value.code == 1 and "null" in e.value.message  # hipErrorInvalidValue
 
 
 def test_kat_intt8_and_domain_wrappers(golden):
