@@ -4,18 +4,22 @@
 Default workload (`--workload msm`): one "step" = one G1 variable-base MSM of 2^lg_msm scalar-point pairs (BASELINE.json
 configs[1]: 2^24) with bases registered in HBM and scalars resident in HBM when the timed region starts.  `value` = pairs/s
 over all ranks (each rank runs its own independent MSM instances: instance-level sharding, no data-path collective -> weak
-scaling).  Every timed result is checked outside the timed region (closed form sum_i s_i (i+1) G, evaluated by a one-point MSM
-on the device; on rank 0 at N = 1 also against the CPU oracle, together with the full 2^24 NTT output).  The JSON line also
-carries: the NTT throughput at 2^24, the 2^20 half of BASELINE.json's metric, the throughput without precomputed tables, the
+scaling).  A plain run does only that: set up, warm up, time the K steps, write --dump-outputs, print the headline line.
+
+`--full` adds everything else, outside the timed region.  Every timed result is checked (closed form sum_i s_i (i+1) G, evaluated
+by a one-point MSM on the device; on rank 0 at N = 1 also against the CPU oracle, together with the full 2^24 NTT output).  The JSON
+line also carries: the NTT throughput at 2^24, the 2^20 half of BASELINE.json's metric, the throughput without precomputed tables, the
 registration cost, the end-to-end times of the reference's own FFI symbols over host buffers, `roofline` objects following
 SURVEY.md 8(d) (algorithmic bytes n * 128 + 144 for the whole MSM, 32 n for the scalar-read phase, 64 n for an NTT), an
 `alu_roofline` against the wall-clock-calibrated arithmetic ceilings of tools/ecbench.hip, and a `cpu_baseline` (the C++
 restatement of the reference's rayon path, oracle/, timed on this box's host cores on a bounded sample).
 
+The proof workloads below always run their checks; `--full` changes nothing there.
+
 `--workload proof1`: BASELINE.json configs[3] - ONE Varuna-proof-shaped call list at a time from one caller thread (the reference
 proves one transaction at a time, proving_key/mod.rs:37): `value` = proofs/s of 32 proofs proved one after the other,
 `ms_per_step` = the latency of one proof; every result of every timed proof is compared with the serial replay and all 15 results
-of two proofs with the CPU oracle.  The default workload carries compact `proof1`, `proofs64` and `concurrent_callers` legs too.
+of two proofs with the CPU oracle.  The default workload carries compact `proof1`, `proofs64` and `concurrent_callers` legs too (`--full`).
 
 `--workload proofs64`: BASELINE.json configs[4] - 64 Varuna-proof-shaped call lists (14 G1 commitments / openings of
 2^16-2^17, ~45 NTTs, the polynomial passes, one 2^16 G2 MSM each; snarkvm_amd/proofs.py), 64 / N proofs per rank, replayed in
@@ -151,8 +155,11 @@ def main():
                     help="bits per base table = widest bucket window; -1: 22 / 20 / 16 by size; tables = ceil(254 / table_bits)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="issue the K steps one synchronous MSM at a time instead of one pipelined batch of K independent MSMs")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: after the timed steps, also check every timed result and run the other distribution, phase times, NTT, rooflines, "
+                         "extra legs, proof legs and CPU baseline (all outside the timed region); a plain run prints the headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the 2^20 / tables1 / FFI legs (they are outside the timed region anyway)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the 2^20 / tables1 / FFI legs (they are outside the timed region anyway)")
     ap.add_argument("--cpu-lg-msm", type=int, default=24, help="CPU baseline sample: 2^k pairs of the same workload (24 = the full configuration, ~10 s on 64 threads)")
     ap.add_argument("--cpu-lg-ntt", type=int, default=24)
     ap.add_argument("--proofs", type=int, default=64)
@@ -161,10 +168,10 @@ def main():
     ap.add_argument("--proof-group", type=int, default=32, help="proofs replayed in lock step per group (proofs64, lockstep mode)")
     ap.add_argument("--lockstep-async", action="store_true", help="proofs64: the whole lock-step group in ONE asynchronous scope (measured slower: 191 vs 203 proofs/s)")
     ap.add_argument("--proof1-sync-msm", action="store_true", help="proof1: synchronous commitments (the A/B of SNARKVM_HIP_SCOPE_ASYNC_MSM)")
-    ap.add_argument("--no-proof-legs", action="store_true", help="default workload: skip the proof1 / proofs64 / concurrent_callers legs")
+    ap.add_argument("--no-proof-legs", action="store_true", help="default workload, --full: skip the proof1 / proofs64 / concurrent_callers legs")
     ap.add_argument("--scalars", choices=["uniform", "witness"], default="uniform",
                     help="distribution of the timed legs' scalars: uniform in [0, r), or witness-like (SURVEY.md 8d config 2: 50 %% zero, 25 %% < 2^16, 25 %% uniform; "
-                         "synthesizer/process/src/tests/test_credits.rs:2868-2925 shapes).  The default line reports BOTH for the headline, proof1 and proofs64 "
+                         "synthesizer/process/src/tests/test_credits.rs:2868-2925 shapes).  The --full line reports BOTH for the headline, proof1 and proofs64 "
                          "(value_witness_like, ...); this flag makes the second distribution the headline itself")
     ap.add_argument("--proof-mem", choices=["torch", "hip"], default="hip",
                     help="proof1: who owns the proof's device buffers and issues its operand copies - \"hip\": snarkvm_hip_malloc / _memcpy_d2d / _memset through the C ABI (what a "
@@ -327,7 +334,7 @@ def main():
         lanes = L.snarkvm_hip_batch_lanes(ctypes.c_size_t(n))
         rb.msm_batch(device_ptrs=[d_scalars.data_ptr()] * (lanes * args.warmup), npoints=[n] * (lanes * args.warmup), window_bits=args.window_bits)
     barrier()
-    sclk = SclkSampler(dev_index)
+    sclk = SclkSampler(dev_index)  # only --full reports it; it samples in both modes so that the timed region is the same
     with sclk:
         t0 = time.perf_counter()
         if args.no_pipeline:
@@ -344,9 +351,46 @@ def main():
     print(f"[bench rank {rank}] {dt_rank / args.steps * 1e3:.3f} ms per step on this rank", file=sys.stderr)
     ms_per_step = dt / args.steps * 1e3
     pairs_per_s = world * n * args.steps / dt
-    want_affine = check_results(res, scalars, "timed_msm", shifts)  # outside the timed region
+    if args.full:
+        want_affine = check_results(res, scalars, "timed_msm", shifts)  # outside the timed region
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, to_affine(res[-1:])[0])
+    head = {
+        "metric": "BLS12-377 G1 MSM scalar-point pairs/sec (+ Fr NTT elements/sec in ntt_*)",
+        "value": pairs_per_s,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "rank_ms_per_step": [d / args.steps * 1e3 for d in rank_dts],
+        "rank_devices": rank_devices,
+        # DESIGN.md 7's prediction made checkable: the sum of every rank's OWN rate (its K steps on its own clock, before the closing barrier) - what N
+        # independent instance streams deliver when nothing on the host or the fabric couples them.  `value` (all ranks' units / the slowest rank's time incl. the
+        # barrier) should sit within a few percent of it; a gap means host-side contention, two ranks on one GPU (duplicate_devices) or a slow box.
+        "predicted_value": sum(n * args.steps / d for d in rank_dts),
+        "value_over_predicted": pairs_per_s / sum(n * args.steps / d for d in rank_dts),
+        "duplicate_devices": duplicate_devices(rank_devices),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,  # the reference publishes no number for this metric
+        "dtype": DTYPE,
+        "data": "synthetic",
+        "config": {"workload": f"G1 Pippenger MSM 2^{args.lg_msm} (BASELINE.json configs[1]), bases (i+1)G registered in HBM, "
+                               f"{'witness-like (50 % zero, 25 % < 2^16, 25 % uniform)' if args.scalars == 'witness' else 'uniform'} scalars in HBM; independent instance per GPU",
+                   "scalars": args.scalars,
+                   "lg_msm": args.lg_msm, "lg_ntt": args.lg_ntt, "window_bits": args.window_bits or "auto", "base_tables": args.tables, "table_bits": args.table_bits,
+                   "pipelined_batch": not args.no_pipeline},
+        "full": args.full,
+    }
+    if not args.full:
+        # a plain run ends with its headline: no result check, no other leg (no CPU baseline either: None, as whenever the line has none)
+        if rank == 0:
+            print(json.dumps(dict(head, vs_cpu_baseline=None, cpu_baseline=None)))
+        rb.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     del d_step
     # ---- the same K pipelined steps on the OTHER distribution (rank 0, N = 1): SURVEY.md 8(d) config 2 names witness-like scalars as the second one
     other = None
@@ -661,32 +705,8 @@ def main():
                 alu_ntt["element_pass_ceiling_per_s"] = ceil["fr_ntt_element_passes_per_s"]
                 alu_ntt["vs_register_loop"] = passes * nn / (ntt_kernel_ms * 1e-3) / ceil["fr_ntt_element_passes_per_s"]
         out = {
-            "metric": "BLS12-377 G1 MSM scalar-point pairs/sec (+ Fr NTT elements/sec in ntt_*)",
-            "value": pairs_per_s,
-            "unit": "pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "rank_ms_per_step": [d / args.steps * 1e3 for d in rank_dts],
-            "rank_devices": rank_devices,
-            # DESIGN.md 7's prediction made checkable: the sum of every rank's OWN rate (its K steps on its own clock, before the closing barrier) - what N
-            # independent instance streams deliver when nothing on the host or the fabric couples them.  `value` (all ranks' units / the slowest rank's time incl. the
-            # barrier) should sit within a few percent of it; a gap means host-side contention, two ranks on one GPU (duplicate_devices) or a slow box.
-            "predicted_value": sum(n * args.steps / d for d in rank_dts),
-            "value_over_predicted": pairs_per_s / sum(n * args.steps / d for d in rank_dts),
-            "duplicate_devices": duplicate_devices(rank_devices),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,  # the reference publishes no number for this metric
+            **head,
             "vs_cpu_baseline": (pairs_per_s / cpu["value"]) if cpu else None,
-            "dtype": DTYPE,
-            "data": "synthetic",
-            "config": {"workload": f"G1 Pippenger MSM 2^{args.lg_msm} (BASELINE.json configs[1]), bases (i+1)G registered in HBM, "
-                                   f"{'witness-like (50 % zero, 25 % < 2^16, 25 % uniform)' if args.scalars == 'witness' else 'uniform'} scalars in HBM; independent instance per GPU",
-                       "scalars": args.scalars,
-                       "lg_msm": args.lg_msm, "lg_ntt": args.lg_ntt, "window_bits": args.window_bits or "auto", "base_tables": args.tables, "table_bits": args.table_bits,
-                       "pipelined_batch": not args.no_pipeline},
             "checks": checks,
             # the same pipelined steps on the second distribution (rank 0, N = 1), each result against its own closed form
             **({f"value_{other['name']}": other["value"], f"ms_per_step_{other['name']}": other["ms_per_step"], f"steps_{other['name']}": other["steps"],

@@ -1095,6 +1095,50 @@ def test_bench_two_rank_path_on_one_gpu():
         assert len(d["duplicate_devices"]) == 1 and sorted(d["duplicate_devices"][0]["ranks"]) == [0, 1]
 
 
+def test_bench_full_two_rank_path_on_one_gpu():
+    """bench.py --full's N > 1 code path (rendezvous, barriers, max-over-ranks timing, rank-0 JSON) with two ranks sharing this
+    GPU over gloo (RCCL refuses two ranks on one device; the collective semantics are the same)."""
+    import json
+    import subprocess
+    import sys
+
+    env = dict(os.environ, SNARKVM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29537",
+           os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--lg-msm", "16", "--lg-ntt", "16", "--ntt-steps", "2", "--full"]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=util.ROOT)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak" and d["cpu_baseline"] is None and d["full"] is True
+    assert "timed_msm" in d["checks"] and d["ntt_value"] > 0 and "phase_ms" in d
+    assert d["value"] > 0 and abs(d["value"] - 2 * (1 << 16) / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    # the self-check of a scaling point: the sum of the ranks' own rates beside `value`, and the two ranks sharing this GPU are flagged
+    assert d["predicted_value"] >= d["value"] * 0.999 and 0 < d["value_over_predicted"] <= 1.001
+    if all(r.get("uuid") for r in d["rank_devices"]):
+        assert len(d["duplicate_devices"]) == 1 and sorted(d["duplicate_devices"][0]["ranks"]) == [0, 1]
+
+
+def test_bench_plain_run_prints_the_headline_only():
+    """bench.py without --full, two ranks sharing this GPU over gloo: every rank leaves after its timed steps, rank 0 prints the
+    headline line, and none of --full's checks, legs or baselines ran."""
+    import json
+    import subprocess
+    import sys
+
+    env = dict(os.environ, SNARKVM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29536",
+           os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--lg-msm", "16"]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=util.ROOT)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 2 * (1 << 16) / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert len(d["rank_ms_per_step"]) == 2 and d["predicted_value"] >= d["value"] * 0.999
+    assert d["cpu_baseline"] is None and d["vs_cpu_baseline"] is None
+    assert not {"checks", "ntt_value", "phase_ms", "roofline", "alu_roofline", "end_to_end_ffi", "proof1"} & set(d)
+
+
 def test_bench_dump_outputs_is_the_last_step_and_repeats(tmp_path):
     """bench.py --dump-outputs: two runs with the same arguments write the same array, and it is the LAST timed step's MSM
     (step k's scalars are the seeded vector rotated by k * 999983 positions) against the oracle's closed form."""

@@ -5,7 +5,7 @@
 # An empty string "" is the default build.  Example (round 4, session 20):
 #   bash tools/ab_tuning.sh r05_reduce -- "reduce_rounds=2" "reduce_rounds=1,seg2=64"
 TAG=$1; shift
-WORKLOAD=msm; ARGS="--steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs --ntt-steps 2"
+WORKLOAD=msm; ARGS="--full --steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs --ntt-steps 2"
 while [ "$1" != "--" ] && [ $# -gt 0 ]; do
   case "$1" in
     --proofs64) WORKLOAD=proofs64; ARGS="--no-cpu-baseline";;

@@ -7,7 +7,7 @@ for v in default inline default inline; do
 done
 cat $O/phases.md | grep -v "^|---\|msm_digits\|msm_scalar_read"; cat $O/g2.md
 unset SNARKVM_HIP_LIB
-A="--steps 6 --warmup 1 --no-cpu-baseline --no-extra-legs"
+A="--full --steps 6 --warmup 1 --no-cpu-baseline --no-extra-legs"
 for r in 2 1 0; do SNARKVM_HIP_TUNING=reduce_rounds=$r timeout 300 python bench.py $A > $O/rr$r.json 2> $O/rr$r.err; python - "$O/rr$r.json" <<'PY'
 import json,sys
 try:

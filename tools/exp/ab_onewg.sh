@@ -1,5 +1,5 @@
 set -u; export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-$(pwd)}"; O=gpurun_out/r03d; mkdir -p $O
-A="--steps 8 --warmup 1 --no-cpu-baseline --no-extra-legs"
+A="--full --steps 8 --warmup 1 --no-cpu-baseline --no-extra-legs"
 timeout 300 python bench.py $A > $O/base.json 2> $O/base.err
 SNARKVM_HIP_TUNING=acc_one_wg=1 timeout 300 python bench.py $A > $O/onewg96.json 2> $O/onewg96.err
 SNARKVM_HIP_TUNING=acc_one_wg=1,acc_lds=83968 timeout 300 python bench.py $A > $O/onewg82.json 2> $O/onewg82.err

@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 OUT=gpurun_out/${TAG}prof
 mkdir -p $OUT
-ARGS1="--steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs --no-pipeline"
-ARGS0="--steps 1 --warmup 0 --no-pipeline --no-cpu-baseline --no-extra-legs --ntt-steps 2"
+ARGS1="--full --steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs --no-pipeline"
+ARGS0="--full --steps 1 --warmup 0 --no-pipeline --no-cpu-baseline --no-extra-legs --ntt-steps 2"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o $TAG -- python bench.py $ARGS1 > $OUT/bench_under_rocprof.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o f -- python bench.py $ARGS0 > $OUT/pmc_fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o w -- python bench.py $ARGS0 > $OUT/pmc_write.log 2>&1

@@ -4,7 +4,7 @@
 # rocprofv3 statistics and PMC passes, the side tables of profiles/r05_summary.md.
 O=gpurun_out/r05_final; mkdir -p $O
 export TMPDIR=/tmp
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_driver_command.json 2> $O/bench_driver_command.err; echo "bench rc=$?"
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r05_bench_driver_command.json 2> $O/bench_driver_command.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 try:

@@ -4,7 +4,7 @@
 # Every step runs under its own `timeout`: a hung step costs its limit, not the lease.
 O=gpurun_out/r06_final; mkdir -p $O
 export TMPDIR=/tmp
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_driver_command.json 2> $O/bench_driver_command.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r06_bench_driver_command.json 2> $O/bench_driver_command.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 try:
