@@ -401,14 +401,10 @@ int snarkvm_hip_selftest_g1_finish(const void *planes_projective, const int32_t 
 int snarkvm_hip_selftest_fq_lazy(uint64_t seed, int iters);
 /* host only: the tail arithmetic of a G1 MSM (ffl.hip.h::fqz_t under the generic addition / doubling laws) against the exact one */
 int snarkvm_hip_selftest_g1_lazy_tail(uint64_t seed, int iters);
-/* The lazy Fq2 arithmetic of the G2 accumulate kernel (csrc/ffl2.hip.h) against the exact arithmetic, on the host: `iters` chained
- * mixed additions of +- points[k] (npoints >= 2 Rust G2Affine records on the curve, 200-byte stride), doublings, cancellations
- * and restarts from infinity included, every coordinate compared after every step; products, squares and the raw partial-sum image
- * on the way.  0 = identical; > 0: first differing step; < 0: a field / conversion case. */
-int snarkvm_hip_selftest_fq2_lazy(const void *points, size_t npoints, uint64_t seed, int iters);
 /* The lane-pair Fq2 arithmetic of the G2 accumulate kernel (csrc/ffl2p.hip.h: the c0 component of every value on the even lane, c1 on
  * the odd lane, operands exchanged inside the VALU) with both lanes of a pair run side by side on the host - the same source - against
- * the exact arithmetic: the chain of snarkvm_hip_selftest_fq2_lazy; doublings and cancellations are resolved inside the pair arithmetic.
+ * the exact arithmetic: `iters` chained mixed additions of +- points[k] (npoints >= 2 Rust G2Affine records on the curve, 200-byte stride), restarts
+ * from infinity included, every coordinate compared after every step; doublings and cancellations are resolved inside the pair arithmetic.
  * 0 = identical; > 0: first differing step; < 0: a conversion case. */
 int snarkvm_hip_selftest_fq2_pair(const void *points, size_t npoints, uint64_t seed, int iters);
 /* The sixteen-lane cooperative Fq2 addition of the G2 tail trees (csrc/hex2.hip.h: lane 4 q + p of a DPP row computes Fq sub-product p of the quad
@@ -421,10 +417,6 @@ int snarkvm_hip_selftest_g2_hex(const void *points, size_t npoints, uint64_t see
  * [3] differing planes, [4..7] first differing fold slots, [8], [9] fold slots / planes the fast kernels handed to the fix kernels (equal x met). */
 RustError snarkvm_hip_devtest_g2_tail_repeat(const void *points, size_t npoints, int m, int hb, int threads, int plane_threads,
                                              int hex, int quads, int iters, uint32_t *report);
-/* The signed-limb butterfly arithmetic of the NTT passes (csrc/frs.hip.h) against the exact arithmetic, on the host: passes of up
- * to nine butterfly stages without a canonical form in between, the closing product, the bare reduction and the folded table
- * form.  0 = identical; > 0: first differing butterfly; < 0: a closing-step case. */
-int snarkvm_hip_selftest_fr_signed(uint64_t seed, int iters);
 /* The NTT's planner, power tables and index maps (csrc/ntt.hip.h) run on the host through the kernels' own __host__ __device__ code.
  * ntt_plan: out[4] = the pass radices (log2) of the 2^lg plan; returns the number of passes, -1 when lg > 28. */
 int snarkvm_hip_selftest_ntt_plan(uint32_t lg, int32_t *out);

@@ -27,7 +27,7 @@ SYMBOLS = [
     "snarkvm_hip_g1_fixed_base_msm", "snarkvm_hip_g1_group_ntt",
     "snarkvm_hip_set_profiling", "snarkvm_hip_get_phase_count", "snarkvm_hip_get_phase_name",
     "snarkvm_hip_get_phase_ms", "snarkvm_hip_synchronize", "snarkvm_hip_coalescer_stats",
-    "snarkvm_hip_selftest_field", "snarkvm_hip_selftest_g1_msm_naive", "snarkvm_hip_selftest_msm_plan", "snarkvm_hip_selftest_g1_finish", "snarkvm_hip_selftest_fq_lazy", "snarkvm_hip_selftest_g1_lazy_tail", "snarkvm_hip_selftest_fr_signed", "snarkvm_hip_selftest_ntt_plan", "snarkvm_hip_selftest_ntt_twiddle", "snarkvm_hip_selftest_ntt_index", "snarkvm_hip_selftest_ntt_host", "snarkvm_hip_selftest_fq2_lazy", "snarkvm_hip_selftest_fq2_pair", "snarkvm_hip_selftest_g2_hex", "snarkvm_hip_devtest_field", "snarkvm_hip_devtest_g2_tail_repeat",
+    "snarkvm_hip_selftest_field", "snarkvm_hip_selftest_g1_msm_naive", "snarkvm_hip_selftest_msm_plan", "snarkvm_hip_selftest_g1_finish", "snarkvm_hip_selftest_fq_lazy", "snarkvm_hip_selftest_g1_lazy_tail", "snarkvm_hip_selftest_ntt_plan", "snarkvm_hip_selftest_ntt_twiddle", "snarkvm_hip_selftest_ntt_index", "snarkvm_hip_selftest_ntt_host", "snarkvm_hip_selftest_fq2_pair", "snarkvm_hip_selftest_g2_hex", "snarkvm_hip_devtest_field", "snarkvm_hip_devtest_g2_tail_repeat",
 ]
 
 
@@ -84,10 +84,8 @@ def lib():
         L.snarkvm_hip_selftest_g1_finish.restype = ctypes.c_int
         L.snarkvm_hip_selftest_fq_lazy.restype = ctypes.c_int
         L.snarkvm_hip_selftest_g1_lazy_tail.restype = ctypes.c_int
-        L.snarkvm_hip_selftest_fr_signed.restype = ctypes.c_int
         for name in ("snarkvm_hip_selftest_ntt_plan", "snarkvm_hip_selftest_ntt_twiddle", "snarkvm_hip_selftest_ntt_index", "snarkvm_hip_selftest_ntt_host"):
             getattr(L, name).restype = ctypes.c_int
-        L.snarkvm_hip_selftest_fq2_lazy.restype = ctypes.c_int
         L.snarkvm_hip_selftest_fq2_pair.restype = ctypes.c_int
         L.snarkvm_hip_selftest_g2_hex.restype = ctypes.c_int
         L.snarkvm_hip_get_phase_count.restype = ctypes.c_int

@@ -1,7 +1,7 @@
 // ffl2p.hip.h - Fq2 = Fq[u] / (u^2 + 5) split over a LANE PAIR, for the G2 bucket-accumulation loop (round 5).
 //
-// ffl2.hip.h holds both components of every Fq2 value in one lane: the accumulator, the base point and the live temporaries of the
-// addition law are 398 VGPRs + 142 AGPRs (profiles/r04_g2.md) - one wave per SIMD and ~410 register-file moves per addition.  Here the
+// With both components of every Fq2 value in one lane (round 4, retired: HISTORY.md) the accumulator, the base point and the live temporaries
+// of the addition law were 398 VGPRs + 142 AGPRs (profiles/r04_g2.md) - one wave per SIMD and ~410 register-file moves per addition.  Here the
 // EVEN lane of a pair holds the c0 component of every value and the ODD lane the c1 component (fields/src/fp2.rs:404-410):
 //     c0 = a0 b0 - a1 (5 b1)        on the even lane
 //     c1 = a0 b1 + a1 b0            on the odd lane
@@ -15,7 +15,7 @@
 // Ranges (units of q; e < 2^-26): every product is (-1 - e, e) on BOTH lanes now (even lane: |a0 b0 - 5 a1 b1| < 6 q^2, minus m q with
 // m < 2^406); product operands are "tight" (|value| <= 1 + 2 e: every limb below 2^29 in magnitude).  Column bounds: even lane
 // [-(14 + 6.4 + 2) 2^58, 13 * 2^58], odd lane [-(4 + 6.4) 2^58, 26 * 2^58]: inside 64 bits.  The addition law normalises every sum or
-// difference with the multiple of q that makes it tight again (ffl2.hip.h sub_norm / norm_k); X and Y of the accumulator stay within
+// difference with the multiple of q that makes it tight again (ffl2.hip.h sub_norm, norm_k below); X and Y of the accumulator stay within
 // [0, 1 + 2 e], ZZ and ZZZ are raw products.
 //
 // Exceptional additions never leave this arithmetic: U2 - X1 = 0 in Fq2 is decided exactly (normalised values have ONE limb image per

@@ -8,7 +8,7 @@
 // variable_base/mod.rs:96-105,116-117).
 //
 // Pipeline (all on one stream of one lane; runtime.hip.h::msm_run enqueues it, DESIGN.md 3.2 has the sizes):
-//   1 scalar read   wide windows (c > 16, registered tables): radix_hist1_fused_kernel (msm_sort.hip.h) reads every 32-byte
+//   1 scalar read   wide windows (c > 16, registered tables): radix_hist1_wide_kernel (msm_sort.hip.h) reads every 32-byte
 //               scalar once, recodes it in registers into signed c-bit digits with the bias trick
 //               (s' = s + sum_w 2^(c-1+cw); digit_w = ((s' >> cw) & (2^c-1)) - 2^(c-1)) and counts level-1 bins in LDS -
 //               no digit matrix exists.  c <= 16: msm_digits_kernel writes u16 digits [rows][n].
@@ -731,14 +731,12 @@ static constexpr uint32_t TAIL_MAX_SEG = 2048;  // buckets per fold column (2^hb
 // is (partial sums of its row / column) / B whatever their distribution over the buckets - a bucket that received half of the
 // scalars (a witness full of ones) costs its row and its column a few more additions, not a reduce round with a host
 // read-back in front of it.
-// FLAT = false (big MSMs after their reduce rounds: <= TAIL_PARTIALS per bucket, thousands of buckets per column): lane ->
-// buckets i, i + B, ... of the column, no LDS staging.
-template <class F, bool FLAT>
+template <class F>
 __global__ void __launch_bounds__(256, TAIL_WAVES<F>::value) msm_fold_kernel(const xyzz_mem_t<F>* __restrict__ sums, const uint32_t* __restrict__ start,
                                                        const uint32_t* __restrict__ cnt, xyzz_mem_t<F>* __restrict__ out, int m, int hb, int hex, int quads,
                                                        uint32_t* __restrict__ flags) {
     __shared__ xyzz_mem_t<F> sh[16];
-    __shared__ uint32_t s_off[FLAT ? TAIL_MAX_SEG + 1 : 1], s_start[FLAT ? TAIL_MAX_SEG : 1], s_tmp[FLAT ? 256 : 1];
+    __shared__ uint32_t s_off[TAIL_MAX_SEG + 1], s_start[TAIL_MAX_SEG], s_tmp[256];
     const uint32_t nlo = 1u << m, nhi = 1u << hb;
     const uint32_t w = blockIdx.y;
     const uint32_t kbase = w << (m + hb);
@@ -749,21 +747,6 @@ __global__ void __launch_bounds__(256, TAIL_WAVES<F>::value) msm_fold_kernel(con
     if (!column && fixed == 0) return;
     const size_t slot = ((size_t)w << (m + 1)) + (column ? fixed : nlo + fixed - 1);
     bool dbl = false;  // Fq2: some addition met equal x coordinates (tail_store)
-    if (!FLAT) {
-        xyzz_t<F> acc = xyzz_t<F>::inf();
-        // one loop for both shapes: a column is nhi buckets at stride 2^m, a row one contiguous range of partial sums
-        const uint32_t k0 = kbase + (fixed << m);
-        const uint32_t nouter = column ? nhi : 1u;
-        for (uint32_t i = column ? threadIdx.x : 0u; i < nouter; i += column ? blockDim.x : 1u) {
-            const uint32_t k = kbase + (i << m) + fixed;
-            const uint32_t q0 = column ? start[k] : start[k0] + threadIdx.x;
-            const uint32_t q1 = column ? q0 + cnt[k] : start[k0 + nlo - 1] + cnt[k0 + nlo - 1];
-            for (uint32_t q = q0; q < q1; q += column ? 1u : blockDim.x) tail_add(acc, load_xyzz<F>(&sums[q]), dbl);
-        }
-        block_sum<F>(acc, sh, hex, false, dbl);
-        tail_store<F>(out, flags, slot, acc, dbl);
-        return;
-    }
     uint32_t nseg;
     if (column) {
         for (uint32_t i = threadIdx.x; i < nhi; i += blockDim.x) {
@@ -938,8 +921,7 @@ __global__ void __launch_bounds__(64) msm_bitplane_fix_kernel(const xyzz_mem_t<F
 // Their instantiations live in translation units of their own (csrc/tail_g1.hip, csrc/tail_g2.hip, csrc/tail_g2_planes.hip, csrc/tail_g2_fix.hip), compiled in parallel with the units that LAUNCH them; everywhere
 // else they are only declared (a launch references the kernel's host-side handle, an ordinary external symbol).
 #define SV_TAIL_FOLD_KERNELS(PREFIX, F)                                                                                                                             \
-    PREFIX template __global__ void msm_fold_kernel<F, true>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, int, int, int, int, uint32_t*);          \
-    PREFIX template __global__ void msm_fold_kernel<F, false>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, int, int, int, int, uint32_t*);
+    PREFIX template __global__ void msm_fold_kernel<F>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, int, int, int, int, uint32_t*);
 #define SV_TAIL_PLANE_KERNELS(PREFIX, F)                                                                                                                            \
     PREFIX template __global__ void msm_bitplane_kernel<F, true>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, uint32_t, int, int, int, int, uint32_t*); \
     PREFIX template __global__ void msm_bitplane_kernel<F, false>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, uint32_t, int, int, int, int, uint32_t*);

@@ -321,48 +321,11 @@ __device__ __forceinline__ void fused_stage_half(const uint4* __restrict__ scala
 #pragma unroll
     for (int k = 0; k < 4; k++) stage[threadIdx.x + k * FUSED_THREADS] = v[k];
 }
-// dynamic LDS: rows * B1 counters.  The scalar read needs no staging here: every thread issues the eight 16-byte loads of its
-// four scalars up front (lane stride 32 B: the two loads of a scalar use the two halves of the same cache lines, so every
-// line is fetched from HBM once) and nothing but the LDS counters sits between the loads and the end of the kernel.
-template <int C>
-__global__ void __launch_bounds__(FUSED_THREADS) radix_hist1_fused_kernel(const uint4* __restrict__ scalars, uint32_t* __restrict__ cnt,
-                                                                   msm_radix_params_t p, msm_digit_params_t dp) {
-    extern __shared__ uint32_t fused_hist[];
-    const uint32_t B1 = 1u << p.HB;
-    const uint32_t rows = (uint32_t)dp.W;  // digit rows per scalar (= W * J)
-    const uint32_t keys = rows * B1;
-    uint32_t* hist = fused_hist;
-    const uint32_t t = blockIdx.x;
-    uint4 lo[FUSED_SPT], hi[FUSED_SPT];
-#pragma unroll
-    for (int q = 0; q < FUSED_SPT; q++) {
-        const size_t i = (size_t)t * FUSED_TILE + (size_t)q * FUSED_THREADS + threadIdx.x;
-        if (i < p.n) {
-            lo[q] = scalars[2 * i];
-            hi[q] = scalars[2 * i + 1];
-        } else {
-            lo[q] = hi[q] = make_uint4(0, 0, 0, 0);
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < keys; i += FUSED_THREADS) hist[i] = 0;
-    __syncthreads();
-    const int half = 1 << (p.c - 1);
-#pragma unroll
-    for (int q = 0; q < FUSED_SPT; q++) {
-        if ((size_t)t * FUSED_TILE + (size_t)q * FUSED_THREADS + threadIdx.x >= p.n) continue;
-        uint32_t s[11];
-        recode_scalar(lo[q], hi[q], dp, s);
-#pragma unroll
-        for (int r = 0; r < FUSED_MAX_ROWS; r++) {
-            uint32_t b, neg;
-            if (C * r < MSM_BIAS_BITS && (uint32_t)r < rows && digit_bucket(recoded_digit<C>(s, r), half, b, neg)) atomicAdd(&hist[r * B1 + (b >> p.LB)], 1u);
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < keys; i += FUSED_THREADS) cnt[(size_t)t * keys + i] = hist[i];
-}
-// The same counts from a WIDER workgroup with REPLICATED histograms (round 4; tuning hist=2, the default).  tools/exp/histbench.hip
-// took the one-tile kernel above apart on 2^24 scalars: reading alone takes 85 - 88 us (6.1 - 6.3 TB/s), reading + recoding + digit
+// The scalar-read phase: dynamic LDS of rows * B1 * HISTW_COPIES counters.  The scalar read needs no staging: every thread issues the
+// four 16-byte loads of its two scalars up front (lane stride 32 B: the two loads of a scalar use the two halves of the same cache
+// lines, so every line is fetched from HBM once) and nothing but the LDS counters sits between the loads and the end of the kernel.
+// A WIDE workgroup with REPLICATED histograms (round 4).  tools/exp/histbench.hip took the round-3 kernel (512 threads x 4 scalars,
+// one histogram; retired, HISTORY.md) apart on 2^24 scalars: reading alone takes 85 - 88 us (6.1 - 6.3 TB/s), reading + recoding + digit
 // extraction 93 us, the full kernel 124 - 127 us - the LDS atomics are what is left, and they serialise when lanes of a wave hit
 // the same counter (64 lanes into 128 bins of a row).  Four private copies of the histogram (copy = lane & 3, interleaved so that
 // different copies never share a bank) cut those collisions fourfold; 1 024 threads x 2 scalars instead of 512 x 4 keep twice the
@@ -895,7 +858,7 @@ static __device__ __noinline__ void lazy_exceptional_add(xyzz_lazy_t* acc, const
 // coordinates times 2^406 as unpacked limbs (g1_lazy_slot_t; runtime.hip.h::bases_to_lazy_form / convert_bases form406); the accumulator lives in signed limbs
 // without a canonical form; partial sums are flushed raw and converted to the exact representation by a dense pass afterwards.  The addition law's exceptional cases (the filter of xyzz_lazy_t::madd) are resolved on
 // the exact arithmetic: cold code.  Per addition: 3 046 multiply-adds + ~900 other instructions (exact kernel: 2 951 + 2 238).
-template <bool PREFETCH>
+template <bool PREFETCH>  // (always true - the two-stage pipeline below; a template so that only the unit that launches it - api.hip - compiles it)
 __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_aff_mem_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
                                                               const uint32_t* __restrict__ boff, const uint32_t* __restrict__ start,
                                                               g1_lazy_partial_t* __restrict__ partial, uint32_t nbt, uint32_t S, uint32_t debug_idx_mask) {
@@ -920,14 +883,12 @@ __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_af
     uint32_t part_off = t - boff[k] / S;
     xyzz_lazy_t acc = xyzz_lazy_t::infinity();
     auto slot_of = [&](uint32_t e) -> const g1_lazy_slot_t* { return (const g1_lazy_slot_t*)&bases[(e & 0x7fffffffu) & debug_idx_mask]; };
-    // Software pipeline of the gather.  PREFETCH (one wave per SIMD, nothing else hides latency): two stages - the INDEX of entry
+    // Software pipeline of the gather (one wave per SIMD, nothing else hides latency): two stages - the INDEX of entry
     // pos + 2 and the BASE of entry pos + 1 are requested before the addition of entry pos starts, so neither the index load nor
-    // the dependent base load (index -> address) is ever waited for with an idle SIMD.  Otherwise (two resident waves): the index
-    // one iteration ahead, the base at its use.
+    // the dependent base load (index -> address) is ever waited for with an idle SIMD.
     uint32_t e_cur = sorted[lo];
     uint32_t e_n1 = lo + 1 < hi ? sorted[lo + 1] : 0u;
-    g1_lazy_slot_t raw_next;
-    if (PREFETCH) raw_next = *slot_of(e_cur);
+    g1_lazy_slot_t raw_next = *slot_of(e_cur);
     for (uint32_t pos = lo;; pos++) {
         const bool end = pos >= hi;
         if (end || pos >= kend) {
@@ -949,13 +910,8 @@ __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_af
             start_k = start[k];
         }
         const uint32_t e = e_cur;
-        g1_lazy_slot_t raw;
-        if (PREFETCH) {
-            raw = raw_next;
-            if (pos + 1 < hi) raw_next = *slot_of(e_n1);  // e_n1 arrived during the previous addition
-        } else {
-            raw = *slot_of(e);
-        }
+        const g1_lazy_slot_t raw = raw_next;
+        if (pos + 1 < hi) raw_next = *slot_of(e_n1);  // e_n1 arrived during the previous addition
         e_cur = e_n1;
         if (pos + 2 < hi) e_n1 = sorted[pos + 2];
         if (raw.w[26]) continue;  // the point at infinity
@@ -971,83 +927,6 @@ __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_af
             acc = tmp;
         }
     }
-}
-
-// ---- G2: the same kernel on the lazily reduced Fq2 arithmetic of ffl2.hip.h (round 4).  Base slots: g2_lazy_slot_t (canonical residues
-// of the four coordinate components times 2^406, unpacked); partial sums leave raw (104 limbs) and g2_partials_to_exact_kernel converts
-// them for the tail kernels; exceptional additions are resolved out of line on the exact arithmetic.
-static __global__ void __launch_bounds__(256) g2_partials_to_exact_kernel(const g2_lazy_partial_t* __restrict__ raw, xyzz_mem_t<fq2_t>* __restrict__ partial,
-                                                                   const uint32_t* __restrict__ start, uint32_t nbt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= start[nbt]) return;
-    store_xyzz<fq2_t>(&partial[i], xyzz_lazy2_t::exact_from_raw(&raw[i]));
-}
-// (inlined: an out-of-line call from this 400-register kernel never returns on gfx950 / ROCm 7.2 - tools/exp/g2lazy_dev.hip reproduces it in
-// 60 lines, with the call the second addition of a doubled point hangs, inlined it matches the host chain; the G1 kernel's 248 registers
-// keep its call working.  The cold code costs the hot loop nothing measurable: the two blocks of the addition keep their instruction counts.)
-static __device__ __forceinline__ void lazy2_exceptional_add(xyzz_lazy2_t* acc, const fq2l_t* px, const fq2l_t* py, bool neg) {
-    xyzz_t<fq2_t> ex = acc->to_exact();
-    const fq_t c348 = fq_t::from_table(FqLConv::C348);
-    fq_t t[4];
-#pragma unroll
-    for (int i = 0; i < 13; i++) {
-        t[0].v[i] = (uint32_t)px->c0.v[i], t[1].v[i] = (uint32_t)px->c1.v[i];
-        t[2].v[i] = (uint32_t)py->c0.v[i], t[3].v[i] = (uint32_t)py->c1.v[i];
-    }
-    ex.add_affine({{t[0] * c348, t[1] * c348}, {t[2] * c348, t[3] * c348}}, neg);
-    *acc = xyzz_lazy2_t::from_exact(ex);
-}
-template <bool PREFETCH>
-__global__ void __launch_bounds__(256, 1) msm_accumulate_lazy2_kernel(const aff_mem_t<fq2_t>* __restrict__ bases, const uint32_t* __restrict__ sorted,
-                                                               const uint32_t* __restrict__ boff, const uint32_t* __restrict__ start,
-                                                               g2_lazy_partial_t* __restrict__ partial, uint32_t nbt, uint32_t S, uint32_t debug_idx_mask) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t total = boff[nbt];
-    const uint64_t lo64 = (uint64_t)t * S;
-    if (lo64 >= total) return;
-    const uint32_t lo = (uint32_t)lo64;
-    const uint32_t hi = (total - lo < S) ? total : lo + S;
-    uint32_t k = find_bucket(boff, nbt, lo);
-    uint32_t kend = boff[k + 1];
-    uint32_t kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];  // bucket bookkeeping one bucket ahead (see msm_accumulate_lazy_kernel)
-    uint32_t start_k = start[k];
-    uint32_t part_off = t - boff[k] / S;
-    xyzz_lazy2_t acc = xyzz_lazy2_t::infinity();
-    auto slot_of = [&](uint32_t e) -> const g2_lazy_slot_t* { return (const g2_lazy_slot_t*)&bases[(e & 0x7fffffffu) & debug_idx_mask]; };
-    uint32_t e_cur = sorted[lo];
-    uint32_t e_n1 = lo + 1 < hi ? sorted[lo + 1] : 0u;
-    for (uint32_t pos = lo;; pos++) {
-        const bool end = pos >= hi;
-        if (end || pos >= kend) {
-            acc.store_raw(&partial[start_k + part_off]);
-            if (end) break;
-            part_off = 0;
-            acc.inf = true;
-            k++;
-            kend = kend2;
-            while (pos >= kend) {
-                k++;
-                kend = boff[k + 1];
-            }
-            kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];
-            start_k = start[k];
-        }
-        const uint32_t e = e_cur;
-        const g2_lazy_slot_t* sp = slot_of(e);
-        e_cur = e_n1;
-        if (pos + 2 < hi) e_n1 = sorted[pos + 2];
-        if (sp->w[g2_lazy_slot_t::INF_WORD]) continue;  // the point at infinity
-        const bool neg = (e >> 31) != 0;
-        fq2l_t px, py;
-        sp->coords(px, py);
-        if (!acc.madd(px, py, neg)) {
-            xyzz_lazy2_t tmp = acc;
-            const fq2l_t tx = px, ty = py;
-            lazy2_exceptional_add(&tmp, &tx, &ty, neg);
-            acc = tmp;
-        }
-    }
-    (void)PREFETCH;  // the 52-limb slot is read at its use: a second resident slot would not fit the register file
 }
 
 // ---- G2 on a lane pair (round 5; ffl2p.hip.h): lanes 2 t and 2 t + 1 walk segment t together, the even lane holding the c0 component of

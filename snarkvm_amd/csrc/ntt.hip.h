@@ -29,7 +29,6 @@
 #include <vector>
 
 #include "ff.hip.h"
-#include "frs.hip.h"
 #include "tuning.hip.h"
 
 namespace sv {
@@ -230,7 +229,7 @@ struct ntt_lds_t {
     uint32_t* tw;    // 9 planes of NL = 2^(a-1) limbs: the powers of this pass' own root w_(2^a) (internal form)
     int NL;
     int E;
-    template <class E>  // fr_t (unsigned limbs) or frs_t (signed limbs): nine 32-bit words either way
+    template <class E>  // fr_t: nine 32-bit words
     __device__ __forceinline__ E get(int e) const {
         E x;
 #pragma unroll
@@ -261,8 +260,8 @@ __device__ __forceinline__ void lazy_butterfly(fr_t& u, fr_t& v, int s, int tw_i
     v = dif;
 }
 
-// The arithmetic of a pass as a policy: `ntt_arith_u` = the unsigned lazy routines of round 3 (tuning ntt_signed=0), `ntt_arith_s` =
-// the signed limbs of frs.hip.h (default).  tw(): a word of the ff.hip.h twiddle tables (w * 2^261) in the form mul() wants.
+// The arithmetic of a pass: the unsigned lazy routines of round 3.  tw(): a word of the ff.hip.h twiddle tables (w * 2^261) in the
+// form mul() wants.  (A signed-limb twin of this struct was measured and retired: HISTORY.md, "retired variants".)
 struct ntt_arith_u {
     typedef fr_t elem;
     __device__ __forceinline__ static elem from_canonical(const fr_t& x) { return x; }
@@ -276,34 +275,6 @@ struct ntt_arith_u {
         fr_t z = y.reduce_lazy();
         if (a > 8) z = z.reduce_lazy();
         return z;
-    }
-};
-struct ntt_arith_s {
-    typedef frs_t elem;
-    __device__ __forceinline__ static elem from_canonical(const fr_t& x) { return frs_t::from_canonical(x); }
-    // (u, v) -> (u + v, (u - v) w): the sum carry-normalised, the difference raw into the product (frs.hip.h); w = 1: the difference
-    // is only normalised
-    __device__ __forceinline__ static void butterfly(elem& u, elem& v, int s, int tw_idx, const ntt_lds_t& L) {
-        (void)s;
-        const elem sum = frs_t::add_norm(u, v);
-        if (tw_idx != 0) {
-            v = frs_t::mul(frs_t::sub_raw(u, v), L.twiddle(tw_idx));
-        } else {
-            elem neg;
-#pragma unroll
-            for (int i = 0; i < 9; i++) neg.v[i] = -v.v[i];
-            v = frs_t::add_norm(u, neg);
-        }
-        u = sum;
-    }
-    __device__ __forceinline__ static fr_t tw(const fr_t& w_int) { return frs_t::twiddle_form(w_int); }
-    __device__ __forceinline__ static fr_t one() { return fr_t::from_table(FrS::C290); }
-    // the closing product of a pass: a normalised value against a table word (frs.hip.h: hide_range)
-    __device__ __forceinline__ static elem mul(const elem& x, const fr_t& w) { return frs_t::mul(x.hide_range(), w); }
-    __device__ __forceinline__ static elem reduce_only(const elem& x) { return frs_t::reduce_only(x); }
-    __device__ __forceinline__ static fr_t finish(const elem& y, int a) {
-        (void)a;
-        return y.to_canonical();
     }
 };
 
@@ -626,19 +597,15 @@ struct ntt_ctx_t {
     std::vector<void*>* leases;
 };
 // fold: 0 plain, 1 times 2^261, 2 times 2^261 * size_inv (size_inv points at the Montgomery form of n^-1)
-// arith_signed: the table serves frs.hip.h (R = 2^290): plain entries carry 2^290 instead of 2^261, folded ones 2^580 instead of 2^522
 static __global__ void ntt_fill_full_tw_kernel(fr_mem_t* __restrict__ out, int a, int s, int tw_shift, const fr_mem_t* __restrict__ lo,
-                                        const fr_mem_t* __restrict__ hi, const fr_mem_t* __restrict__ top, int fold, const fr_mem_t* __restrict__ size_inv,
-                                        int arith_signed) {
+                                        const fr_mem_t* __restrict__ hi, const fr_mem_t* __restrict__ top, int fold, const fr_mem_t* __restrict__ size_inv) {
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= ((size_t)1 << (a + s))) return;
     const uint32_t k = (uint32_t)(idx >> s), inner = (uint32_t)(idx & (((size_t)1 << s) - 1));
     fr_t t = ntt_pow_compose(lo, hi, top, ntt_tw_index((inner * k) << tw_shift));
     if (fold) {
-        t = t * fr_t::from_table(arith_signed ? FrS::C580 : FrP::R2);  // Montgomery form of (2^261 mod r): the stored word becomes t * 2^522 (signed: t * 2^580)
+        t = t * fr_t::from_table(FrP::R2);  // Montgomery form of (2^261 mod r): the stored word becomes t * 2^522
         if (fold == 2) t = t * fr_t::load(size_inv);
-    } else if (arith_signed) {
-        t = frs_t::twiddle_form(t);
     }
     t.store(&out[idx]);
 }
@@ -681,7 +648,7 @@ static inline const fr_mem_t* ntt_get_full_tw(const ntt_ctx_t& cx, int a, int s,
         cache.bytes += need;
         const int fold = !prelast_lg ? 0 : (dir == NTT_INVERSE ? 2 : 1);
         hipLaunchKernelGGL(ntt_fill_full_tw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cx.st, slot.p, a, s, tw_shift, cx.tb->pow_lo[dir],
-                           cx.tb->pow_hi[dir], cx.tb->pow_top[dir], fold, (const fr_mem_t*)(cx.tb->size_inv + (prelast_lg ? prelast_lg : 0)), tuning().ntt_signed ? 1 : 0);
+                           cx.tb->pow_hi[dir], cx.tb->pow_top[dir], fold, (const fr_mem_t*)(cx.tb->size_inv + (prelast_lg ? prelast_lg : 0)));
         (void)hipStreamSynchronize(cx.st);  // other streams may use the table from now on
     }
     slot.last_use = ++cache.tick;
@@ -699,13 +666,8 @@ static inline void ntt_launch_pass(hipStream_t st, const ntt_pass_t& p, const nt
         if (threads < 64) threads = 64;
         if (threads > 512) threads = 512;
         const size_t shmem = (9 * E + 9 * ((size_t)1 << (p.a ? p.a - 1 : 0))) * sizeof(uint32_t);  // a [2^8 x 8] tile + its twiddles: 78 KB, two workgroups per CU
-        const bool sg = tuning().ntt_signed != 0;
-        if (bt && sg)
-            hipLaunchKernelGGL((ntt_pass_kernel_v2<true, ntt_arith_s>), dim3((unsigned)ntiles, nvec), dim3(threads), shmem, st, p, tb, *bt);
-        else if (bt)
+        if (bt)
             hipLaunchKernelGGL((ntt_pass_kernel_v2<true, ntt_arith_u>), dim3((unsigned)ntiles, nvec), dim3(threads), shmem, st, p, tb, *bt);
-        else if (sg)
-            hipLaunchKernelGGL((ntt_pass_kernel_v2<false, ntt_arith_s>), dim3((unsigned)ntiles), dim3(threads), shmem, st, p, tb, ntt_no_batch_t{});
         else
             hipLaunchKernelGGL((ntt_pass_kernel_v2<false, ntt_arith_u>), dim3((unsigned)ntiles), dim3(threads), shmem, st, p, tb, ntt_no_batch_t{});
     }

@@ -256,26 +256,13 @@ struct device_t {
     void init() {  // the calling thread has this device current
         std::lock_guard<std::mutex> lk(init_mu);
         if (ready) return;
-        // The upper half of the lanes runs on LOW-priority streams (tuning aux_low_prio): a scope hands its asynchronous MSMs - the work that is NOT on the caller's
-        // critical path: the independent G2 MSM of a proof, commitments whose results are only due at scope_end - to those lanes (take_for_scope searches from the
-        // top), ordinary calls and the scopes' own lanes take from the bottom.  When the chip is contended the dispatcher serves the critical stream first and the
-        // background MSM fills the gaps the transcript order leaves (one proof in Fiat-Shamir order idles the GPU ~1.3 ms between its rounds).  With more than
-        // LANES / 2 concurrent callers ordinary calls reach those lanes too: they then simply share one priority level among themselves.
-        int prio_low = 0, prio_high = 0;
-        if (hipDeviceGetStreamPriorityRange(&prio_low, &prio_high) != hipSuccess) prio_low = prio_high = 0;  // (numerically: low >= high)
+        // A scope hands its asynchronous MSMs - the work that is NOT on the caller's critical path: the independent G2 MSM of a proof, commitments whose results
+        // are only due at scope_end - to the upper half of the lanes (take_for_scope searches from the top); ordinary calls and the scopes' own lanes take from the
+        // bottom.  Every lane has the same kind of stream: a low priority or a compute-unit mask for the upper half was measured and retired (HISTORY.md).
         for (int l = 0; l < LANES; l++) {
             lane[l].dev = this;
             lane[l].index = l;
-            if (l >= LANES / 2 && tuning().aux_cus > 0) {
-                // (experiment, tuning aux_cus = N: the same lanes on streams that may only use the first N compute units of the mask order - a background MSM
-                // then cannot take the whole chip away from the critical stream for the length of its fold)
-                uint32_t mask[8] = {0};
-                for (int b = 0; b < tuning().aux_cus && b < 256; b++) mask[b >> 5] |= 1u << (b & 31);
-                HIP_TRY(hipExtStreamCreateWithCUMask(&lane[l].stream, 8, mask));
-            } else if (l >= LANES / 2 && tuning().aux_low_prio && prio_low != prio_high)
-                HIP_TRY(hipStreamCreateWithPriority(&lane[l].stream, hipStreamNonBlocking, prio_low));
-            else
-                HIP_TRY(hipStreamCreateWithFlags(&lane[l].stream, hipStreamNonBlocking));
+            HIP_TRY(hipStreamCreateWithFlags(&lane[l].stream, hipStreamNonBlocking));
             HIP_TRY(hipStreamCreateWithFlags(&lane[l].alt, hipStreamNonBlocking));
             for (auto& e : lane[l].ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
@@ -451,8 +438,6 @@ static void tu_kernel_attributes(int logical) {
 #ifdef SV_TU_NTT  // the unit that launches the NTT passes (api_fr.hip)
     HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<false, ntt_arith_u>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
     HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<true, ntt_arith_u>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<false, ntt_arith_s>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<true, ntt_arith_s>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
 #endif
     done[logical] = 1;
 }
@@ -905,10 +890,10 @@ static msm_tail_geom_t msm_tail_geometry(const msm_plan_t& pl, uint32_t nwin, ms
     return g;
 }
 // 7.-9. of msm_run: per-bucket partial-sum lists (sums, start, cnt) -> fold -> bit-plane sums -> copy to `host_planes` (the host runs
-// the Horner chain).  flat: flattened-list fold (any distribution of the partial sums over the buckets).
+// the Horner chain).  The fold takes any distribution of the partial sums over the buckets (msm.hip.h 7a: flattened lists).
 template <class F>
 static void msm_tail_launch(lane_t& c, const msm_plan_t& pl, const msm_tail_geom_t& g, uint32_t nwin, uint32_t nbt, const xyzz_mem_t<F>* sums,
-                            const uint32_t* start, const uint32_t* cnt, bool flat, const msm_pending_t& pd, void* host_planes) {
+                            const uint32_t* start, const uint32_t* cnt, const msm_pending_t& pd, void* host_planes) {
     hipStream_t st = c.stream;
     c.planes.ensure((size_t)pd.nplanes * sizeof(xyzz_mem_t<F>));
     const bool is_g2 = sizeof(F) == sizeof(fq2_t);
@@ -948,12 +933,8 @@ static void msm_tail_launch(lane_t& c, const msm_plan_t& pl, const msm_tail_geom
         if (sizeof(F) > 64 && fold_threads == 256u && fold_blocks <= 256u && (tuning().fold_small2 == 128 || tuning().fold_small2 == 64)) fold_threads = (unsigned)tuning().fold_small2;
         if (fold_threads == 64u) quads_fold = 0;
         const dim3 fold_grid((1u << g.fold_m) + (1u << g.fold_hb), (unsigned)nwin);
-        if (flat || fold_threads != 64u)
-            hipLaunchKernelGGL((msm_fold_kernel<F, true>), fold_grid, dim3(fold_threads), 0, st, sums, start, cnt, c.fold_sums.as<xyzz_mem_t<F>>(), g.fold_m, g.fold_hb, hex,
-                               quads_fold, fold_flags);
-        else
-            hipLaunchKernelGGL((msm_fold_kernel<F, false>), fold_grid, dim3(fold_threads), 0, st, sums, start, cnt, c.fold_sums.as<xyzz_mem_t<F>>(), g.fold_m, g.fold_hb, hex,
-                               quads_fold, fold_flags);
+        hipLaunchKernelGGL((msm_fold_kernel<F>), fold_grid, dim3(fold_threads), 0, st, sums, start, cnt, c.fold_sums.as<xyzz_mem_t<F>>(), g.fold_m, g.fold_hb, hex, quads_fold,
+                           fold_flags);
         if constexpr (TAIL_FLAGGED<F>::value)
             hipLaunchKernelGGL((msm_fold_fix_kernel<F>), fold_grid, dim3(64), 0, st, sums, start, cnt, c.fold_sums.as<xyzz_mem_t<F>>(), g.fold_m, g.fold_hb,
                                (const uint32_t*)fold_flags);
@@ -991,7 +972,7 @@ struct msm_bucket_sink_t {
 // bigger MSM; pd.nplanes = 0) or fold -> bit planes -> copy to `host_planes`.
 template <class T, class PB, class PE>
 static void msm_reduce_and_tail(lane_t& c, const msm_plan_t& pl, const msm_tail_geom_t& tg, uint32_t nwin, uint32_t nbt, int rounds, size_t T0_max, size_t T1_max,
-                                const msm_bucket_sink_t* sink, msm_pending_t& pd, void* host_planes, bool flat, PB&& phase_begin, PE&& phase_end) {
+                                const msm_bucket_sink_t* sink, msm_pending_t& pd, void* host_planes, PB&& phase_begin, PE&& phase_end) {
     hipStream_t st = c.stream;
     phase_begin("msm_reduce_partials");
     uint32_t *cnt_in = c.cnt_a.as<uint32_t>(), *cnt_out = c.cnt_b.as<uint32_t>();
@@ -1024,8 +1005,60 @@ static void msm_reduce_and_tail(lane_t& c, const msm_plan_t& pl, const msm_tail_
         return;
     }
     phase_begin("msm_bucket_reduce");
-    msm_tail_launch<T>(c, pl, tg, nwin, nbt, pin, start_in, cnt_in, flat, pd, host_planes);
+    msm_tail_launch<T>(c, pl, tg, nwin, nbt, pin, start_in, cnt_in, pd, host_planes);
     phase_end();
+}
+// Step 5 of msm_run: the accumulate launch for F - G1 on the lazy arithmetic (ffl.hip.h), G2 on a lane pair (ffl2p.hip.h), or F's exact kernel
+// (tuning lazy / lazy2 = 0) - `nthreads` segments of pl.S sorted entries, per-bucket partial sums into part_a (start_a: their slots).
+// one_wave: a single-round grid of at most 2^22 entries runs one wave per SIMD, where nothing else hides the base gather.
+template <class F>
+static void msm_launch_accumulate(lane_t& c, const msm_plan_t& pl, const aff_mem_t<F>* vbase, uint32_t* boffp, uint32_t nbt, size_t nthreads, bool one_wave,
+                                  bool ltail) {
+    hipStream_t st = c.stream;
+#ifdef SV_BENCH  // profiling builds only (wrong results): restrict the gather to the first 2^k bases to separate ALU time from HBM gather time
+    static const uint32_t dbg_mask = getenv("SNARKVM_HIP_DEBUG_IDX_MASK") ? (uint32_t)strtoul(getenv("SNARKVM_HIP_DEBUG_IDX_MASK"), nullptr, 0) : 0xffffffffu;
+#else
+    constexpr uint32_t dbg_mask = 0xffffffffu;
+#endif
+    const size_t tmax = nthreads + nbt + 1;  // every thread leaves >= 1 partial sum, one more per bucket boundary inside its segment
+    if constexpr (sizeof(F) == sizeof(fq_t)) {
+        if (msm_lazy_on<F>()) {
+            // lazy tail: the raw partial sums (208 B each) ARE the tail's input (part_a holds T0_max >= tmax of them); else they go to their own
+            // buffer and the dense conversion pass fills part_a
+            if (!ltail) c.part_raw.ensure(tmax * sizeof(g1_lazy_partial_t));
+            g1_lazy_partial_t* raw_out = ltail ? c.part_a.as<g1_lazy_partial_t>() : c.part_raw.as<g1_lazy_partial_t>();
+            // One workgroup per CU (a dynamic LDS request no second workgroup fits beside) = one accumulate wave per SIMD with half
+            // of the register file and ~64 KB of LDS left free: single-round grids always; multi-round grids when
+            // tuning acc_one_wg is set - the sort and tail kernels of the NEXT instance of a pipelined batch (another
+            // lane's stream) then find room beside the accumulate waves instead of waiting for gaps between its rounds.
+            // (a 3-waves-per-SIMD build of this kernel - 168 VGPRs - was measured: no gain)
+            hipLaunchKernelGGL((msm_accumulate_lazy_kernel<true>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), one_wave || tuning().acc_one_wg ? msm_acc_lds() : 0, st,
+                               vbase, c.sorted.as<uint32_t>(), boffp, c.start_a.as<uint32_t>(), raw_out, nbt, pl.S, dbg_mask);
+            if (!ltail)
+                hipLaunchKernelGGL(g1_partials_to_exact_kernel, dim3((unsigned)((tmax + 255) / 256)), dim3(256), 0, st, (const g1_lazy_partial_t*)raw_out,
+                                   c.part_a.as<g1_xyzz_mem_t>(), (const uint32_t*)c.start_a.as<uint32_t>(), nbt);
+            return;
+        }
+    } else {
+#ifndef SV_NO_G2
+        if (msm_lazy_on<F>()) {
+            // two lanes per segment, two waves per SIMD; raw 512-byte partial sums, then the dense conversion
+            c.part_raw.ensure(tmax * sizeof(g2_pair_partial_t));
+            hipLaunchKernelGGL((msm_accumulate_pair2_kernel<false>), dim3((unsigned)((2 * nthreads + 255) / 256)), dim3(256), 0, st, vbase, c.sorted.as<uint32_t>(),
+                               boffp, c.start_a.as<uint32_t>(), c.part_raw.as<g2_pair_partial_t>(), nbt, pl.S, dbg_mask);
+            hipLaunchKernelGGL(g2_pair_partials_to_exact_kernel, dim3((unsigned)((8 * tmax + 255) / 256)), dim3(256), 0, st,
+                               (const g2_pair_partial_t*)c.part_raw.as<g2_pair_partial_t>(), c.part_a.as<xyzz_mem_t<fq2_t>>(),
+                               (const uint32_t*)c.start_a.as<uint32_t>(), nbt);
+            return;
+        }
+#endif
+    }
+    if (one_wave)  // software-pipelined gather
+        hipLaunchKernelGGL((msm_accumulate_seg_kernel<F, 1, true>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase, c.sorted.as<uint32_t>(), boffp,
+                           c.start_a.as<uint32_t>(), c.part_a.as<xyzz_mem_t<F>>(), nbt, pl.S, dbg_mask);
+    else
+        hipLaunchKernelGGL((msm_accumulate_seg_kernel<F, 1, false>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase, c.sorted.as<uint32_t>(), boffp,
+                           c.start_a.as<uint32_t>(), c.part_a.as<xyzz_mem_t<F>>(), nbt, pl.S, dbg_mask);
 }
 // Device side of one MSM on lane `c`: d_bases = converted device bases; d_scalars = device scalars (32 B each).  Everything
 // is enqueued on the lane's stream, ending with the copy of the bit-plane sums into `host_planes` (pinned, >=
@@ -1197,14 +1230,10 @@ static msm_pending_t msm_run(lane_t& c, const aff_mem_t<F>* d_bases, const uint4
             uint32_t* choff = csum + ngroups;
             phase_begin("msm_scalar_read");
             const size_t hist_lds = (size_t)keys * 4;
-            // hist = 2: 1 024-thread workgroups with four private histogram copies (msm_sort.hip.h); 1: the round-3 kernel
-            const int hist_variant = tuning().hist;
+            // 1 024-thread workgroups with four private histogram copies (msm_sort.hip.h)
 #define SV_FUSED_HIST(CB)                                                                                                                         \
     case CB:                                                                                                                                      \
-        if (hist_variant == 2)                                                                                                                    \
-            hipLaunchKernelGGL((radix_hist1_wide_kernel<CB>), dim3(ntiles), dim3(HISTW_THREADS), hist_lds * HISTW_COPIES, st, d_scalars, counts1, rp, dp); \
-        else                                                                                                                                      \
-            hipLaunchKernelGGL((radix_hist1_fused_kernel<CB>), dim3(ntiles), dim3(FUSED_THREADS), hist_lds, st, d_scalars, counts1, rp, dp);     \
+        hipLaunchKernelGGL((radix_hist1_wide_kernel<CB>), dim3(ntiles), dim3(HISTW_THREADS), hist_lds * HISTW_COPIES, st, d_scalars, counts1, rp, dp); \
         break;
             switch (pl.c) { SV_FUSED_HIST(17) SV_FUSED_HIST(18) SV_FUSED_HIST(19) SV_FUSED_HIST(20) SV_FUSED_HIST(21) SV_FUSED_HIST(22) }
 #undef SV_FUSED_HIST
@@ -1319,84 +1348,19 @@ static msm_pending_t msm_run(lane_t& c, const aff_mem_t<F>* d_bases, const uint4
             if (mu && tuning().fuse_reduce < 0) rounds = mu->K >= 8 ? 1 : 0;
             hipLaunchKernelGGL(msm_alloc_seg_kernel, dim3((nbt + 1 + 255) / 256), dim3(256), 0, st, boffp, c.cnt_a.as<uint32_t>(), nbt, pl.S);
             exclusive_scan_u32(st, c.cnt_a.as<uint32_t>(), c.start_a.as<uint32_t>(), (size_t)nbt + 1, c.scan_tmp.as<uint32_t>());
-            const size_t nthreads = (E_max + pl.S - 1) / pl.S;
-#ifdef SV_BENCH  // profiling builds only (wrong results): restrict the gather to the first 2^k bases to separate ALU time from HBM gather time
-            static const uint32_t dbg_mask = getenv("SNARKVM_HIP_DEBUG_IDX_MASK") ? (uint32_t)strtoul(getenv("SNARKVM_HIP_DEBUG_IDX_MASK"), nullptr, 0) : 0xffffffffu;
-#else
-            constexpr uint32_t dbg_mask = 0xffffffffu;
-#endif
-            // (a 3-waves-per-SIMD build of this kernel - 168 VGPRs - and a software-pipelined gather were measured: no gain)
-            const int prefetch_env = tuning().prefetch;  // 0: never, 1: single-round launches only, 2: always (lazy kernel: -2 .. 3 %)
-            if constexpr (sizeof(F) == sizeof(fq_t)) {
-                if (msm_lazy_on<F>()) {
-                    // raw partial sums (208 B each) go to their own buffer; the dense conversion pass fills part_a for the tail
-                    const size_t tmax = nthreads + nbt + 1;  // every thread leaves >= 1 partial sum, one more per bucket boundary inside its segment
-                    // lazy tail: the raw partial sums ARE the tail's input (part_a holds T0_max >= tmax of them); else they go to their own
-                    // buffer and the dense conversion pass fills part_a
-                    if (!ltail) c.part_raw.ensure(tmax * sizeof(g1_lazy_partial_t));
-                    g1_lazy_partial_t* raw_out = ltail ? c.part_a.as<g1_lazy_partial_t>() : c.part_raw.as<g1_lazy_partial_t>();
-                    // One workgroup per CU (a dynamic LDS request no second workgroup fits beside) = one accumulate wave per SIMD with half
-                    // of the register file and ~64 KB of LDS left free: single-round grids always; multi-round grids when
-                    // tuning acc_one_wg is set - the sort and tail kernels of the NEXT instance of a pipelined batch (another
-                    // lane's stream) then find room beside the accumulate waves instead of waiting for gaps between its rounds.
-                    const int one_wg_env = tuning().acc_one_wg;
-                    if ((single_round && prefetch_ok && prefetch_env) || prefetch_env >= 2)
-                        hipLaunchKernelGGL((msm_accumulate_lazy_kernel<true>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256),
-                                           (single_round && prefetch_ok) || one_wg_env ? msm_acc_lds() : 0, st, vbase, c.sorted.as<uint32_t>(), boffp, c.start_a.as<uint32_t>(),
-                                           raw_out, nbt, pl.S, dbg_mask);
-                    else
-                        hipLaunchKernelGGL((msm_accumulate_lazy_kernel<false>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase,
-                                           c.sorted.as<uint32_t>(), boffp, c.start_a.as<uint32_t>(), raw_out, nbt, pl.S, dbg_mask);
-                    if (!ltail)
-                        hipLaunchKernelGGL(g1_partials_to_exact_kernel, dim3((unsigned)((tmax + 255) / 256)), dim3(256), 0, st,
-                                           (const g1_lazy_partial_t*)raw_out, c.part_a.as<g1_xyzz_mem_t>(), (const uint32_t*)c.start_a.as<uint32_t>(), nbt);
-                    goto accumulated;
-                }
-            } else {
-#ifndef SV_NO_G2
-                if (msm_lazy_on<F>() && tuning().pair2) {
-                    // G2 on a lane pair (ffl2p.hip.h): two lanes per segment, two waves per SIMD; raw 512-byte partial sums, then the dense conversion
-                    const size_t tmax = nthreads + nbt + 1;
-                    c.part_raw.ensure(tmax * sizeof(g2_pair_partial_t));
-                    hipLaunchKernelGGL((msm_accumulate_pair2_kernel<false>), dim3((unsigned)((2 * nthreads + 255) / 256)), dim3(256), 0, st, vbase, c.sorted.as<uint32_t>(),
-                                       boffp, c.start_a.as<uint32_t>(), c.part_raw.as<g2_pair_partial_t>(), nbt, pl.S, dbg_mask);
-                    hipLaunchKernelGGL(g2_pair_partials_to_exact_kernel, dim3((unsigned)((8 * tmax + 255) / 256)), dim3(256), 0, st,
-                                       (const g2_pair_partial_t*)c.part_raw.as<g2_pair_partial_t>(), c.part_a.as<xyzz_mem_t<fq2_t>>(),
-                                       (const uint32_t*)c.start_a.as<uint32_t>(), nbt);
-                    goto accumulated;
-                }
-                if (msm_lazy_on<F>()) {  // G2 on the lazy Fq2 arithmetic of ffl2.hip.h: raw 416-byte partial sums, then the dense conversion
-                    const size_t tmax = nthreads + nbt + 1;
-                    c.part_raw.ensure(tmax * sizeof(g2_lazy_partial_t));
-                    hipLaunchKernelGGL((msm_accumulate_lazy2_kernel<false>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase,
-                                       c.sorted.as<uint32_t>(), boffp, c.start_a.as<uint32_t>(), c.part_raw.as<g2_lazy_partial_t>(), nbt, pl.S, dbg_mask);
-                    hipLaunchKernelGGL(g2_partials_to_exact_kernel, dim3((unsigned)((tmax + 255) / 256)), dim3(256), 0, st,
-                                       (const g2_lazy_partial_t*)c.part_raw.as<g2_lazy_partial_t>(), c.part_a.as<xyzz_mem_t<fq2_t>>(),
-                                       (const uint32_t*)c.start_a.as<uint32_t>(), nbt);
-                    goto accumulated;
-                }
-#endif
-            }
-            if (single_round && prefetch_ok && prefetch_env)
-                hipLaunchKernelGGL((msm_accumulate_seg_kernel<F, 1, true>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase,
-                                   c.sorted.as<uint32_t>(), boffp, c.start_a.as<uint32_t>(), c.part_a.as<xyzz_mem_t<F>>(), nbt, pl.S, dbg_mask);
-            else
-                hipLaunchKernelGGL((msm_accumulate_seg_kernel<F, 1, false>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase,
-                                   c.sorted.as<uint32_t>(), boffp, c.start_a.as<uint32_t>(), c.part_a.as<xyzz_mem_t<F>>(), nbt, pl.S, dbg_mask);
-        accumulated:;
+            msm_launch_accumulate<F>(c, pl, vbase, boffp, nbt, (E_max + pl.S - 1) / pl.S, single_round && prefetch_ok, ltail);
         }
         phase_end();
     }
     // 6.-9. reduce rounds, then the bucket merge (a chunk of a bigger MSM) or fold -> bit-plane sums -> (host) Horner: on the lazy arithmetic
     // when the accumulate kernel left raw partial sums (G1, tuning lazy_tail), else on F's exact arithmetic
-    const bool flat = single_round || tuning().fold_flat != 0;
     if constexpr (sizeof(F) == sizeof(fq_t)) {
         if (ltail) {
-            msm_reduce_and_tail<fqz_t>(c, pl, tg, nwin, nbt, rounds, T0_max, T1_max, sink, pd, host_planes, flat, phase_begin, phase_end);
+            msm_reduce_and_tail<fqz_t>(c, pl, tg, nwin, nbt, rounds, T0_max, T1_max, sink, pd, host_planes, phase_begin, phase_end);
             return pd;
         }
     }
-    msm_reduce_and_tail<F>(c, pl, tg, nwin, nbt, rounds, T0_max, T1_max, sink, pd, host_planes, flat, phase_begin, phase_end);
+    msm_reduce_and_tail<F>(c, pl, tg, nwin, nbt, rounds, T0_max, T1_max, sink, pd, host_planes, phase_begin, phase_end);
     return pd;
 }
 // The tail of a chunked MSM: fold + bit planes over the bucket sink (every bucket holds L partial sums, one per lane).
@@ -1416,12 +1380,12 @@ static msm_pending_t msm_tail_from_sink(lane_t& c, size_t chunk_n, int window_bi
     c.phase_begin("msm_bucket_reduce");
     if constexpr (sizeof(F) == sizeof(fq_t)) {
         if (pd.lazy) {
-            msm_tail_launch<fqz_t>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<fqz_t>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), true, pd, host_planes);
+            msm_tail_launch<fqz_t>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<fqz_t>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), pd, host_planes);
             c.phase_end();
             return pd;
         }
     }
-    msm_tail_launch<F>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<F>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), true, pd, host_planes);
+    msm_tail_launch<F>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<F>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), pd, host_planes);
     c.phase_end();
     return pd;
 }
@@ -1444,7 +1408,7 @@ static void msm_run_sync(lane_t& c, const aff_mem_t<F>* d_bases, const uint4* d_
     c.phase_host("msm_host_finish", host_now_ms() - t0);  // the Horner chain over the bit planes, on the calling thread
 }
 
-// Accumulation runs on the lazily reduced arithmetic: G1 on ffl.hip.h (tuning lazy=0: the exact kernel), G2 on ffl2.hip.h (tuning
+// Accumulation runs on the lazily reduced arithmetic: G1 on ffl.hip.h (tuning lazy=0: the exact kernel), G2 on the lane pair of ffl2p.hip.h (tuning
 // lazy2=0).  Process wide: every base slot an MSM of that group reads - registered tables and the staging of table-less calls - then
 // holds form406.
 template <class F>

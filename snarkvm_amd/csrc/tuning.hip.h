@@ -7,7 +7,8 @@
 //     SNARKVM_HIP_TUNING="key=value,key=value,..."        (unknown keys are an error reported on stderr and ignored)
 //
 // Every key is an A/B switch whose two sides return bit-identical results (tests/test_gpu_multidevice.py runs the suite's
-// MSM / NTT checks under each of them); the defaults are the measured winners and are what DESIGN.md describes.  Operational
+// MSM / NTT checks under each of them); the defaults are the measured winners and are what DESIGN.md describes.  A variant that lost
+// its measurement and is no fallback for anything leaves the tree together with its key (HISTORY.md, "retired variants").  Operational
 // configuration - not tuning - keeps its own, documented variables: SNARKVM_HIP_DEVICES (device set), SNARKVM_HIP_BASE_CACHE /
 // _MB (the opt-in base cache of snarkvm_msm), SNARKVM_HIP_NTT_TW_MB (HBM cap of the closing-twiddle cache), SNARKVM_HIP_TRACE
 // (chunk timeline on stderr).
@@ -20,18 +21,14 @@
 //                            fold / bit-plane kernels spill 808 B at 256 registers): 30.71 vs 30.88 ms per step, 197.4 vs 196.6 proofs/s.  Round 5: ON - where it
 //                            pays is a single proof (no conversion pass in any of its six commitment rounds: 8.49 vs 8.88 ms per proof,
 //                            profiles/r05_proof1_timeline.md)
-//   lazy2           1        G2 accumulation on the signed-limb Fq2 arithmetic (0: exact kernel)
+//   lazy2           1        G2 accumulation on the signed-limb Fq2 arithmetic, one value per lane pair (ffl2p.hip.h: c0 on the even lane, c1 on the odd lane; 0: exact kernel)
 //   fused           1        wide windows: scalar read fused with the level-1 partition (0: stand-alone digit matrix)
-//   hist            2        scalar-read kernel variant (1: 512 threads x 4 scalars, one LDS histogram - round 3; 2: 1 024 threads x 2
-//                            scalars, four private histogram copies)
-//   prefetch        2        base gather software pipeline: 0 never, 1 single-round grids, 2 always
 //   acc_lds         98304    dynamic LDS request that keeps a second accumulate workgroup off a CU (single-round grids); 0: off
 //   acc_one_wg      0        1: one accumulate workgroup per CU for multi-round grids too
 //   reduce_rounds   1        fixed reduce rounds of a multi-round MSM (0 .. 8), each shrinking a bucket's partial sums by the group size (seg2, 16).
 //                            Round 4: one round of 16 instead of two of 8 - for uniform scalars the second round only copied (0.84 -> 0.57 ms of
 //                            reduce time at 2^24, 29.84 -> 29.51 ms per step; one round of 64: 0.99 ms); what an all-equal scalar vector leaves in
 //                            one bucket (2^24: 16 384 partial sums instead of 4 096) goes to the flattened-list fold: ~3 ms more on that input
-//   fold_flat       1        flattened-list fold for every MSM (0: per-bucket lists for big ones)
 //   fuse_batch      1        small instances of a batch travel as fused multi-instance groups
 //   fuse_max_k      64       instances per fused group
 //   fuse_reduce     -1       reduce rounds of a fused group before its fold (0: none; 1: one for every group: +1.6 % on the lock-step proof replay and a bound
@@ -58,7 +55,6 @@
 //   ntt_min_tiles   256      workgroups a small-transform pass is spread over
 //   ntt_full_tw     1        materialised closing-twiddle tables
 //   ntt_fold        1        2^261 [/ n] folded into the table of the pass before the last
-//   ntt_signed      0        1: NTT butterflies on the signed limbs of frs.hip.h (measured: 2.115 vs 2.062 ms of kernels at 2^24 - not faster)
 //   ntt_batch       1        snarkvm_hip_ntt_device_batch: one launch per pass for all vectors of a (direction, type) group
 //   xcd             1        scatter kernels of the radix partition: XCD x walks a contiguous tile range (msm_sort.hip.h::xcd_tile)
 //   fold_threads2   128      G2: threads per output of a small fold (its kernels run one wave per SIMD: 256-thread workgroups = one per CU)
@@ -69,12 +65,6 @@
 //   tail_quads      13       fold / bit planes: quad-strided accumulation in front of the trees (no plain one-lane addition), bit mask: 1 = G2 bit planes, 2 = G2 fold (measured slower: off), 4 = G1 bit planes, 8 = G1 fold
 //   fold_small2     256      G2: threads per output of a fold of <= 256 workgroups (one turn of the chip; 128 / 64: round 5's halved workgroup - an A/B and bisection switch)
 //   fold_mid        128      G1: threads per output of a fold of 513 .. 1 024 workgroups (a fused group of 3 - 4 proof-sized instances); 64: one wave per output
-//   aux_cus         0        experiment: N > 0 creates the upper half of the lanes (where a scope puts its further MSM streams) with a compute-unit mask of N CUs.
-//                            One proof in transcript order, whose only further-stream MSM is the independent G2 one: 8.06 ms with 0, 7.83 - 7.90 with 128, 7.88 - 7.95
-//                            with 192, 8.54 with 64, 9.8 - 10.1 with 32 (two alternating runs, one box) - a background MSM confined to half the chip disturbs the
-//                            critical stream less.  Not the default and not an ABI flag: every mode that puts commitment ROUNDS on those lanes is 1.5 - 5x slower
-//                            under the mask, and the reference's prover issues no such MSM (profiles/r06_summary.md).
-//   pair2           1        G2 accumulation on a lane pair (ffl2p.hip.h: c0 on the even lane, c1 on the odd lane; 0: both components in one lane, ffl2.hip.h)
 //   horner2         1        p / (X - z): three launches with a scan inside every workgroup (0: the four-level chunk recursion of round 3)
 #pragma once
 #include <stdio.h>
@@ -84,12 +74,12 @@
 namespace sv {
 
 struct tuning_t {
-    int lazy = 1, lazy2 = 1, fused = 1, hist = 2, prefetch = 2;
+    int lazy = 1, lazy2 = 1, fused = 1;
     long acc_lds = 96 * 1024;
-    int acc_one_wg = 0, reduce_rounds = 1, fold_flat = 1, fuse_batch = 1, fuse_max_k = 64, fuse_reduce = -1, coalesce = 1, coalesce_us = 40, lanes = 0;
+    int acc_one_wg = 0, reduce_rounds = 1, fuse_batch = 1, fuse_max_k = 64, fuse_reduce = -1, coalesce = 1, coalesce_us = 40, lanes = 0;
     int msm_chunk_lg = 20, scalar_chunk_lg = 22, taper = 1, ring_lanes = 3, seg = 0, seg2 = 0, fold_l = 0, scan1 = 1;
-    int ntt_min_tiles = 256, ntt_full_tw = 1, ntt_fold = 1, ntt_signed = 0, ntt_batch = 1;
-    int xcd = 1, fold_threads2 = 128, coalesce_slots = 2, ramp = 3, scalar_geo = 4, lazy_tail = 1, horner2 = 1, pair2 = 1, hex2 = 1, group_quad = 1, tail_quads = 13, aux_low_prio = 0, fold_small2 = 256, fold_mid = 128, aux_cus = 0;
+    int ntt_min_tiles = 256, ntt_full_tw = 1, ntt_fold = 1, ntt_batch = 1;
+    int xcd = 1, fold_threads2 = 128, coalesce_slots = 2, ramp = 3, scalar_geo = 4, lazy_tail = 1, horner2 = 1, hex2 = 1, group_quad = 1, tail_quads = 13, fold_small2 = 256, fold_mid = 128;
 
     bool set(const char* key, long v) {
 #define SV_TUNE_KEY(name)                  \
@@ -97,11 +87,11 @@ struct tuning_t {
         name = (decltype(name))v;          \
         return true;                       \
     }
-        SV_TUNE_KEY(lazy) SV_TUNE_KEY(lazy2) SV_TUNE_KEY(fused) SV_TUNE_KEY(hist) SV_TUNE_KEY(prefetch) SV_TUNE_KEY(acc_lds)
-        SV_TUNE_KEY(acc_one_wg) SV_TUNE_KEY(reduce_rounds) SV_TUNE_KEY(fold_flat) SV_TUNE_KEY(fuse_batch) SV_TUNE_KEY(fuse_max_k) SV_TUNE_KEY(fuse_reduce) SV_TUNE_KEY(coalesce)
+        SV_TUNE_KEY(lazy) SV_TUNE_KEY(lazy2) SV_TUNE_KEY(fused) SV_TUNE_KEY(acc_lds)
+        SV_TUNE_KEY(acc_one_wg) SV_TUNE_KEY(reduce_rounds) SV_TUNE_KEY(fuse_batch) SV_TUNE_KEY(fuse_max_k) SV_TUNE_KEY(fuse_reduce) SV_TUNE_KEY(coalesce)
         SV_TUNE_KEY(coalesce_us) SV_TUNE_KEY(lanes) SV_TUNE_KEY(msm_chunk_lg) SV_TUNE_KEY(scalar_chunk_lg) SV_TUNE_KEY(taper) SV_TUNE_KEY(ring_lanes) SV_TUNE_KEY(seg) SV_TUNE_KEY(seg2)
-        SV_TUNE_KEY(fold_l) SV_TUNE_KEY(scan1) SV_TUNE_KEY(ntt_min_tiles) SV_TUNE_KEY(ntt_full_tw) SV_TUNE_KEY(ntt_fold) SV_TUNE_KEY(ntt_signed)
-        SV_TUNE_KEY(ntt_batch) SV_TUNE_KEY(xcd) SV_TUNE_KEY(fold_threads2) SV_TUNE_KEY(coalesce_slots) SV_TUNE_KEY(ramp) SV_TUNE_KEY(scalar_geo) SV_TUNE_KEY(lazy_tail) SV_TUNE_KEY(horner2) SV_TUNE_KEY(pair2) SV_TUNE_KEY(hex2) SV_TUNE_KEY(group_quad) SV_TUNE_KEY(tail_quads) SV_TUNE_KEY(aux_low_prio) SV_TUNE_KEY(fold_small2) SV_TUNE_KEY(fold_mid) SV_TUNE_KEY(aux_cus)
+        SV_TUNE_KEY(fold_l) SV_TUNE_KEY(scan1) SV_TUNE_KEY(ntt_min_tiles) SV_TUNE_KEY(ntt_full_tw) SV_TUNE_KEY(ntt_fold)
+        SV_TUNE_KEY(ntt_batch) SV_TUNE_KEY(xcd) SV_TUNE_KEY(fold_threads2) SV_TUNE_KEY(coalesce_slots) SV_TUNE_KEY(ramp) SV_TUNE_KEY(scalar_geo) SV_TUNE_KEY(lazy_tail) SV_TUNE_KEY(horner2) SV_TUNE_KEY(hex2) SV_TUNE_KEY(group_quad) SV_TUNE_KEY(tail_quads) SV_TUNE_KEY(fold_small2) SV_TUNE_KEY(fold_mid)
 #undef SV_TUNE_KEY
         return false;
     }
@@ -141,8 +131,6 @@ struct tuning_t {
         fix("lanes", lanes, 0, 8);
         fix("ring_lanes", ring_lanes, 2, 8);
         fix("ntt_min_tiles", ntt_min_tiles, 1, 1 << 20);
-        fix("hist", hist, 1, 2);
-        fix("prefetch", prefetch, 0, 2);
         fix("acc_lds", acc_lds, 0, 160 * 1024);
         fix("msm_chunk_lg", msm_chunk_lg, 16, 30);
         fix("scalar_chunk_lg", scalar_chunk_lg, 18, 30);

@@ -233,7 +233,7 @@ def chain_digest(lg):
 def test_tuning_paths_are_bit_identical(lg):
     code = f"import sys; sys.path.insert(0, {ROOT!r}); from tests.test_gpu_ntt_large import chain_digest; print(chain_digest({lg}))"
     want = chain_digest(lg)
-    for tuning in ("ntt_signed=0,ntt_full_tw=0", "ntt_signed=1,ntt_fold=0,ntt_min_tiles=262144"):
+    for tuning in ("ntt_full_tw=0", "ntt_fold=0,ntt_min_tiles=262144"):
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SNARKVM_HIP_TUNING=tuning), capture_output=True, text=True, timeout=600,
                            cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
