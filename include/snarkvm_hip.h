@@ -144,9 +144,32 @@ RustError snarkvm_hip_ntt_device(void *d_inout, uint32_t lg_domain_size, int ntt
 RustError snarkvm_hip_ntt_device_batch(void *const *d_inouts, size_t count, uint32_t lg_domain_size, int ntt_order,
                                        const int *ntt_directions, const int *ntt_types);
 
+/* snarkvm_polymul over operands that live in device memory and stay there: d_out (2^lg_domain_size elements) = the product of `pcount`
+ * coefficient-form polynomials d_polys[k] of plens[k] elements and `ecount` evaluation-form vectors d_evals[k] (natural order over the
+ * domain, elens[k] == 2^lg_domain_size), reduced mod X^n - 1 like the host symbol.  d_polys / d_evals are HOST arrays of device pointers,
+ * read during the call and not retained.  Nothing is staged: the forward transforms read each polynomial where it is (zero beyond its
+ * length), the inverse transform reads the product of the evaluation-form factors, and no pointwise pass runs in between.
+ *  - Output: with at least one operand all 2^lg_domain_size elements of d_out are written - also for a single polynomial (a copy, then a
+ *    zeroed tail; the host symbol leaves that tail to its caller's pre-zeroed buffer, so the two agree whenever that contract is met).
+ *  - pcount + ecount == 0: success, nothing is touched, no device is needed.
+ *  - Operands are never written.  plens[k] may be anything from 0 to 2^lg_domain_size; a zero-length polynomial makes the product zero.
+ *  - d_out may coincide exactly with the START of one operand (v <- v * d in place): every read of that operand is ordered before the
+ *    first write of d_out.  Any other overlap of d_out with an operand is refused with hipErrorInvalidValue before anything is launched.
+ *  - Errors, none of which leaves a partial result: lg_domain_size > 28 -> hipErrorMemoryAllocation (as snarkvm_ntt); plens[k] >
+ *    2^lg_domain_size, elens[k] != 2^lg_domain_size, a null pointer, an operand on another device than d_out -> hipErrorInvalidValue.
+ *  - Inside a snarkvm_hip_scope the call is only enqueued, in order with the other device-resident calls.
+ *  - Workspace (from the calling lane; a repeated call grows nothing, snarkvm_hip_alloc_stats), in vectors of 2^lg_domain_size elements:
+ *    pcount == 0: 1.  Otherwise r + 1 with r = min(pcount, 48, 48 * 2^26 / 2^lg_domain_size) - the coefficient operands are transformed r at
+ *    a time, one kernel launch per pass but the last, which runs per operand so that the results can reuse the slots it frees: 3 vectors
+ *    for two polynomials.  One more vector (an accumulator) when pcount > r, or when more than 4 evaluation-form factors remain
+ *    ((pcount - 1) mod r + 1 transforms of the last chunk, the accumulator, ecount): those are multiplied 4 at a time.
+ *    At lg_domain_size == 0: 1, plus the accumulator beyond 4 operands. */
+RustError snarkvm_hip_polymul_device(void *d_out, size_t pcount, const void *const *d_polys, const size_t *plens, size_t ecount,
+                                     const void *const *d_evals, const size_t *elens, uint32_t lg_domain_size);
+
 /* Deferred synchronisation for device-resident operands.  Between snarkvm_hip_scope_begin (d_any: any device pointer on the GPU
  * to use, or NULL for any GPU) and snarkvm_hip_scope_end, calls of THIS thread whose operands and results live in device memory
- * - snarkvm_hip_ntt_device, _ntt_device_batch, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
+ * - snarkvm_hip_ntt_device, _ntt_device_batch, _polymul_device, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
  * kernels with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
  * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end.  Every other call (MSMs,
  * host buffers, a pointer on another GPU) first waits for the scope's queued work, so results are the same as without a scope - and

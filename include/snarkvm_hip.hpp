@@ -170,6 +170,23 @@ private:
     size_t bytes_ = 0;
 };
 
+// polymul over operands in device memory (snarkvm_hip.h: snarkvm_hip_polymul_device): d_out (2^lg elements, all written) = the product of the
+// coefficient-form operands `polys` ({device pointer, length <= 2^lg}) and the evaluation vectors `evals` (2^lg elements each).  No operand is
+// written; d_out may be the start of one of them.  Inside a Scope the call is only enqueued.
+struct DevicePoly {
+    const void* data;
+    size_t len;
+};
+inline void polymul_device(uint32_t lg, void* d_out, const std::vector<DevicePoly>& polys, const std::vector<const void*>& evals = {}) {
+    std::vector<const void*> pptrs;
+    std::vector<size_t> plens, elens(evals.size(), (size_t)1 << lg);
+    for (auto& p : polys) {
+        pptrs.push_back(p.data);
+        plens.push_back(p.len);
+    }
+    check(snarkvm_hip_polymul_device(d_out, pptrs.size(), pptrs.data(), plens.data(), evals.size(), evals.data(), elens.data(), lg));
+}
+
 // Registered bases (an SRS resident in HBM with precomputed window tables): register once, commit per call.  `tables` x
 // `window_bits` must cover 254 bits (17 x 15 for proof-sized MSMs, 12 x 22 at 2^24).  Concurrent commit() calls of proof size
 // are fused inside the library (runtime.hip.h::msm_coalesced).

@@ -174,6 +174,91 @@ RustError snarkvm_polymul(void* out, size_t pcount, const void* polynomials, con
     API_END
 }
 
+// The same product over operands that live in device memory and stay there (header: snarkvm_hip_polymul_device).  Nothing is staged:
+// the forward transforms read the coefficient operands where they are (bounded load: zero beyond plens[k]), the inverse transform's
+// first pass reads the product of the evaluation-form factors (product load), and the last pass writes d_out.
+//   C (ntt_data, 2^lg) + X (ntt_scratch, r slots of 2^lg): the ring of ntt_forward_bounded for r coefficient operands per chunk;
+//   acc (ntt_acc, 2^lg): the product so far, when the operands come in several chunks or leave more than NTT_PROD_MAX factors.
+RustError snarkvm_hip_polymul_device(void* d_out, size_t pcount, const void* const* d_polys, const size_t* plens, size_t ecount, const void* const* d_evals,
+                                     const size_t* elens, uint32_t lg) {
+    if (pcount + ecount == 0) return ok();
+    API_BEGIN_DEV(device_for(d_out, 1))
+    check_ntt_args(lg, 0, 0, 0);
+    if (!d_out || (pcount && (!d_polys || !plens)) || (ecount && (!d_evals || !elens))) throw hip_failure{hipErrorInvalidValue, "polymul_device: null argument", __LINE__};
+    const size_t n = (size_t)1 << lg;
+    const size_t bytes = sizeof(fr_mem_t) * n;
+    bool zero = false;
+    for (size_t k = 0; k < pcount + ecount; k++) {
+        const bool poly = k < pcount;
+        const void* ptr = poly ? d_polys[k] : d_evals[k - pcount];
+        const size_t len = poly ? plens[k] : elens[k - pcount];
+        if (!ptr) throw hip_failure{hipErrorInvalidValue, "polymul_device: null operand", __LINE__};
+        if (poly && len > n) throw hip_failure{hipErrorInvalidValue, "polymul_device: polynomial longer than the domain", __LINE__};
+        if (!poly && len != n) throw hip_failure{hipErrorInvalidValue, "polymul_device: evaluation vector length != domain size", __LINE__};
+        if (g_rt.devs[device_for(ptr, 1)]->physical != c.dev->physical)
+            throw hip_failure{hipErrorInvalidValue, "polymul_device: an operand lives on another device than d_out", __LINE__};
+        // d_out may BE an operand (same start): every read of it is queued before the first write of d_out.  Any other overlap is refused.
+        const uint8_t *o = (const uint8_t*)d_out, *q = (const uint8_t*)ptr;
+        if (q != o && len && q < o + bytes && o < q + sizeof(fr_mem_t) * len) throw hip_failure{hipErrorInvalidValue, "polymul_device: d_out overlaps an operand", __LINE__};
+        zero = zero || len == 0;
+    }
+    hipStream_t st = c.stream;
+    fr_mem_t* out = (fr_mem_t*)d_out;
+    c.phase_begin("polymul_kernels");
+    if (zero) {  // a zero polynomial among the factors
+        HIP_TRY(hipMemsetAsync(out, 0, bytes, st));
+    } else if (pcount == 1 && ecount == 0) {  // a copy (snarkvm.cu:196-202), and the tail the host symbol leaves to its caller
+        if (d_polys[0] != d_out) HIP_TRY(hipMemcpyAsync(out, d_polys[0], sizeof(fr_mem_t) * plens[0], hipMemcpyDeviceToDevice, st));
+        if (plens[0] < n) HIP_TRY(hipMemsetAsync(out + plens[0], 0, sizeof(fr_mem_t) * (n - plens[0]), st));
+    } else {
+        // coefficient operands per chunk: one batched launch per pass, within the scratch bound of snarkvm_hip_ntt_device_batch
+        const size_t r_max = lg <= (uint32_t)NTT_TW_LG ? (size_t)NTT_BATCH_MAX : ((size_t)NTT_BATCH_MAX << NTT_TW_LG) >> lg;
+        const size_t np = lg ? pcount : 0;  // a size-1 transform is the identity: the operands are their own evaluations
+        const size_t r = np < r_max ? np : r_max;
+        const size_t last_chunk = np ? (np - 1) % r_max + 1 : 0;
+        const bool chunked = np > r_max;
+        const bool need_acc = chunked || (chunked ? 1 : 0) + last_chunk + (pcount - np) + ecount > (size_t)NTT_PROD_MAX;
+        if (np) c.ntt_data.ensure(bytes);
+        c.ntt_scratch.ensure(bytes * (r ? r : 1));
+        if (need_acc) c.ntt_acc.ensure(bytes);
+        fr_mem_t *ring0 = c.ntt_data.as<fr_mem_t>(), *scratch = c.ntt_scratch.as<fr_mem_t>(), *acc = c.ntt_acc.as<fr_mem_t>();
+        const ntt_ctx_t cx = c.ntt_ctx();
+        const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+        std::vector<const fr_mem_t*> fac;  // evaluation-form factors still to be multiplied
+        // groups of NTT_PROD_MAX factors -> acc, which takes their place, until at most `keep` factors are left
+        auto fold = [&](size_t keep) {
+            while (fac.size() > keep) {
+                const size_t m = fac.size() < (size_t)NTT_PROD_MAX ? fac.size() : (size_t)NTT_PROD_MAX;
+                hipLaunchKernelGGL(fr_product_kernel, dim3(blocks), dim3(256), 0, st, acc, ntt_product_args(fac.data(), (int)m), n);
+                fac.erase(fac.begin(), fac.begin() + m);
+                fac.insert(fac.begin(), acc);
+            }
+        };
+        fr_mem_t* work = scratch;  // a vector no factor lives in: the slot the last forward transform has left behind
+        for (size_t k0 = 0; k0 < np; k0 += r_max) {
+            const size_t nv = np - k0 < r_max ? np - k0 : r_max;
+            fr_mem_t* dst[NTT_BATCH_MAX];
+            for (size_t y = 0; y < nv; y++) dst[y] = y ? scratch + ((y - 1) << lg) : ring0;
+            ntt_forward_bounded(cx, (const fr_mem_t* const*)d_polys + k0, plens + k0, dst, (unsigned)nv, scratch, (int)lg);
+            fac.insert(fac.end(), dst, dst + nv);
+            work = scratch + ((nv - 1) << lg);
+            if (k0 + nv < np) fold(1);  // the ring is about to be reused (a chunk that is not the last one holds r_max >= 12 transforms)
+        }
+        for (size_t k = np; k < pcount; k++) fac.push_back((const fr_mem_t*)d_polys[k]);
+        for (size_t k = 0; k < ecount; k++) fac.push_back((const fr_mem_t*)d_evals[k]);
+        fold((size_t)NTT_PROD_MAX);
+        const ntt_product_t pa = ntt_product_args(fac.data(), (int)fac.size());
+        if (lg == 0)
+            hipLaunchKernelGGL(fr_product_kernel, dim3(1), dim3(64), 0, st, out, pa, n);
+        else
+            ntt_inverse_product(cx, pa, work, out, (int)lg);
+    }
+    c.phase_end();
+    HIP_TRY(hipGetLastError());
+    c.sync_or_defer();
+    API_END
+}
+
 // ---- Fr vector helpers ---------------------------------------------------------------------------
 RustError snarkvm_hip_fr_mul_device(void* d_out, const void* d_a, const void* d_b, size_t n) {
     API_BEGIN_DEV(device_for(d_out, n ? 1 : 0))

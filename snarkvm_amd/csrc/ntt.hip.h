@@ -321,9 +321,65 @@ struct ntt_batch_t {
     int in_scratch, out_scratch;
 };
 struct ntt_no_batch_t {};
-template <bool BATCH, class A>
-__global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tables_t tb, typename std::conditional<BATCH, ntt_batch_t, ntt_no_batch_t>::type bt) {
+
+// Load policies: what the first stage group of a pass - the only place that touches global input - reads at global index g.
+//   ntt_load_plain    in[g]: every transform of the NTT entry points.
+//   ntt_load_bounded  in[g] for g < len, zero beyond: the forward transform of a coefficient-form operand of len <= 2^lg elements, read
+//                     where the caller keeps it (never written, never read past len).  Batched form only: src[y] / len[y] per operand,
+//                     the pass writes to scratch slot y or to v[y] like any batched pass.
+//   ntt_load_product  v[0][g] * ... * v[m - 1][g] over m <= NTT_PROD_MAX full-length vectors in memory form: the inverse transform of a
+//                     pointwise product without the pass that would materialise it.  A Montgomery product of two memory words is short of
+//                     the memory form by 2^5 (fr_pointwise_mul_kernel); `fix` = 2^(5 (m - 1)) in internal form restores it with ONE
+//                     product for the whole chain.  Every product is canonical, so A::from_canonical sees what a plain load gives it.
+static constexpr int NTT_PROD_MAX = 4;
+struct ntt_bounded_t : ntt_batch_t {
+    const fr_mem_t* src[NTT_BATCH_MAX];
+    size_t len[NTT_BATCH_MAX];
+};
+struct ntt_product_t {
+    const fr_mem_t* v[NTT_PROD_MAX];
+    int m;
+    fr_mem_t fix;  // used when m >= 2
+};
+struct ntt_load_plain {
+    template <bool BATCH>
+    using args = typename std::conditional<BATCH, ntt_batch_t, ntt_no_batch_t>::type;
+};
+struct ntt_load_bounded {
+    template <bool BATCH>
+    using args = ntt_bounded_t;
+};
+struct ntt_load_product {
+    template <bool BATCH>
+    using args = ntt_product_t;
+};
+// 2^(5 (m - 1)) in internal form: MEM2INT = 2^266, and mont261(2^(261 + 5 i), 2^266) = 2^(261 + 5 (i + 1))
+SV_HD ntt_product_t ntt_product_args(const fr_mem_t* const* v, int m) {
+    ntt_product_t pa{};
+    for (int j = 0; j < NTT_PROD_MAX; j++) pa.v[j] = j < m ? v[j] : nullptr;
+    pa.m = m;
+    fr_t fix = fr_t::from_table(FrP::MEM2INT);
+    for (int j = 2; j < m; j++) fix = fix * fr_t::from_table(FrP::MEM2INT);
+    fix.store(&pa.fix);
+    return pa;
+}
+__device__ __forceinline__ fr_t ntt_product_at(const ntt_product_t& pa, size_t g) {
+    fr_t x = load_fr_global(&pa.v[0][g]);
+    if (pa.m > 1) {
+#pragma unroll
+        for (int j = 1; j < NTT_PROD_MAX; j++)
+            if (j < pa.m) x = x * load_fr_global(&pa.v[j][g]);
+        x = x * fr_t::load(&pa.fix);
+    }
+    return x;
+}
+
+template <bool BATCH, class A, class LD = ntt_load_plain>
+__global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tables_t tb, typename LD::template args<BATCH> bt) {
     typedef typename A::elem elem;
+    constexpr bool BOUNDED = std::is_same<LD, ntt_load_bounded>::value, PRODUCT = std::is_same<LD, ntt_load_product>::value;
+    static_assert(!BOUNDED || BATCH, "the bounded load takes its operands from the batch arguments");
+    static_assert(!PRODUCT || !BATCH, "the product load is a single transform");
     extern __shared__ uint32_t lds32[];
     if constexpr (BATCH) {
         fr_mem_t* vec = bt.v[blockIdx.y];
@@ -331,6 +387,12 @@ __global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tabl
         p.in = bt.in_scratch ? scr : vec;
         p.out = bt.out_scratch ? scr : vec;
     }
+    size_t in_len = 0;
+    if constexpr (BOUNDED) {
+        p.in = bt.src[blockIdx.y];
+        in_len = bt.len[blockIdx.y];
+    }
+    (void)in_len;
     const int R = 1 << p.a, T = 1 << p.lgT, E = R << p.lgT;
     ntt_lds_t L;
     L.data = lds32;
@@ -393,7 +455,13 @@ __global__ void __launch_bounds__(512) ntt_pass_kernel_v2(ntt_pass_t p, ntt_tabl
                 const int row = row0 + m * row_step;
                 if (first) {
                     const size_t g = in_base + row * in_rho_stride + col * in_col_stride;
-                    fr_t xin = load_fr_global(&p.in[g]);
+                    fr_t xin;
+                    if constexpr (BOUNDED)
+                        xin = g < in_len ? load_fr_global(&p.in[g]) : fr_t::zero();
+                    else if constexpr (PRODUCT)
+                        xin = ntt_product_at(bt, g);
+                    else
+                        xin = load_fr_global(&p.in[g]);
                     if (p.coset_pre) xin = xin * ntt_coset_pow(tb, 0, (uint32_t)g);
                     x[m] = A::from_canonical(xin);
                 } else {
@@ -468,6 +536,13 @@ static __global__ void fr_pointwise_mul_kernel(fr_mem_t* out, const fr_mem_t* a,
         if (fix_now) x = x.from_mem_mont();  // * 2^266 * 2^-261 = * 2^5
         x.store(&out[i]);
     }
+}
+// out[i] = v[0][i] * ... * v[m - 1][i] in memory form, the product load of the pass kernel as a pass of its own: folds a group of factors
+// into an accumulator when a product has more factors than one load takes.  `out` may be one of the factors.
+static __global__ void fr_product_kernel(fr_mem_t* out, ntt_product_t pa, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < n; i += st) store_fr_global(&out[i], ntt_product_at(pa, i));
 }
 // Fr::to_bigint (fp_256.rs:380-413) / from_bigint (fp_256.rs:362-377) over a vector: kzg10 convert_to_bigints
 static __global__ void fr_to_bigint_kernel(fr_mem_t* out, const fr_mem_t* in, size_t n, int to_bigint) {
@@ -658,19 +733,58 @@ static inline const fr_mem_t* ntt_get_full_tw(const ntt_ctx_t& cx, int a, int s,
     return slot.p;
 }
 
-static inline void ntt_launch_pass(hipStream_t st, const ntt_pass_t& p, const ntt_tables_t& tb, const ntt_batch_t* bt = nullptr, unsigned nvec = 1) {
+struct ntt_launch_dims_t {
+    unsigned ntiles;
+    int threads;
+    size_t shmem;
+};
+static inline ntt_launch_dims_t ntt_launch_dims(const ntt_pass_t& p) {
     const size_t E = (size_t)1 << (p.a + p.lgT);
-    const size_t ntiles = ((size_t)1 << p.lg_n) / E;
-    {
-        int threads = (int)(E / 4);  // one radix-4 group per thread
-        if (threads < 64) threads = 64;
-        if (threads > 512) threads = 512;
-        const size_t shmem = (9 * E + 9 * ((size_t)1 << (p.a ? p.a - 1 : 0))) * sizeof(uint32_t);  // a [2^8 x 8] tile + its twiddles: 78 KB, two workgroups per CU
-        if (bt)
-            hipLaunchKernelGGL((ntt_pass_kernel_v2<true, ntt_arith_u>), dim3((unsigned)ntiles, nvec), dim3(threads), shmem, st, p, tb, *bt);
-        else
-            hipLaunchKernelGGL((ntt_pass_kernel_v2<false, ntt_arith_u>), dim3((unsigned)ntiles), dim3(threads), shmem, st, p, tb, ntt_no_batch_t{});
+    ntt_launch_dims_t d;
+    d.ntiles = (unsigned)(((size_t)1 << p.lg_n) / E);
+    d.threads = (int)(E / 4);  // one radix-4 group per thread
+    if (d.threads < 64) d.threads = 64;
+    if (d.threads > 512) d.threads = 512;
+    d.shmem = (9 * E + 9 * ((size_t)1 << (p.a ? p.a - 1 : 0))) * sizeof(uint32_t);  // a [2^8 x 8] tile + its twiddles: 78 KB, two workgroups per CU
+    return d;
+}
+static inline void ntt_launch_pass(hipStream_t st, const ntt_pass_t& p, const ntt_tables_t& tb, const ntt_batch_t* bt = nullptr, unsigned nvec = 1) {
+    const ntt_launch_dims_t d = ntt_launch_dims(p);
+    if (bt)
+        hipLaunchKernelGGL((ntt_pass_kernel_v2<true, ntt_arith_u>), dim3(d.ntiles, nvec), dim3(d.threads), d.shmem, st, p, tb, *bt);
+    else
+        hipLaunchKernelGGL((ntt_pass_kernel_v2<false, ntt_arith_u>), dim3(d.ntiles), dim3(d.threads), d.shmem, st, p, tb, ntt_no_batch_t{});
+}
+// the first pass of nvec forward transforms of coefficient operands (bounded load); the first pass of an inverse transform of a product
+static inline void ntt_launch_pass_bounded(hipStream_t st, const ntt_pass_t& p, const ntt_tables_t& tb, const ntt_bounded_t& bt, unsigned nvec) {
+    const ntt_launch_dims_t d = ntt_launch_dims(p);
+    hipLaunchKernelGGL((ntt_pass_kernel_v2<true, ntt_arith_u, ntt_load_bounded>), dim3(d.ntiles, nvec), dim3(d.threads), d.shmem, st, p, tb, bt);
+}
+static inline void ntt_launch_pass_product(hipStream_t st, const ntt_pass_t& p, const ntt_tables_t& tb, const ntt_product_t& pa) {
+    const ntt_launch_dims_t d = ntt_launch_dims(p);
+    hipLaunchKernelGGL((ntt_pass_kernel_v2<false, ntt_arith_u, ntt_load_product>), dim3(d.ntiles), dim3(d.threads), d.shmem, st, p, tb, pa);
+}
+
+// pass k of plan `pl` as the drivers launch it: geometry, direction / type fields, tile width for `nvec` vectors per launch, and the
+// closing-twiddle table.  `folded` carries "the pass before the last one folded 2^261 [/ n] into its table" from pass to pass.
+static inline ntt_pass_t ntt_pass_setup(const ntt_ctx_t& cx, const ntt_plan_t& pl, int lg, int k, int dir, int type, unsigned nvec, bool& folded) {
+    ntt_pass_t p = ntt_pass_geometry(pl, lg, k);
+    p.dir = dir;
+    p.coset_pre = (k == 0 && dir == NTT_FORWARD && type == NTT_COSET) ? 1 : 0;
+    p.scale_post = (p.last && dir == NTT_INVERSE) ? (type == NTT_COSET ? 2 : 1) : 0;
+    p.tw_full = nullptr;
+    p.reduce_only = 0;
+    if (!p.last) {
+        p.lgT = ntt_tile_lg(p.a, p.s, lg, nvec);
+        const bool prelast = (k == pl.npass - 2);
+        bool f = false;
+        p.tw_full = ntt_get_full_tw(cx, p.a, p.s, p.tw_shift, dir, prelast ? lg : 0, &f);
+        folded = f;
+    } else {
+        p.reduce_only = folded ? 1 : 0;
+        p.lgT = ntt_tile_lg(p.a, p.a1, lg, nvec);
     }
+    return p;
 }
 
 // NN-order transform of 2^lg elements held in `data`; `scratch` is a second buffer of the same size.
@@ -691,26 +805,9 @@ static inline void ntt_run_nn(const ntt_ctx_t& cx, fr_mem_t* data, fr_mem_t* scr
         for (unsigned i = 0; i < nvec; i++) bt.v[i] = vecs[i];
         bt.scratch = scratch;
     }
-    const int scale_post = (dir == NTT_INVERSE) ? (type == NTT_COSET ? 2 : 1) : 0;
-    const int coset_pre = (dir == NTT_FORWARD && type == NTT_COSET) ? 1 : 0;
     bool folded = false;  // the pass before the last one used a table with 2^261 [/ n] folded in
     for (int k = 0; k < pl.npass; k++) {
-        ntt_pass_t p = ntt_pass_geometry(pl, lg, k);
-        p.dir = dir;
-        p.coset_pre = (k == 0) ? coset_pre : 0;
-        p.scale_post = p.last ? scale_post : 0;
-        p.tw_full = nullptr;
-        p.reduce_only = 0;
-        if (!p.last) {
-            p.lgT = ntt_tile_lg(p.a, p.s, lg, nvec);
-            const bool prelast = (k == pl.npass - 2);
-            bool f = false;
-            p.tw_full = ntt_get_full_tw(cx, p.a, p.s, p.tw_shift, dir, prelast ? lg : 0, &f);
-            folded = f;
-        } else {
-            p.reduce_only = folded ? 1 : 0;
-            p.lgT = ntt_tile_lg(p.a, p.a1, lg, nvec);
-        }
+        ntt_pass_t p = ntt_pass_setup(cx, pl, lg, k, dir, type, nvec, folded);
         if (pl.npass == 1) {
             p.in = data;
             p.out = scratch;
@@ -734,6 +831,63 @@ static inline void ntt_run_nn(const ntt_ctx_t& cx, fr_mem_t* data, fr_mem_t* scr
     }
     if (pl.npass == 1)
         (void)hipMemcpyAsync(data, scratch, sizeof(fr_mem_t) << lg, hipMemcpyDeviceToDevice, st);
+}
+
+// ---- the transforms of a device-resident product (snarkvm_hip_polymul_device), 1 <= lg ------------------------------------------
+// Forward NN transforms of nvec (<= NTT_BATCH_MAX) coefficient-form operands src[y] of len[y] <= 2^lg elements, read in place and never
+// written, into dst[y].  `scratch` holds nvec * 2^lg elements.  The first pass (bounded load) and the middle passes are one launch
+// for all operands; the last pass is out of place and runs per operand, in list order, so dst[y] may be scratch slot y' < y: the
+// slot has been consumed by then.  That ring keeps the workspace of nvec transforms at nvec + 1 vectors.
+static inline void ntt_forward_bounded(const ntt_ctx_t& cx, const fr_mem_t* const* src, const size_t* len, fr_mem_t* const* dst, unsigned nvec,
+                                       fr_mem_t* scratch, int lg) {
+    const ntt_tables_t& tb = *cx.tb;
+    const ntt_plan_t pl = ntt_make_plan(lg);
+    ntt_bounded_t bt{};
+    bt.scratch = scratch;
+    for (unsigned y = 0; y < nvec; y++) bt.src[y] = src[y], bt.len[y] = len[y];
+    bool folded = false;
+    for (int k = 0; k < pl.npass; k++) {
+        const bool per_vector = (k == pl.npass - 1);
+        ntt_pass_t p = ntt_pass_setup(cx, pl, lg, k, NTT_FORWARD, NTT_STANDARD, per_vector ? 1 : nvec, folded);
+        if (pl.npass == 1) {  // operand -> destination, one launch each (the two are never the same memory)
+            for (unsigned y = 0; y < nvec; y++) {
+                ntt_bounded_t one{};
+                one.v[0] = dst[y];
+                one.src[0] = src[y];
+                one.len[0] = len[y];
+                ntt_launch_pass_bounded(cx.st, p, tb, one, 1);
+            }
+        } else if (k == 0) {
+            bt.in_scratch = 0, bt.out_scratch = 1;
+            ntt_launch_pass_bounded(cx.st, p, tb, bt, nvec);
+        } else if (!p.last) {
+            bt.in_scratch = 1, bt.out_scratch = 1;
+            ntt_launch_pass(cx.st, p, tb, &bt, nvec);
+        } else {
+            for (unsigned y = 0; y < nvec; y++) {
+                p.in = scratch + ((size_t)y << lg);
+                p.out = dst[y];
+                ntt_launch_pass(cx.st, p, tb);
+            }
+        }
+    }
+}
+// out = the inverse NN transform of the pointwise product of pa.m evaluation vectors, none of which is written.  `work` holds 2^lg
+// elements and is none of the factors; `out` may be one of them: every pass but the last reads the factors or `work` and writes
+// `work`, and a single-pass transform goes through `work` as well.
+static inline void ntt_inverse_product(const ntt_ctx_t& cx, const ntt_product_t& pa, fr_mem_t* work, fr_mem_t* out, int lg) {
+    const ntt_plan_t pl = ntt_make_plan(lg);
+    bool folded = false;
+    for (int k = 0; k < pl.npass; k++) {
+        ntt_pass_t p = ntt_pass_setup(cx, pl, lg, k, NTT_INVERSE, NTT_STANDARD, 1, folded);
+        p.in = work;
+        p.out = (p.last && pl.npass > 1) ? out : work;
+        if (k == 0)
+            ntt_launch_pass_product(cx.st, p, *cx.tb, pa);
+        else
+            ntt_launch_pass(cx.st, p, *cx.tb);
+    }
+    if (pl.npass == 1) (void)hipMemcpyAsync(out, work, sizeof(fr_mem_t) << lg, hipMemcpyDeviceToDevice, cx.st);
 }
 
 // Full FFI semantics (any order): bit-reversed inputs/outputs are handled with an explicit permutation pass.

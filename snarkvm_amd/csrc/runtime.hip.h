@@ -438,6 +438,8 @@ static void tu_kernel_attributes(int logical) {
 #ifdef SV_TU_NTT  // the unit that launches the NTT passes (api_fr.hip)
     HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<false, ntt_arith_u>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
     HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<true, ntt_arith_u>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<true, ntt_arith_u, ntt_load_bounded>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<false, ntt_arith_u, ntt_load_product>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
 #endif
     done[logical] = 1;
 }

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -58,6 +58,20 @@ def polymul(domain, polynomials, evaluations, zero=None):
                                      ctypes.c_uint32(lg))
     _lib.check(err)
     return out
+
+
+def polymul_device(lg, out_ptr, polys=(), evals=()):
+    """Extension (no reference counterpart): `polymul` over operands that live in device memory and stay there
+    (`snarkvm_hip_polymul_device`).  out_ptr: device vector of 2^lg elements, all of it written; polys: (device pointer, length) pairs
+    of coefficient-form operands, length <= 2^lg; evals: device pointers of evaluation vectors of 2^lg elements.  No operand is written;
+    out_ptr may be the start of one of them.  Inside a scope the call is only enqueued."""
+    polys = [(int(p), int(n)) for p, n in polys]
+    evals = [int(e) for e in evals]
+    pp = (ctypes.c_void_p * max(1, len(polys)))(*[p for p, _ in polys])
+    pl = (ctypes.c_size_t * max(1, len(polys)))(*[n for _, n in polys])
+    ep = (ctypes.c_void_p * max(1, len(evals)))(*evals)
+    el = (ctypes.c_size_t * max(1, len(evals)))(*([1 << lg] * len(evals)))
+    _lib.check(_lib.lib().snarkvm_hip_polymul_device(ctypes.c_void_p(int(out_ptr)), len(polys), pp, pl, len(evals), ep, el, lg))
 
 
 def msm(points, scalars):
