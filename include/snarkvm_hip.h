@@ -170,7 +170,7 @@ RustError snarkvm_hip_polymul_device(void *d_out, size_t pcount, const void *con
 /* Deferred synchronisation for device-resident operands.  Between snarkvm_hip_scope_begin (d_any: any device pointer on the GPU
  * to use, or NULL for any GPU) and snarkvm_hip_scope_end, calls of THIS thread whose operands and results live in device memory
  * - snarkvm_hip_ntt_device, _ntt_device_batch, _polymul_device, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
- * kernels with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
+ * kernels (snarkvm_hip_fr_lincomb among them) with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
  * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end.  Every other call (MSMs,
  * host buffers, a pointer on another GPU) first waits for the scope's queued work, so results are the same as without a scope - and
  * then runs on the scope's own stream: a thread inside a scope never waits for a free stream.  Scopes do not nest; a scope must be
@@ -361,6 +361,26 @@ RustError snarkvm_hip_fr_divide_by_vanishing(void *quotient, void *remainder, co
 /* DensePolynomial::mul_by_vanishing_poly (dense.rs:153-159): out (len + domain_size coefficients) = p * (X^D - 1). */
 RustError snarkvm_hip_fr_mul_by_vanishing(void *out, const void *poly, size_t len, size_t domain_size, int on_device);
 
+/* Linear combination of polynomials in one pass: out[i] = sum_k coeffs[k] * polys[k][i] for i < n_out, polys[k][i] counting as zero from
+ * lens[k] on - every linear combination SonicKZG10::open_combinations materialises (`poly += (coeff, cur_poly)` per term,
+ * polycommit/sonic_pc/mod.rs:413-473) and the fold of batch_open (combine_polynomials, mod.rs:548-564).  Followed by
+ * snarkvm_hip_fr_divide_by_linear over `out` the remainder is the combination's evaluation (get_lc_eval, snark/varuna/varuna.rs:584-590).
+ * `polys`, `lens` and `coeffs` (count x 32 bytes, Montgomery form) are HOST arrays, read during the call and not retained; on_device
+ * governs `out` and every polys[k].  A pointer may be NULL iff its length is 0.  The device reads K + 1 vectors where a chain of
+ * fr_vec_op calls moves 3K - 1; operands travel 24 per kernel launch (FR_LINCOMB_CHUNK), a longer list takes `out` back in as a term.
+ *  - Output: all n_out elements are written, zeros past the longest operand; count == 0 zero-fills.
+ *  - n_out == 0: success, nothing is touched, no device is needed.
+ *  - `out` may coincide exactly with the START of one operand (p <- p + sum ...): that operand is read before `out` is written.  Any other
+ *    overlap of `out` with an operand is refused with hipErrorInvalidValue before anything is launched (so is `out` listed as an operand
+ *    more than 24 times).  Operands may overlap each other and repeat; they are never written.
+ *  - Errors, none of which leaves a partial result: lens[k] > n_out, a missing pointer, an operand on another device than `out`
+ *    -> hipErrorInvalidValue.
+ *  - With on_device = 1 inside a snarkvm_hip_scope the call is only enqueued.
+ *  - With on_device = 0 the operands are staged into one lane buffer (n_out + sum lens[k] elements): one upload each, one download.
+ *  - Workspace: none with on_device = 1; a repeated call grows nothing (snarkvm_hip_alloc_stats). */
+RustError snarkvm_hip_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs,
+                                 int on_device);
+
 /* Strided batches of the passes above on device memory - the same pass over one vector of every proof of a batch proved in lock
  * step (VarunaSNARK::prove_batch, snark/varuna/varuna.rs:336): member y of the batch uses every vector pointer advanced by
  * y * stride elements (stride >= the vector length); ONE kernel launch sequence for the whole batch.  fr_vec_op_strided: `scalar`
@@ -453,6 +473,10 @@ int snarkvm_hip_selftest_ntt_index(uint32_t lg, const int32_t *plan, int npass);
 /* The whole NN transform of 2^lg <= 2^16 elements (memory form, in place) computed on the host pass by pass in exact arithmetic over the
  * kernels' addressing, twiddles, coset powers and output map (plan = NULL: the backend's plan; else npass forced radices).  0, or -1. */
 int snarkvm_hip_selftest_ntt_host(void *inout, uint32_t lg, const int32_t *plan, int npass, int dir, int type);
+/* snarkvm_hip_fr_lincomb over host memory with the CPU in the kernel's place: the same validation, operand order and split into launches,
+ * every launch a loop over i through the kernel's own per-element routine (csrc/poly.hip.h: fr_lincomb_at, Fp::sum_of_products).  0, or -1
+ * when the arguments are refused. */
+int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 

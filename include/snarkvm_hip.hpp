@@ -187,6 +187,20 @@ inline void polymul_device(uint32_t lg, void* d_out, const std::vector<DevicePol
     check(snarkvm_hip_polymul_device(d_out, pptrs.size(), pptrs.data(), plens.data(), evals.size(), evals.data(), elens.data(), lg));
 }
 
+// Linear combination of polynomials in one device pass (snarkvm_hip.h: snarkvm_hip_fr_lincomb): out[i] = sum_k coeffs[k] * polys[k][i] for
+// i < n_out, polys[k] counting as zero from its length (<= n_out) on.  coeffs: polys.size() x 32 bytes of HOST memory, Montgomery form;
+// on_device governs `out` and every polys[k].data.  No operand is written; out may be the start of one of them.  With on_device inside a
+// Scope the call is only enqueued; a divide_by_linear over `out` then yields the opening quotient and the combination's evaluation.
+inline void fr_lincomb(void* out, size_t n_out, const std::vector<DevicePoly>& polys, const void* coeffs, bool on_device) {
+    std::vector<const void*> pptrs;
+    std::vector<size_t> plens;
+    for (auto& p : polys) {
+        pptrs.push_back(p.data);
+        plens.push_back(p.len);
+    }
+    check(snarkvm_hip_fr_lincomb(out, n_out, pptrs.size(), pptrs.data(), plens.data(), coeffs, on_device ? 1 : 0));
+}
+
 // Registered bases (an SRS resident in HBM with precomputed window tables): register once, commit per call.  `tables` x
 // `window_bits` must cover 254 bits (17 x 15 for proof-sized MSMs, 12 x 22 at 2^24).  Concurrent commit() calls of proof size
 // are fused inside the library (runtime.hip.h::msm_coalesced).

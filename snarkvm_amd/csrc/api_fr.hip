@@ -4,6 +4,8 @@
 #define SV_TU_NTT
 #include "runtime.hip.h"
 
+#include <algorithm>
+
 extern "C" {
 
 // ---- NTT -------------------------------------------------------------------------------------
@@ -575,6 +577,109 @@ RustError snarkvm_hip_fr_mul_by_vanishing(void* out, const void* poly, size_t le
         fr_call_done(c, on_device);
     }
     API_END
+}
+
+// ---- linear combination of polynomials (poly.hip.h: fr_lincomb_kernel) --------------------------------------------------
+// What the device call and its host replay share: validation, operand order and the split into launches.  src[k]: the caller's index of
+// table entry k, -1 for `out` taken back in as a term with coefficient one (every launch after the first).
+struct fr_lincomb_launch_t {
+    fr_lincomb_t t;
+    int64_t src[FR_LINCOMB_CHUNK];
+};
+// nullptr, or why the call is refused (hipErrorInvalidValue).  Nothing has been touched either way.
+static const char* fr_lincomb_plan(const void* out, size_t n_out, size_t count, const void* const* polys, const size_t* lens, const void* coeffs,
+                                   std::vector<fr_lincomb_launch_t>& plan) {
+    if (!out || (count && (!polys || !lens || !coeffs))) return "missing argument";
+    struct entry_t {
+        size_t k, len;
+        bool aliased;
+    };
+    std::vector<entry_t> live;
+    size_t aliased = 0;
+    const uint8_t* o = (const uint8_t*)out;
+    for (size_t k = 0; k < count; k++) {
+        const size_t len = lens[k];
+        if (len > n_out) return "an operand is longer than n_out";
+        if (!len) continue;
+        const uint8_t* q = (const uint8_t*)polys[k];
+        if (!q) return "null operand of non-zero length";
+        // out may BE an operand (same start): a thread reads index i of every operand before it writes out[i].  Any other overlap is refused.
+        if (q != o && q < o + sizeof(fr_mem_t) * n_out && o < q + sizeof(fr_mem_t) * len) return "out overlaps an operand";
+        live.push_back({k, len, q == o});
+        aliased += q == o;
+    }
+    const auto longer = [](const entry_t& a, const entry_t& b) { return a.len > b.len; };
+    std::stable_sort(live.begin(), live.end(), longer);
+    if (aliased && live.size() > (size_t)FR_LINCOMB_CHUNK) {
+        // the first launch overwrites out: every operand that IS out goes into it, beside the longest of the others
+        if (aliased > (size_t)FR_LINCOMB_CHUNK) return "out is an operand more often than one launch holds operands";
+        std::stable_partition(live.begin(), live.end(), [](const entry_t& e) { return e.aliased; });
+        std::stable_sort(live.begin(), live.begin() + FR_LINCOMB_CHUNK, longer);
+    }
+    size_t at = 0;
+    do {
+        fr_lincomb_launch_t L{};
+        int m = 0;
+        if (at) {  // the sum so far
+            L.t.p[0] = (const fr_mem_t*)out, L.t.len[0] = n_out, L.src[0] = -1;
+            for (int l = 0; l < 9; l++) L.t.c[0][l] = FrP::ONE[l];
+            m = 1;
+        }
+        for (; m < FR_LINCOMB_CHUNK && at < live.size(); m++, at++) {
+            const entry_t& e = live[at];
+            const fr_mem_t c_mem = fr_mem_from_host((const uint8_t*)coeffs + sizeof(fr_mem_t) * e.k);
+            const fr_t c = fr_t::load(&c_mem).from_mem_mont();
+            L.t.p[m] = (const fr_mem_t*)polys[e.k], L.t.len[m] = e.len, L.src[m] = (int64_t)e.k;
+            for (int l = 0; l < 9; l++) L.t.c[m][l] = c.v[l];
+        }
+        L.t.count = m;
+        plan.push_back(L);
+    } while (at < live.size());
+    return nullptr;
+}
+RustError snarkvm_hip_fr_lincomb(void* out, size_t n_out, size_t count, const void* const* polys, const size_t* lens, const void* coeffs, int on_device) {
+    if (n_out == 0) return ok();
+    std::vector<fr_lincomb_launch_t> plan;
+    if (const char* why = fr_lincomb_plan(out, n_out, count, polys, lens, coeffs, plan)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_lincomb: ") + why);
+    API_BEGIN_DEV(device_for(out, on_device ? 1 : 0))
+    fr_mem_t* dout = (fr_mem_t*)out;
+    if (on_device) {
+        for (size_t k = 0; k < count; k++)
+            if (lens[k] && g_rt.devs[device_for(polys[k], 1)]->physical != c.dev->physical)
+                throw hip_failure{hipErrorInvalidValue, "fr_lincomb: an operand lives on another device than out", __LINE__};
+    } else {
+        // host operands: one lane buffer holds out and, behind it, every operand; one upload each, one download
+        size_t total = n_out;
+        for (size_t k = 0; k < count; k++) total += lens[k];
+        c.poly[0].ensure(sizeof(fr_mem_t) * total);
+        dout = c.poly[0].as<fr_mem_t>();
+        std::vector<const fr_mem_t*> staged(count, nullptr);
+        fr_mem_t* next = dout + n_out;
+        for (size_t k = 0; k < count; k++) {
+            if (!lens[k]) continue;
+            HIP_TRY(hipMemcpyAsync(next, polys[k], sizeof(fr_mem_t) * lens[k], hipMemcpyHostToDevice, c.stream));
+            staged[k] = next;
+            next += lens[k];
+        }
+        for (fr_lincomb_launch_t& L : plan)
+            for (int m = 0; m < L.t.count; m++) L.t.p[m] = L.src[m] < 0 ? dout : staged[(size_t)L.src[m]];
+    }
+    for (const fr_lincomb_launch_t& L : plan) hipLaunchKernelGGL(fr_lincomb_kernel, dim3(fr_grid(n_out)), dim3(256), 0, c.stream, dout, n_out, L.t);
+    HIP_TRY(hipGetLastError());
+    fr_finish_out(c, dout, out, n_out, on_device);
+    fr_call_done(c, on_device);
+    API_END
+}
+// The same call on host memory with the CPU in the kernel's place: the same plan, every launch a loop over i through the kernel's own
+// per-element routine.  0, or -1 when the plan refuses the arguments.
+int snarkvm_hip_selftest_fr_lincomb(void* out, size_t n_out, size_t count, const void* const* polys, const size_t* lens, const void* coeffs) {
+    if (n_out == 0) return 0;
+    std::vector<fr_lincomb_launch_t> plan;
+    if (fr_lincomb_plan(out, n_out, count, polys, lens, coeffs, plan)) return -1;
+    fr_mem_t* o = (fr_mem_t*)out;
+    for (const fr_lincomb_launch_t& L : plan)
+        for (size_t i = 0; i < n_out; i++) fr_lincomb_at(L.t, i).store(&o[i]);
+    return 0;
 }
 
 // ---- setup-time group operations (group.hip.h) -------------------------------------------------------

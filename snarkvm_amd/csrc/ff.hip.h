@@ -291,6 +291,42 @@ struct Fp {
         for (int i = 0; i < N; i++) r.v[i] = neg ? up[i] : (cd < 0 ? (uint32_t)t[i] : dn[i]);
         return r;
     }
+    // sum_{g < G} a[g] * b[g] with ONE Montgomery reduction (the reference's sum_of_products, fp_256.rs:167-222; here the terms of a linear
+    // combination of polynomials, poly.hip.h).  Column k holds at most N G operand products and N - 1 reduction products, each < 2^58, plus
+    // m_k < 2^29 and the carry < 2^35: for N = 9 that is 9 G + 8 < 64 products, G <= 6.  Value: a[g] canonical (< p), b[g] any integer
+    // < 2^(32 WORDS) with normalised limbs, so T < G p 2^(32 WORDS) and (T + m p) / 2^(29 N) < p (G 2^(32 WORDS - 29 N) + 1) < 2p as long as
+    // G 2^(32 WORDS) <= 2^(29 N) - Fr: 6 / 32 + 1; Fq has no such room, hence the second assertion.  Result canonical.
+    template <int G>
+    SV_HD static Fp sum_of_products(const Fp* a, const Fp* b) {
+        static_assert(G >= 1 && N * G + N - 1 < 64, "sum_of_products: the 64-bit column accumulator holds at most 63 products of 58 bits");
+        static_assert(G <= 8 && 32 * WORDS + 3 <= 29 * N, "sum_of_products: the sum must reduce to less than 2p");
+        uint32_t m[N], t[N];
+        uint64_t acc = 0;
+#pragma unroll
+        for (int k = 0; k < 2 * N; k++) {
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+#pragma unroll
+                for (int i = 0; i < N; i++) {
+                    const int j = k - i;
+                    if (j >= 0 && j < N) acc += (uint64_t)a[g].v[i] * b[g].v[j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < N; i++) {
+                const int j = k - i;
+                if (j >= 1 && j < N && i < k) acc += (uint64_t)m[i] * P::MOD[j];
+            }
+            if (k < N) {
+                m[k] = (0u - (uint32_t)acc) & LIMB_MASK;
+                acc += m[k];
+            } else {
+                t[k - N] = (k == 2 * N - 1) ? (uint32_t)acc : ((uint32_t)acc & LIMB_MASK);
+            }
+            acc >>= 29;
+        }
+        return cond_sub(t);
+    }
     // dedicated squaring: off-diagonal products once, against the doubled operand
     SV_HD Fp sqr() const {
         uint32_t m[N], t[N], v2[N];

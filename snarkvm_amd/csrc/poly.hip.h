@@ -9,6 +9,7 @@
 //   fr_distribute_powers_kernel v_i <- v_i * c * g^i                             fft/domain.rs:224-254
 //   fr_fold_vanishing_kernel    quotient / remainder by X^D - 1                  dense.rs:161-169 (divide_by_vanishing_poly)
 //   fr_mul_vanishing_kernel     p * (X^D - 1)                                    dense.rs:153-159
+//   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
 //
 // Representation note (ff.hip.h): the raw memory limbs of a, read as an internal value, are the internal Montgomery form of
 // a * 2^-5 ("shifted").  Sums and differences of shifted values are shifted values; the product of a TRUE internal
@@ -261,6 +262,62 @@ static __global__ void fr_onehot_kernel(fr_mem_t* v, size_t n, fr_mem_t x_mem, f
     fr_mem_t zero_mem;
     fr_t::zero().store(&zero_mem);
     for (; i < n; i += st) v[i] = (fr_t::load(&v[i]) == x) ? one_mem : zero_mem;
+}
+
+// ---- linear combination of polynomials ------------------------------------------------------------------------------
+// out[i] = sum_k c_k p_k[i] for i < n_out, p_k[i] = 0 from len_k on: every linear combination SonicKZG10::open_combinations materialises
+// (`poly += (coeff, cur_poly)` per term, sonic_pc/mod.rs:413-473) and the fold of batch_open (combine_polynomials, mod.rs:548-564), in ONE pass
+// over K + 1 vectors where a chain of AXPY passes moves 3K - 1.  The operand table travels BY KERNEL ARGUMENT: nothing is staged or retained (an
+// enqueue-only call inside a scope has no later moment to release a table), and pointers, lengths and coefficients are wave-uniform - scalar
+// loads from the kernel-argument segment.  Coefficients arrive in the TRUE internal form (the host ran from_mem_mont, ff.hip.h compiles for it),
+// vector elements are read raw ("shifted", see above): every product c_k * p_k[i], and so the sum, is a shifted value and is stored raw.
+// Terms are taken FR_LINCOMB_G at a time through Fp::sum_of_products: one Montgomery reduction per group instead of one per term (72 of the
+// 153 multiply-adds of a product).  What has been timed of that choice, and what is still an estimate, is stated in DESIGN.md section 4
+// (tools/bench_fr_lincomb.py is the tool).
+// The host sorts the operands by length, longest first (fr_lincomb_plan): the live operands at index i are a prefix of the table, a group whose
+// first operand has ended is skipped with everything behind it, and a shorter operand inside a live group reads as zero.
+static constexpr int FR_LINCOMB_G = 6;
+static_assert(FR_LINCOMB_G == 6, "fr_lincomb_at dispatches the short last group over 1 .. 5");
+static constexpr int FR_LINCOMB_CHUNK = 24;  // operands per launch: four groups; 24 x (8 + 8 + 36) B + 4 = 1252 B of the 4 KB of kernel arguments
+struct fr_lincomb_t {
+    const fr_mem_t* p[FR_LINCOMB_CHUNK];
+    size_t len[FR_LINCOMB_CHUNK];      // non-increasing over k < count
+    uint32_t c[FR_LINCOMB_CHUNK][9];   // limbs of c_k, true internal form
+    int count;
+};
+template <int G>
+SV_HD fr_t fr_lincomb_group(const fr_lincomb_t& t, int k0, size_t i) {
+    fr_t c[G], x[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        c[g] = fr_t::from_table(t.c[k0 + g]);
+        x[g] = i < t.len[k0 + g] ? fr_t::load(&t.p[k0 + g][i]) : fr_t::zero();
+    }
+    return fr_t::sum_of_products<G>(c, x);
+}
+// the per-element routine: the kernel below and the host replay (snarkvm_hip_selftest_fr_lincomb) both call it
+SV_HD fr_t fr_lincomb_at(const fr_lincomb_t& t, size_t i) {
+    fr_t acc = fr_t::zero();
+#pragma unroll 1
+    for (int k0 = 0; k0 < t.count && i < t.len[k0]; k0 += FR_LINCOMB_G) {
+        fr_t s;
+        switch (t.count - k0) {  // only the last group of a launch is short
+            case 1: s = fr_lincomb_group<1>(t, k0, i); break;
+            case 2: s = fr_lincomb_group<2>(t, k0, i); break;
+            case 3: s = fr_lincomb_group<3>(t, k0, i); break;
+            case 4: s = fr_lincomb_group<4>(t, k0, i); break;
+            case 5: s = fr_lincomb_group<5>(t, k0, i); break;
+            default: s = fr_lincomb_group<FR_LINCOMB_G>(t, k0, i); break;
+        }
+        acc = acc + s;
+    }
+    return acc;
+}
+// out may be the start of one operand: a thread reads every operand at i before it writes out[i], and no other thread touches index i
+static __global__ void __launch_bounds__(256) fr_lincomb_kernel(fr_mem_t* out, size_t n_out, fr_lincomb_t t) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < n_out; i += st) fr_lincomb_at(t, i).store(&out[i]);
 }
 
 // ---- X^D - 1 -------------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -72,6 +72,24 @@ def polymul_device(lg, out_ptr, polys=(), evals=()):
     ep = (ctypes.c_void_p * max(1, len(evals)))(*evals)
     el = (ctypes.c_size_t * max(1, len(evals)))(*([1 << lg] * len(evals)))
     _lib.check(_lib.lib().snarkvm_hip_polymul_device(ctypes.c_void_p(int(out_ptr)), len(polys), pp, pl, len(evals), ep, el, lg))
+
+
+FR_LINCOMB_CHUNK = 24  # operands per kernel launch of snarkvm_hip_fr_lincomb (include/snarkvm_hip.h; csrc/poly.hip.h FR_LINCOMB_CHUNK)
+
+
+def fr_lincomb_device(d_out, n_out, d_polys, lens, coeffs):
+    """Extension (no reference counterpart): d_out[i] = sum_k coeffs[k] * d_polys[k][i] for i < n_out over vectors that live in device memory
+    (`snarkvm_hip_fr_lincomb`, on_device = 1); d_polys[k] counts as zero from lens[k] <= n_out on.  coeffs: (k, 4) Montgomery limbs on the
+    host.  No operand is written; d_out may be the start of one of them.  Inside a scope the call is only enqueued."""
+    k = len(d_polys)
+    if len(lens) != k:
+        raise ValueError("length mismatch")
+    cs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4) if k else np.zeros((0, 4), dtype=np.uint64)
+    if cs.shape[0] != k:
+        raise ValueError("length mismatch")
+    pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
+    pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
+    _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(ctypes.c_void_p(int(d_out) if d_out else None), int(n_out), k, pp, pl, _ptr(cs), 1))
 
 
 def msm(points, scalars):

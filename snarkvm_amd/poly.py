@@ -4,6 +4,7 @@ Host mirror of the reference functions the Varuna prover runs between its NTTs a
 
     DensePolynomial::{evaluate, mul_by_vanishing_poly, divide_by_vanishing_poly}   fft/polynomial/dense.rs:98-114, 153-169
     `polynomial / (X - point)` (Polynomial::divide_with_q_and_r)                    fft/polynomial/mod.rs:222-256
+    `poly += (coeff, cur_poly)` over the terms of a linear combination              polycommit/sonic_pc/mod.rs:413-473, 548-564
     batch_inversion / batch_inversion_and_mul                                       fields/src/lib.rs:66-129
     EvaluationDomain::{distribute_powers_and_mul_by_const,
                        evaluate_all_lagrange_coefficients}                          fft/domain.rs:224-292
@@ -49,6 +50,22 @@ def vec_op(op, a, b=None, c=None, scalar=None):
     _lib.check(_lib.lib().snarkvm_hip_fr_vec_op(ctypes.c_int(VEC_OPS[op]), _p(out), _p(a), _p(b), _p(c), _p(s), ctypes.c_size_t(n),
                                                ctypes.c_int(0)))
     return out
+
+
+def lincomb(coeffs, polys):
+    """sum_k coeffs[k] * polys[k] over polynomials of any lengths in ONE device pass (`snarkvm_hip_fr_lincomb`): what the reference builds
+    term by term with `poly += (coeff, cur_poly)` (sonic_pc/mod.rs:427-447, 548-564).  Trimmed like a DensePolynomial."""
+    polys = [_v(p) for p in polys]
+    k = len(polys)
+    cs = _v(coeffs) if k else np.zeros((0, 4), dtype=np.uint64)
+    if cs.shape[0] != k:
+        raise ValueError("length mismatch")
+    n = max([p.shape[0] for p in polys] + [0])
+    out = np.empty((n, 4), dtype=np.uint64)
+    ptrs = (ctypes.c_void_p * max(1, k))(*[p.ctypes.data if p.shape[0] else None for p in polys])
+    lens = (ctypes.c_size_t * max(1, k))(*[p.shape[0] for p in polys])
+    _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(_p(out), n, k, ptrs, lens, _p(cs), 0))
+    return trim(out)
 
 
 def divide_by_linear(coeffs, point):

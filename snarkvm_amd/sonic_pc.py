@@ -1,4 +1,4 @@
-"""`SonicKZG10::{commit, combine_for_open, batch_open}` (algorithms/src/polycommit/sonic_pc/mod.rs:177-342) on the gfx950 backend.
+"""`SonicKZG10::{commit, combine_for_open, batch_open, open_combinations}` (algorithms/src/polycommit/sonic_pc/mod.rs:177-342, 413-473) on the gfx950 backend.
 
 The caller side of the MSM hot path.  The reference fans the commitments of one call out over a CPU pool, one
 `KZG10::commit` / `KZG10::commit_lagrange` per labelled polynomial (mod.rs:186-245), each of which re-uploads its slice of the
@@ -8,6 +8,10 @@ launch (`snarkvm_hip_msm_registered_batch_ex`): instance k = (plaintext base ran
 device fuses `Fr::to_bigint` into its scalar read (kzg10/mod.rs:455-474) and runs the instances concurrently on several
 streams (and devices); a degree-bounded polynomial is the same MSM starting at the shifted-powers offset
 `max_bound - degree_bound` (data_structures.rs:310-331).
+
+A linear combination of polynomials - the fold of `batch_open` over the polynomials of a query point, and every `LinearCombination`
+that `open_combinations` materialises - is ONE device pass over its operands (`poly.lincomb`, `snarkvm_hip_fr_lincomb`), whatever their
+number and lengths, where the reference adds term by term.
 
 The Fiat-Shamir sponge is out of scope: `batch_open` takes the challenges it would squeeze from any object
 with `squeeze_short_nonnative_field_element()`.
@@ -20,6 +24,7 @@ from . import _lib, kzg10, poly
 from .kzg10 import KZG10, KZGRandomness, PCError
 from .layout import G1_AFFINE, G1_PROJECTIVE
 
+FR_MODULUS = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001  # r (fr.rs:137-142)
 FR_ONE = np.array([0x7D1C7FFFFFFFFFF3, 0x7257F50F6FFFFFF2, 0x16D81575512C0FEE, 0x0D4BDA322BBB9A9D], dtype=np.uint64)  # Fr R (fr.rs:158-163)
 
 
@@ -209,25 +214,11 @@ class SonicKZG10:
 
     @staticmethod
     def combine_polynomials(coeffs_polys_rands):
-        """sonic_pc/mod.rs:548-564: sum_i coeff_i * poly_i and the same combination of the blinding polynomials (device AXPY)."""
+        """sonic_pc/mod.rs:548-564: sum_i coeff_i * poly_i and the same combination of the blinding polynomials, one device pass each."""
         items = list(coeffs_polys_rands)
-
-        def combine(vectors):
-            length = max([v.shape[0] for _, v in vectors] + [0])
-            acc = np.zeros((length, 4), dtype=np.uint64)
-            for coeff, v in vectors:
-                if v.shape[0] == 0:
-                    continue
-                padded = np.zeros((length, 4), dtype=np.uint64)
-                padded[: v.shape[0]] = v
-                if np.array_equal(np.asarray(coeff, dtype=np.uint64).reshape(4), FR_ONE):
-                    acc = poly.vec_op("add", acc, padded)
-                else:
-                    acc = poly.vec_op("axpy", acc, padded, scalar=coeff)
-            return poly.trim(acc)
-
-        combined_poly = combine([(c, p) for c, p, _ in items])
-        combined_rand = KZGRandomness(combine([(c, np.ascontiguousarray(r.blinding_polynomial, dtype=np.uint64).reshape(-1, 4)) for c, _, r in items]))
+        coeffs = [c for c, _, _ in items]
+        combined_poly = poly.lincomb(coeffs, [p for _, p, _ in items])
+        combined_rand = KZGRandomness(poly.lincomb(coeffs, [r.blinding_polynomial for _, _, r in items]))
         return combined_poly, combined_rand
 
     @staticmethod
@@ -267,6 +258,94 @@ class SonicKZG10:
             fs_rng.squeeze_short_nonnative_field_element()  # `_randomizer` (mod.rs:331)
             proofs.append(KZG10.open(_OpenPowers(ck.powers()), polynomial, point, rand))
         return proofs
+
+    @staticmethod
+    def open_combinations(max_degree, ck, linear_combinations, polynomials, rands, query_set, fs_rng):
+        """sonic_pc/mod.rs:413-473: every linear combination becomes a labelled polynomial (and its randomness) - `ONE` terms are not
+        committed to and skipped; a degree-bounded polynomial may only stand alone, with coefficient one; the hiding bound is the largest
+        of the terms' - and the lot is opened with `batch_open`.  Returns its proofs (`BatchLCProof.proof`)."""
+        polys, rands = list(polynomials), list(rands)
+        if len(polys) != len(rands):
+            raise PCError("length mismatch")
+        label_map = {p.label: (p, r) for p, r in zip(polys, rands)}
+        lc_polynomials, lc_randomness = [], []
+        for lc in linear_combinations:
+            coeffs, cur_polys, cur_rands = [], [], []
+            degree_bound = hiding_bound = None
+            for coeff, term in lc.iter():
+                if term is ONE:
+                    continue
+                if term not in label_map:
+                    raise PCError(f"MissingPolynomial {{ label: {term} }}")
+                cur_poly, cur_rand = label_map[term]
+                if cur_poly.degree_bound is not None:
+                    if len(lc) != 1:
+                        raise PCError(f"EquationHasDegreeBounds({lc.label})")
+                    if not np.array_equal(coeff, FR_ONE):
+                        raise PCError(f"Coefficient must be one for degree-bounded equations ({lc.label})")
+                    degree_bound = cur_poly.degree_bound
+                if cur_poly.hiding_bound is not None:  # Some(_) > None
+                    hiding_bound = cur_poly.hiding_bound if hiding_bound is None else max(hiding_bound, cur_poly.hiding_bound)
+                coeffs.append(coeff)
+                cur_polys.append(cur_poly.coeffs)
+                cur_rands.append(cur_rand.blinding_polynomial)
+            lc_polynomials.append(LabeledPolynomial(lc.label, poly.lincomb(coeffs, cur_polys), degree_bound, hiding_bound))
+            lc_randomness.append(KZGRandomness(poly.lincomb(coeffs, cur_rands)))
+        return SonicKZG10.batch_open(max_degree, ck, lc_polynomials, query_set, lc_randomness, fs_rng)
+
+
+class _One:
+    """`LCTerm::One` (data_structures.rs:455-462): the constant term, which is not committed to.  Sorts before every label."""
+
+    def __repr__(self):
+        return "1"
+
+
+ONE = _One()
+
+
+class LinearCombination:
+    """sonic_pc/data_structures.rs:525-576: a labelled map term -> coefficient, the term a polynomial label or `ONE`, the coefficient
+    (4,) Montgomery limbs.  `new` merges equal terms (a sum that comes to zero stays, as in the reference); `add` also drops a term
+    whose coefficient has become zero."""
+
+    def __init__(self, label, terms=()):
+        self.label = label
+        self.terms = {}
+        for c, t in terms:
+            self.terms[t] = _fr_add(self.terms.get(t), c)
+
+    @classmethod
+    def empty(cls, label):
+        return cls(label)
+
+    @classmethod
+    def new(cls, label, terms):
+        return cls(label, terms)
+
+    def add(self, c, t):
+        self.terms[t] = _fr_add(self.terms.get(t), c)
+        if not self.terms[t].any():
+            del self.terms[t]
+        return self
+
+    def is_empty(self):
+        return not self.terms
+
+    def __len__(self):
+        return len(self.terms)
+
+    def iter(self):
+        """(coefficient, term) in the order of the reference's BTreeMap: `ONE` first, then the labels."""
+        for t in sorted(self.terms, key=lambda t: (t is not ONE, "" if t is ONE else t)):
+            yield self.terms[t], t
+
+
+def _fr_add(a, b):
+    """a + b in Fr on (4,) Montgomery limbs (the Montgomery form is linear); a = None counts as zero."""
+    val = lambda x: 0 if x is None else sum(int(w) << (64 * i) for i, w in enumerate(np.asarray(x, dtype=np.uint64).reshape(4)))  # noqa: E731
+    s = (val(a) + val(b)) % FR_MODULUS
+    return np.array([(s >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
 
 
 class _OpenPowers:
