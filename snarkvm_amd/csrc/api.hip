@@ -474,7 +474,6 @@ static void msm_registered_host_scalars(void* out, const snarkvm_hip_bases* h, s
             for (size_t l = 1; l < L; l++) HIP_TRY(hipStreamWaitEvent(lg.lanes[l]->stream, ready, 0));
             for (size_t j = 0; j < mine.size(); j++) merged.push_back(lg.lanes[j % L]->new_event());
         }
-        const g1_aff_mem_t* base = h->d[lg.lanes[0]->dev->logical];
         auto upload = [&](size_t j, hipStream_t st) {
             lane_t& c = *lg.lanes[j % L];
             const size_t lo = bound[mine[j]], hi = bound[mine[j] + 1];
@@ -486,16 +485,25 @@ static void msm_registered_host_scalars(void* out, const snarkvm_hip_bases* h, s
             const size_t lo = bound[mine[j]], hi = bound[mine[j] + 1];
             const size_t a0 = lo < n0 ? lo : n0, a1 = hi < n0 ? hi : n0;  // part inside range 0
             const size_t m0 = a1 - a0;
-            const g1_aff_mem_t* b0 = base + off0 + a0;
-            const g1_aff_mem_t* b1 = base + off1 + (lo > n0 ? lo - n0 : 0);
+            const size_t s1 = off1 + (lo > n0 ? lo - n0 : 0);  // where the part inside range 1 begins
+            msm_req_t r;
+            if (m0)
+                r.off0 = off0 + a0, r.n0 = m0, r.off1 = s1, r.n1 = hi - lo - m0;
+            else
+                r.off0 = s1, r.n0 = hi - lo;
             msm_bucket_sink_t mine_sink = sink;
             if (use_sink) {
                 mine_sink.after = j ? merged[j - 1] : nullptr;
                 mine_sink.done = merged[j];
             }
-            const msm_pending_t pd = msm_run<fq_t>(c, m0 ? b0 : b1, c.scalars_tmp.as<uint4>(), hi - lo, c.pin.as<uint8_t>() + (use_sink ? 0 : slot * (j / L)), chunk_c,
-                                                   b1, m0 ? m0 : ~(size_t)0, scalars_montgomery, h->tables, h->n, prof, h->table_bits, nullptr,
-                                                   use_sink ? &mine_sink : nullptr);
+            msm_job_t<fq_t> job = msm_handle_job<fq_t>(*h, lg.lanes[0]->dev->logical, r);
+            job.scalars = c.scalars_tmp.as<uint4>();
+            job.scalars_montgomery = scalars_montgomery;
+            job.window_bits = chunk_c;
+            job.host_planes = c.pin.as<uint8_t>() + (use_sink ? 0 : slot * (j / L));
+            job.profile = prof;
+            job.sink = use_sink ? &mine_sink : nullptr;
+            const msm_pending_t pd = msm_run<fq_t>(c, job);
             if (!use_sink) pend[j] = pd;
         };
         if (mine.size() == 1) {
@@ -510,7 +518,11 @@ static void msm_registered_host_scalars(void* out, const snarkvm_hip_bases* h, s
         if (use_sink) {  // the last merge (which waited for all earlier ones), then the one tail on lane 0
             lane_t& c0 = *lg.lanes[0];
             HIP_TRY(hipStreamWaitEvent(c0.stream, merged.back(), 0));
-            pend[0] = msm_tail_from_sink<fq_t>(c0, max_cnt, chunk_c, sink, c0.pin.p, h->tables, h->table_bits);
+            msm_job_t<fq_t> tail = msm_handle_job<fq_t>(*h, c0.dev->logical, msm_req_t{});  // the chunks' plan: the largest chunk over the handle's tables
+            tail.n = max_cnt;
+            tail.window_bits = chunk_c;
+            tail.host_planes = c0.pin.p;
+            pend[0] = msm_tail_from_sink<fq_t>(c0, tail, sink);
         }
         for (size_t l = 0; l < L; l++) {
             HIP_TRY(hipStreamSynchronize(lg.lanes[l]->alt));
@@ -537,6 +549,27 @@ static void msm_single_coalesced(void* out, const snarkvm_hip_bases* h, size_t o
     t.window_bits = window_bits;
     msm_coalesced<fq_t>(*h, &t, 1);
 }
+// One MSM over registered bases, whatever the entry point: enqueued on the caller's scope, fused with concurrent callers, cut into scalar chunks
+// (host scalars), or run synchronously on a lane of the device that owns the scalars.
+static void msm_registered_single(const snarkvm_hip_bases* h, const msm_req_t& one, int scalars_on_device, int scalars_montgomery, int window_bits) {
+    const size_t n = one.n0 + one.n1;
+    if (msm_scope_enqueue<fq_t>(*h, &one, 1, scalars_on_device, scalars_montgomery, window_bits)) {
+    } else if (msm_coalescible(*h, n, window_bits)) {
+        msm_single_coalesced(one.out, h, one.off0, one.n0, one.off1, one.n1, one.scalars, scalars_on_device, scalars_montgomery, window_bits);
+    } else if (!scalars_on_device) {
+        msm_registered_host_scalars(one.out, h, one.off0, one.n0, one.off1, one.n1, one.scalars, scalars_montgomery, window_bits);
+    } else {
+        lane_guard lg(device_for(one.scalars, n ? 1 : 0));
+        lane_t& c = lg.c();
+        c.begin_call();
+        msm_job_t<fq_t> job = msm_handle_job<fq_t>(*h, c.dev->logical, one);
+        job.scalars = (const uint4*)one.scalars;
+        job.scalars_montgomery = scalars_montgomery;
+        job.window_bits = window_bits;
+        msm_run_sync<fq_t>(c, job, one.out);
+        c.end_call();
+    }
+}
 RustError snarkvm_hip_msm_registered(void* out, const snarkvm_hip_bases_t* h, size_t offset, size_t npoints, const void* scalars,
                                      int scalars_on_device, int window_bits) {
     API_TRY
@@ -545,19 +578,7 @@ RustError snarkvm_hip_msm_registered(void* out, const snarkvm_hip_bases_t* h, si
     if (!out || (npoints && !scalars)) throw hip_failure{hipErrorInvalidValue, "msm_registered: null argument", __LINE__};
     msm_req_t one;
     one.off0 = offset, one.n0 = npoints, one.scalars = scalars, one.out = out;
-    if (msm_scope_enqueue<fq_t>(*h, &one, 1, scalars_on_device, 0, window_bits)) {
-    } else if (msm_coalescible(*h, npoints, window_bits)) {
-        msm_single_coalesced(out, h, offset, npoints, 0, 0, scalars, scalars_on_device, 0, window_bits);
-    } else if (!scalars_on_device) {
-        msm_registered_host_scalars(out, h, offset, npoints, 0, 0, scalars, 0, window_bits);
-    } else {
-        lane_guard lg(device_for(scalars, npoints ? 1 : 0));
-        lane_t& c = lg.c();
-        c.begin_call();
-        msm_run_sync<fq_t>(c, h->d[c.dev->logical] + offset, (const uint4*)scalars, npoints, out, window_bits, nullptr, ~(size_t)0, 0, h->tables, h->n,
-                           h->table_bits);
-        c.end_call();
-    }
+    msm_registered_single(h, one, scalars_on_device, 0, window_bits);
     API_CATCH
 }
 RustError snarkvm_hip_msm_registered_ex(void* out, const snarkvm_hip_bases_t* h, size_t off0, size_t n0, size_t off1, size_t n1,
@@ -565,23 +586,10 @@ RustError snarkvm_hip_msm_registered_ex(void* out, const snarkvm_hip_bases_t* h,
     API_TRY
     if (!h || off0 + n0 > h->n || off1 + n1 > h->n) throw hip_failure{hipErrorInvalidValue, "msm_registered_ex: range exceeds the registered bases", __LINE__};
     check_window_bits(window_bits, "msm_registered_ex");
-    const size_t n = n0 + n1;
-    if (!out || (n && !scalars)) throw hip_failure{hipErrorInvalidValue, "msm_registered_ex: null argument", __LINE__};
+    if (!out || ((n0 + n1) && !scalars)) throw hip_failure{hipErrorInvalidValue, "msm_registered_ex: null argument", __LINE__};
     msm_req_t one;
     one.off0 = off0, one.n0 = n0, one.off1 = n1 ? off1 : 0, one.n1 = n1, one.scalars = scalars, one.out = out;
-    if (msm_scope_enqueue<fq_t>(*h, &one, 1, scalars_on_device, scalars_montgomery, window_bits)) {
-    } else if (msm_coalescible(*h, n, window_bits)) {
-        msm_single_coalesced(out, h, off0, n0, off1, n1, scalars, scalars_on_device, scalars_montgomery, window_bits);
-    } else if (!scalars_on_device) {
-        msm_registered_host_scalars(out, h, off0, n0, off1, n1, scalars, scalars_montgomery, window_bits);
-    } else {
-        lane_guard lg(device_for(scalars, n ? 1 : 0));
-        lane_t& c = lg.c();
-        c.begin_call();
-        const g1_aff_mem_t* base = h->d[c.dev->logical];
-        msm_run_sync<fq_t>(c, base + off0, (const uint4*)scalars, n, out, window_bits, base + off1, n0, scalars_montgomery, h->tables, h->n, h->table_bits);
-        c.end_call();
-    }
+    msm_registered_single(h, one, scalars_on_device, scalars_montgomery, window_bits);
     API_CATCH
 }
 

@@ -120,7 +120,12 @@ RustError snarkvm_hip_msm_g2_registered(void* out, const snarkvm_hip_bases_g2_t*
         c.phase_end();
         d_sc = c.scalars_tmp.as<uint4>();
     }
-    msm_run_sync<fq2_t>(c, h->d[c.dev->logical] + offset, d_sc, npoints, out, window_bits, nullptr, ~(size_t)0, 0, h->tables, h->n, h->table_bits);
+    msm_req_t one;
+    one.off0 = offset, one.n0 = npoints;
+    msm_job_t<fq2_t> job = msm_handle_job<fq2_t>(*h, c.dev->logical, one);
+    job.scalars = d_sc;
+    job.window_bits = window_bits;
+    msm_run_sync<fq2_t>(c, job, out);
 #endif
     API_END
 }

@@ -24,6 +24,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -969,14 +970,39 @@ struct msm_bucket_sink_t {
     // chained - a chunk's merge waits for `after` (the previous chunk's merge) and records `done`
     hipEvent_t after = nullptr, done = nullptr;
 };
+// SNARKVM_HIP_TRACE=2 (diagnostics): wait for the stream after every phase and name it on stderr - locates a kernel that never returns
+static int msm_trace_level() {
+    static const int level = getenv("SNARKVM_HIP_TRACE") ? atoi(getenv("SNARKVM_HIP_TRACE")) : 0;
+    return level;
+}
+// The phases of one msm_run, handed from stage to stage: profiling events on the lane (`profile`) and the trace lines (n: the size they quote).
+struct msm_phases_t {
+    lane_t& c;
+    bool profile;
+    int trace;
+    size_t n;
+    const char* cur = "";
+    void begin(const char* name) {
+        cur = name;
+        if (trace >= 2) fprintf(stderr, "[snarkvm_hip] msm n=%zu: %s ...\n", n, name);
+        if (profile) c.phase_begin(name);
+    }
+    void end() {
+        if (profile) c.phase_end();
+        if (trace >= 2) {
+            const hipError_t e = hipStreamSynchronize(c.stream);
+            fprintf(stderr, "[snarkvm_hip] msm n=%zu: %s done (%s)\n", n, cur, hipGetErrorString(e));
+        }
+    }
+};
 // Steps 6.-9. of msm_run on the tail arithmetic T (F itself, or fqz_t for a G1 MSM whose accumulate kernel left raw lazy partial sums):
 // reduce rounds (cnt_a, start_a, part_a) -> (cnt_b, start_b, part_b) -> ..., then either the merge into a bucket sink (a chunk of a
 // bigger MSM; pd.nplanes = 0) or fold -> bit planes -> copy to `host_planes`.
-template <class T, class PB, class PE>
+template <class T>
 static void msm_reduce_and_tail(lane_t& c, const msm_plan_t& pl, const msm_tail_geom_t& tg, uint32_t nwin, uint32_t nbt, int rounds, size_t T0_max, size_t T1_max,
-                                const msm_bucket_sink_t* sink, msm_pending_t& pd, void* host_planes, PB&& phase_begin, PE&& phase_end) {
+                                const msm_bucket_sink_t* sink, msm_pending_t& pd, void* host_planes, msm_phases_t& ph) {
     hipStream_t st = c.stream;
-    phase_begin("msm_reduce_partials");
+    ph.begin("msm_reduce_partials");
     uint32_t *cnt_in = c.cnt_a.as<uint32_t>(), *cnt_out = c.cnt_b.as<uint32_t>();
     uint32_t *start_in = c.start_a.as<uint32_t>(), *start_out = c.start_b.as<uint32_t>();
     xyzz_mem_t<T> *pin = c.part_a.as<xyzz_mem_t<T>>(), *pout = c.part_b.as<xyzz_mem_t<T>>();
@@ -993,22 +1019,22 @@ static void msm_reduce_and_tail(lane_t& c, const msm_plan_t& pl, const msm_tail_
         std::swap(pin, pout);
         T_in_max = T_out_max;
     }
-    phase_end();
+    ph.end();
     if (sink) {
         // a chunk of a bigger MSM: its per-bucket partial sums join the sink; the tail runs once, after the last chunk (msm_tail_from_sink)
-        phase_begin("msm_bucket_merge");
+        ph.begin("msm_bucket_merge");
         if (sink->after) HIP_TRY(hipStreamWaitEvent(st, sink->after, 0));
         hipLaunchKernelGGL((msm_bucket_merge_kernel<T>), dim3((nbt + 255) / 256), dim3(256), 0, st, (const xyzz_mem_t<T>*)pin, (const uint32_t*)start_in,
                            (const uint32_t*)cnt_in, (xyzz_mem_t<T>*)sink->acc, nbt, sink->L, sink->slot);
         if (sink->done) HIP_TRY(hipEventRecord(sink->done, st));
-        phase_end();
+        ph.end();
         HIP_TRY(hipGetLastError());
         pd.nplanes = 0;
         return;
     }
-    phase_begin("msm_bucket_reduce");
+    ph.begin("msm_bucket_reduce");
     msm_tail_launch<T>(c, pl, tg, nwin, nbt, pin, start_in, cnt_in, pd, host_planes);
-    phase_end();
+    ph.end();
 }
 // Step 5 of msm_run: the accumulate launch for F - G1 on the lazy arithmetic (ffl.hip.h), G2 on a lane pair (ffl2p.hip.h), or F's exact kernel
 // (tuning lazy / lazy2 = 0) - `nthreads` segments of pl.S sorted entries, per-bucket partial sums into part_a (start_a: their slots).
@@ -1062,60 +1088,83 @@ static void msm_launch_accumulate(lane_t& c, const msm_plan_t& pl, const aff_mem
         hipLaunchKernelGGL((msm_accumulate_seg_kernel<F, 1, false>), dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, st, vbase, c.sorted.as<uint32_t>(), boffp,
                            c.start_a.as<uint32_t>(), c.part_a.as<xyzz_mem_t<F>>(), nbt, pl.S, dbg_mask);
 }
-// Device side of one MSM on lane `c`: d_bases = converted device bases; d_scalars = device scalars (32 B each).  Everything
-// is enqueued on the lane's stream, ending with the copy of the bit-plane sums into `host_planes` (pinned, >=
-// msm_plane_bytes<F>(...)); the caller synchronises the stream and runs msm_collect / msm_accum_t::finish.
 template <class F>
 static size_t msm_plane_bytes() {
     return (size_t)MSM_MAX_POS * msm_point_bytes<F>();  // upper bound on tail windows * bits
 }
+// One device-side MSM, as msm_run takes it.
 template <class F>
-static msm_pending_t msm_run(lane_t& c, const aff_mem_t<F>* d_bases, const uint4* d_scalars, size_t n, void* host_planes, int window_bits,
-                             const aff_mem_t<F>* d_bases1 = nullptr, size_t n0 = ~(size_t)0, int scalars_montgomery = 0, int tables = 1,
-                             size_t table_stride = 0, bool profile = true, int table_bits = 0, const msm_multi_t* mu = nullptr,
-                             const msm_bucket_sink_t* sink = nullptr, hipEvent_t scalars_read = nullptr) {
-    // scalars_read: recorded on the lane's stream behind the last kernel that reads the scalar vectors (the digit kernel; wide windows:
-    // the fused level-1 scatter) - from there on the caller may overwrite them while the MSM is still running
-    // mu != nullptr: fused multi-instance run (msm_sort.hip.h): n = mu->npad padded positions, d_bases = the handle's table array,
-    // d_scalars unused (the instance table carries the pointers), one bucket window per instance; host_planes holds
-    // mu->K * 2 * (fold_m + 1) planes.
-    // SNARKVM_HIP_TRACE=2 (diagnostics): wait for the stream after every phase and name it on stderr - locates a kernel that never returns
-    static const int trace2 = getenv("SNARKVM_HIP_TRACE") ? atoi(getenv("SNARKVM_HIP_TRACE")) : 0;
-    const char* cur_phase = "";
-    auto phase_begin = [&](const char* name) {
-        cur_phase = name;
-        if (trace2 >= 2) fprintf(stderr, "[snarkvm_hip] msm n=%zu: %s ...\n", n, name);
-        if (profile) c.phase_begin(name);
-    };
-    auto phase_end = [&]() {
-        if (profile) c.phase_end();
-        if (trace2 >= 2) {
-            const hipError_t e = hipStreamSynchronize(c.stream);
-            fprintf(stderr, "[snarkvm_hip] msm n=%zu: %s done (%s)\n", n, cur_phase, hipGetErrorString(e));
-        }
-    };
-    msm_pending_t pd;
-    pd.planes = host_planes;
+struct msm_job_t {
+    // bases (converted, on the lane's device): scalar i < n0 meets bases[i], the others bases1[i - n0]; bases1 == nullptr: one range, n0 is not read.
+    // tables > 1: table j, 2^(table_bits * j) * P, lies table_stride slots behind table j - 1 (bases_handle_t).
+    const aff_mem_t<F>* bases = nullptr;
+    const aff_mem_t<F>* bases1 = nullptr;
+    size_t n0 = 0;
+    int tables = 1;
+    size_t table_stride = 0;
+    int table_bits = 0;
+    // scalars: n of them on the device, 32 B each; scalars_montgomery: Fr memory images, the read fuses Fr::to_bigint
+    const uint4* scalars = nullptr;
+    size_t n = 0;
+    int scalars_montgomery = 0;
+    // geometry: the window width, 0 = the planner's choice
+    int window_bits = 0;
+    // output: pinned, >= msm_plane_bytes<F>() - the bit-plane sums (msm_run_sync, msm_tail_from_sink: set by the callee / read as the staging area)
+    void* host_planes = nullptr;
+    // options
+    bool profile = true;  // the phases leave profiling events on the lane
+    // fused multi-instance run (msm_sort.hip.h): n = multi->npad padded positions, bases = the handle's table array, `scalars` unused (the instance
+    // table carries the pointers), one bucket window per instance; host_planes holds multi->K * 2 * (fold_m + 1) planes
+    const msm_multi_t* multi = nullptr;
+    const msm_bucket_sink_t* sink = nullptr;  // a chunk of a bigger MSM: its partial sums join the sink, no tail
+    // recorded on the lane's stream behind the last kernel that reads the scalar vectors (the digit kernel; wide windows: the fused level-1
+    // scatter) - from there on the caller may overwrite them while the MSM is still running
+    hipEvent_t scalars_read = nullptr;
+};
+// What the stages of msm_run share: plan, geometry and the filled kernel parameter blocks.  Plain values; the lane's buffers are named where they are used.
+template <class F>
+struct msm_layout_t {
+    msm_plan_t pl;
+    bool wide;    // u32 digits, three-level sort
+    bool fused;   // the level-1 partition reads the scalars itself
+    bool ltail;   // the tail runs on the lazy arithmetic
+    bool single_round, prefetch_ok;  // see msm_stage_accumulate
+    uint32_t nwin, nbt;              // bucket windows of the tail (multi: one per instance), buckets in all
+    size_t E_max, T0_max, T1_max;    // digit entries; bounds on the partial sums before / after the first reduce round
+    const aff_mem_t<F>* vbase;       // what the sort's virtual indices are slots of (msm_radix_params_t)
+    msm_tail_geom_t tg;
+    msm_radix_params_t rp;
+    msm_digit_params_t dp;
+    // the radix partition: B1 level-1 bins per window, nbins in all, LBL key bits at the last level, nseg_last segments feeding it
+    int LBL;
+    uint32_t B1, nbins, nseg_last;
+    size_t ncounts1, tiles1, tiles2_max;
+};
+// Validation, the plan, the bucket-side workspace and the geometry of every later stage.  Fills the pending record the host finish reads.
+template <class F>
+static msm_layout_t<F> msm_layout(lane_t& c, const msm_job_t<F>& j, msm_pending_t& pd) {
+    const msm_multi_t* mu = j.multi;
+    const size_t n = j.n;
+    size_t n0 = j.bases1 ? j.n0 : n;
     if (n0 > n) n0 = n;
-    if (n == 0) return pd;  // no planes: the sum is the point at infinity
+    msm_layout_t<F> L{};
     if (n >= ((size_t)1 << 31)) throw hip_failure{hipErrorInvalidValue, "msm: npoints must be < 2^31", __LINE__};
-    const msm_plan_t pl = msm_make_plan(n, mu ? table_bits : window_bits, tables, table_bits);
-    const bool wide = pl.c > 16;  // u32 digits, three-level sort
-    if (mu && (wide || pl.W != 1 || pl.c < 12 || (size_t)pl.J * mu->hn >= ((size_t)1 << 31) || n != mu->npad || n % SORT_TILE))
+    const msm_plan_t pl = L.pl = msm_make_plan(n, mu ? j.table_bits : j.window_bits, j.tables, j.table_bits);
+    L.wide = pl.c > 16;
+    if (mu && (L.wide || pl.W != 1 || pl.c < 12 || (size_t)pl.J * mu->hn >= ((size_t)1 << 31) || n != mu->npad || n % SORT_TILE))
         throw hip_failure{hipErrorInvalidValue, "msm: geometry not eligible for a fused multi-instance run", __LINE__};
     if ((size_t)pl.Wd * n >= ((size_t)1 << 32)) throw hip_failure{hipErrorInvalidValue, "msm: windows * npoints must be < 2^32", __LINE__};
     if ((size_t)pl.J * n >= ((size_t)1 << 31)) throw hip_failure{hipErrorInvalidValue, "msm: tables * npoints must be < 2^31", __LINE__};
-    const aff_mem_t<F>* vb1 = d_bases1 ? d_bases1 : d_bases;
-    const aff_mem_t<F>* vbase = mu ? d_bases : (vb1 < d_bases ? vb1 : d_bases);
+    const aff_mem_t<F>* vb1 = j.bases1 ? j.bases1 : j.bases;
+    L.vbase = mu ? j.bases : (vb1 < j.bases ? vb1 : j.bases);
     if (!mu) {
-        const size_t top0 = (size_t)(d_bases - vbase) + n0, top1 = (size_t)(vb1 - vbase) + (n - n0);
-        if ((size_t)(pl.J - 1) * table_stride + (top0 > top1 ? top0 : top1) >= ((size_t)1 << 31))
+        const size_t top0 = (size_t)(j.bases - L.vbase) + n0, top1 = (size_t)(vb1 - L.vbase) + (n - n0);
+        if ((size_t)(pl.J - 1) * j.table_stride + (top0 > top1 ? top0 : top1) >= ((size_t)1 << 31))
             throw hip_failure{hipErrorInvalidValue, "msm: base slots must be addressable in 31 bits (tables * registered points < 2^31)", __LINE__};
     }
-    hipStream_t st = c.stream;
-    const size_t E_max = (size_t)pl.Wd * n;
-    const uint32_t nwin = mu ? mu->K : (uint32_t)pl.W;  // bucket windows of the tail (multi: one per instance)
-    const uint32_t nbt = nwin * pl.nb;
+    const size_t E_max = L.E_max = (size_t)pl.Wd * n;
+    const uint32_t nwin = L.nwin = mu ? mu->K : (uint32_t)pl.W;
+    const uint32_t nbt = L.nbt = nwin * pl.nb;
 
     c.scan_tmp.ensure((scan_tmp_elems((size_t)nbt + 1)) * 4);
     c.boff.ensure(((size_t)nbt + 2) * 4);
@@ -1125,253 +1174,306 @@ static msm_pending_t msm_run(lane_t& c, const aff_mem_t<F>* d_bases, const uint4
     c.start_b.ensure(((size_t)nbt + 1) * 4);
     // thread-count bounds per level: T_(r+1) <= T_r / S2 + nbt + 1 (fixed point ~ nbt * 64/63), plus slack
     const size_t slack = (size_t)nbt / 32 + 64;
-    const size_t T0_max = E_max / pl.S + nbt + 1 + slack;
-    const size_t T1_max = T0_max / pl.S2 + nbt + 1 + slack;
-    const bool ltail = msm_lazy_tail_on<F>();
-    pd.lazy = ltail;
-    c.part_a.ensure(T0_max * msm_partial_bytes<F>());
-    c.part_b.ensure(T1_max * msm_partial_bytes<F>());
-    const int K = pl.c - 1;  // bucket-index bits
-    const msm_tail_geom_t tg = msm_tail_geometry(pl, nwin, pd, mu ? (int)mu->K : 0);
+    L.T0_max = E_max / pl.S + nbt + 1 + slack;
+    L.T1_max = L.T0_max / pl.S2 + nbt + 1 + slack;
+    pd.lazy = L.ltail = msm_lazy_tail_on<F>();
+    c.part_a.ensure(L.T0_max * msm_partial_bytes<F>());
+    c.part_b.ensure(L.T1_max * msm_partial_bytes<F>());
+    L.tg = msm_tail_geometry(pl, nwin, pd, mu ? (int)mu->K : 0);
     if (mu && (size_t)pd.nplanes > mu->plane_capacity) throw hip_failure{hipErrorInvalidValue, "msm: plane staging of the fused group too small", __LINE__};
-    if (sink && (mu || sink->nbt != nbt)) throw hip_failure{hipErrorInvalidValue, "msm: bucket sink does not match the plan", __LINE__};
+    if (j.sink && (mu || j.sink->nbt != nbt)) throw hip_failure{hipErrorInvalidValue, "msm: bucket sink does not match the plan", __LINE__};
     c.planes.ensure((size_t)pd.nplanes * msm_partial_bytes<F>());
 
-    // 1. scalar read.  Wide windows: fused with the level-1 partition below (the digits never exist in memory); otherwise the
-    // stand-alone digit kernel writes the [rows][n] digit matrix.
-    const int fused_env = tuning().fused;
-    const bool fused = !mu && wide && fused_env && pl.c <= 22 && pl.Wd <= FUSED_MAX_ROWS;  // level-1 key of <= 7 bits: FUSED_G * 2^HB <= FUSED_THREADS
-    msm_digit_params_t dp;
-    memcpy(dp.bias, pl.bias, sizeof dp.bias);
-    dp.c = pl.c;
-    dp.W = pl.Wd;
-    dp.n = n;
-    dp.montgomery = scalars_montgomery;
-    if (!fused) {
-        phase_begin("msm_digits");
-        c.digits.ensure(E_max * (wide ? sizeof(uint32_t) : sizeof(uint16_t)));
-        size_t blocks = (n + 255) / 256;
-        if (mu)
-            hipLaunchKernelGGL(msm_digits_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mu->d_inst, mu->K, c.digits.as<uint16_t>(), dp);
-        if (blocks > 256 * 16) blocks = 256 * 16;
-        if (mu)
-            ;
-        else if (wide)
-            hipLaunchKernelGGL((msm_digits_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st, d_scalars, c.digits.as<uint32_t>(), dp);
-        else
-            hipLaunchKernelGGL((msm_digits_kernel<uint16_t>), dim3((unsigned)blocks), dim3(256), 0, st, d_scalars, c.digits.as<uint16_t>(), dp);
-        phase_end();
-        if (scalars_read) HIP_TRY(hipEventRecord(scalars_read, st));
-    }
-    int rounds = 0;
-    // see step 5; a fused multi-instance run never reads back either: its instances are small (<= 2^18 points each), so the
+    // level-1 key of <= 7 bits: FUSED_G * 2^HB <= FUSED_THREADS
+    L.fused = !mu && L.wide && tuning().fused && pl.c <= 22 && pl.Wd <= FUSED_MAX_ROWS;
+    memcpy(L.dp.bias, pl.bias, sizeof L.dp.bias);
+    L.dp.c = pl.c;
+    L.dp.W = pl.Wd;
+    L.dp.n = n;
+    L.dp.montgomery = j.scalars_montgomery;
+    // see msm_stage_accumulate; a fused multi-instance run never reads back either: its instances are small (<= 2^18 points each), so the
     // flattened-list fold takes whatever partial sums the accumulate grid leaves
-    const bool single_round = mu || (size_t)pl.Wd * n <= ((size_t)1 << 22);
-    const bool prefetch_ok = (size_t)pl.Wd * n <= ((size_t)1 << 22);  // one wave per SIMD: nothing else hides the gather
-    {
-        // ---- 2.-4. LDS-staged radix partition (msm_sort.hip.h) -> bucket-major `sorted` + boff; two levels, three when wide
-        msm_radix_params_t rp;
-        rp.n = n;
-        rp.c = pl.c;
-        rp.W = pl.W;
-        rp.J = pl.J;
-        // virtual indices = slots relative to vbase (msm_radix_params_t): the lower of the two base ranges, or the handle's table array
-        if (mu) {
-            rp.inst = mu->d_inst;
-            rp.ninst = mu->K;
-            rp.vstride = (uint32_t)mu->hn;
-        } else {
-            rp.vn0 = (uint32_t)n0;
-            rp.vr0 = (uint32_t)(d_bases - vbase);
-            rp.vr1 = (uint32_t)(vb1 - vbase);
-            rp.vstride = (uint32_t)table_stride;
-        }
-        const int LBL = K < 7 ? K : 7;  // key bits of the last level
-        rp.LB = wide ? 14 : LBL;        // bits left below the level-1 key
-        rp.HB = K - rp.LB;
-        rp.nb = pl.nb;
-        rp.xcd = (uint32_t)tuning().xcd;
-        rp.tiles_per_row = fused ? (uint32_t)((n + FUSED_TILE - 1) / FUSED_TILE) : (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
-        rp.TPW = (uint32_t)pl.J * rp.tiles_per_row;
-        const uint32_t B1 = 1u << rp.HB;
-        const uint32_t nbins = nwin * B1;
-        // single: W windows x B1 bins x TPW tiles; multi: the windows (instances) partition the J * npad / TILE tiles among themselves
-        const size_t ncounts1 = (size_t)(mu ? B1 : nbins) * rp.TPW;
-        const size_t tiles1 = (size_t)(mu ? 1 : pl.W) * rp.TPW;
-        const uint32_t nseg_last = wide ? nbins << 7 : nbins;  // segments feeding the last level
-        const size_t tiles2_max = E_max / SORT_TILE + nseg_last + 1;
-        c.counts.ensure(ncounts1 * 4);
-        c.offsets.ensure(ncounts1 * 4);
-        c.scan_tmp.ensure(scan_tmp_elems(ncounts1 > (size_t)nbt + 2 ? ncounts1 : (size_t)nbt + 2) * 4);
-        c.rv1.ensure(E_max * 4);
-        c.rl1.ensure(E_max * (wide ? 2 : 1));
-        c.rcounts2.ensure(tiles2_max * 128 * 4);
-        c.roff2.ensure(tiles2_max * 128 * 4);
-        c.rbinstart.ensure(((size_t)nbins + 2) * 4);
-        c.rntiles.ensure(((size_t)nseg_last + 2) * 4);
-        c.rtstart.ensure(((size_t)nseg_last + 2) * 4);
-        c.rbsize.ensure(((size_t)nbt + 3) * 4);
-        c.sorted.ensure(E_max * 4);
-        uint32_t* counts1 = c.counts.as<uint32_t>();
-        uint32_t* off1 = c.offsets.as<uint32_t>();
-        uint32_t* bsize = c.rbsize.as<uint32_t>();
-        uint32_t* d_max = bsize + nbt + 1;
-        uint32_t* boffp = c.boff.as<uint32_t>();
-        if (fused) {
-            // the scalar-read phase proper: a read-only pass over the scalars (32 B each) that leaves the level-1 histograms
-            const uint32_t ntiles = rp.tiles_per_row, keys = (uint32_t)pl.Wd * B1;
-            const uint32_t nchunks = (ntiles + FUSED_CHUNK - 1) / FUSED_CHUNK;
-            const size_t ngroups = (size_t)keys * nchunks;
-            c.counts.ensure((size_t)ntiles * keys * 4);
-            c.offsets.ensure((size_t)ntiles * keys * 4);
-            c.fchunk.ensure(2 * ngroups * 4);
-            c.scan_tmp.ensure(scan_tmp_elems(ngroups > (size_t)nbt + 2 ? ngroups : (size_t)nbt + 2) * 4);
-            counts1 = c.counts.as<uint32_t>();
-            off1 = c.offsets.as<uint32_t>();
-            uint32_t* csum = c.fchunk.as<uint32_t>();
-            uint32_t* choff = csum + ngroups;
-            phase_begin("msm_scalar_read");
-            const size_t hist_lds = (size_t)keys * 4;
-            // 1 024-thread workgroups with four private histogram copies (msm_sort.hip.h)
-#define SV_FUSED_HIST(CB)                                                                                                                         \
-    case CB:                                                                                                                                      \
-        hipLaunchKernelGGL((radix_hist1_wide_kernel<CB>), dim3(ntiles), dim3(HISTW_THREADS), hist_lds * HISTW_COPIES, st, d_scalars, counts1, rp, dp); \
-        break;
-            switch (pl.c) { SV_FUSED_HIST(17) SV_FUSED_HIST(18) SV_FUSED_HIST(19) SV_FUSED_HIST(20) SV_FUSED_HIST(21) SV_FUSED_HIST(22) }
-#undef SV_FUSED_HIST
-            phase_end();
-            phase_begin("msm_sort_level1");
-            const unsigned key_blocks = (keys + FUSED_THREADS - 1) / FUSED_THREADS;
-            hipLaunchKernelGGL(fused_chunk_sums_kernel, dim3(nchunks, key_blocks), dim3(FUSED_THREADS), 0, st, (const uint32_t*)counts1, csum, ntiles, nchunks, keys, B1,
-                               (uint32_t)pl.W, (uint32_t)pl.J);
-            exclusive_scan_u32(st, csum, choff, ngroups, c.scan_tmp.as<uint32_t>());
-            hipLaunchKernelGGL(fused_tile_offsets_kernel, dim3(nchunks, key_blocks), dim3(FUSED_THREADS), 0, st, (const uint32_t*)counts1, (const uint32_t*)choff,
-                               (const uint32_t*)csum, off1, c.rbinstart.as<uint32_t>(), ntiles, nchunks, keys, B1, (uint32_t)pl.W, (uint32_t)pl.J);
-#define SV_FUSED_SCATTER(CB)                                                                                                                      \
-    case CB:                                                                                                                                      \
-        hipLaunchKernelGGL((radix_scatter1_fused_kernel<CB>), dim3(ntiles), dim3(FUSED_THREADS), 0, st, d_scalars, (const uint32_t*)counts1,     \
-                           (const uint32_t*)off1, c.rv1.as<uint32_t>(), c.rl1.as<uint16_t>(), rp, dp);                                            \
-        break;
-            switch (pl.c) { SV_FUSED_SCATTER(17) SV_FUSED_SCATTER(18) SV_FUSED_SCATTER(19) SV_FUSED_SCATTER(20) SV_FUSED_SCATTER(21) SV_FUSED_SCATTER(22) }
-#undef SV_FUSED_SCATTER
-            if (scalars_read) HIP_TRY(hipEventRecord(scalars_read, st));
-        } else if (wide) {
-            phase_begin("msm_sort_level1");
-            hipLaunchKernelGGL((radix_hist1_kernel<uint32_t>), dim3((unsigned)tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint32_t>(), counts1, rp);
-            exclusive_scan_u32(st, counts1, off1, ncounts1, c.scan_tmp.as<uint32_t>());
-            hipLaunchKernelGGL((radix_scatter1_kernel<uint32_t, uint16_t>), dim3((unsigned)tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint32_t>(),
-                               counts1, off1, c.rv1.as<uint32_t>(), c.rl1.as<uint16_t>(), rp);
-        } else {
-            phase_begin("msm_sort_level1");
-            hipLaunchKernelGGL((radix_hist1_kernel<uint16_t>), dim3((unsigned)tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint16_t>(), counts1, rp);
-            exclusive_scan_u32(st, counts1, off1, ncounts1, c.scan_tmp.as<uint32_t>());
-            hipLaunchKernelGGL((radix_scatter1_kernel<uint16_t, uint8_t>), dim3((unsigned)tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint16_t>(),
-                               counts1, off1, c.rv1.as<uint32_t>(), c.rl1.as<uint8_t>(), rp);
-        }
-        if (mu)
-            hipLaunchKernelGGL(radix_bin_layout_multi_kernel, dim3((nbins + 1 + 255) / 256), dim3(256), 0, st, off1, counts1, ncounts1,
-                               c.rbinstart.as<uint32_t>(), nbins, rp);
-        else if (!fused)
-            hipLaunchKernelGGL(radix_bin_layout_kernel, dim3((nbins + 1 + 255) / 256), dim3(256), 0, st, off1, counts1, ncounts1, c.rbinstart.as<uint32_t>(),
-                               nbins, rp.TPW);
-        phase_end();
-        // one further level: items (v_in, rem_in) grouped in `nseg` segments -> grouped by (segment, next `bits` key bits)
-        auto tile_segments = [&](const uint32_t* seg_start, uint32_t nseg) {
-            hipLaunchKernelGGL(radix_bin_tiles_kernel, dim3((nseg + 1 + 255) / 256), dim3(256), 0, st, seg_start, c.rntiles.as<uint32_t>(), nseg);
-            exclusive_scan_u32(st, c.rntiles.as<uint32_t>(), c.rtstart.as<uint32_t>(), (size_t)nseg + 1, c.scan_tmp.as<uint32_t>());
-        };
-        // per (segment, key): exclusive prefix of the tile counts + group sizes; few big segments -> one workgroup per segment
-        auto colscan = [&](uint32_t* sizes, uint32_t nsegs, int bits, uint32_t* dmax) {
-            if (nsegs <= 4096)
-                hipLaunchKernelGGL(radix_colscan2_seg_kernel, dim3(nsegs), dim3(1024), 0, st, c.rcounts2.as<uint32_t>(), c.roff2.as<uint32_t>(),
-                                   c.rtstart.as<uint32_t>(), sizes, nsegs, bits, dmax);
-            else
-                hipLaunchKernelGGL(radix_colscan2_kernel, dim3(((nsegs << bits) + 1 + 255) / 256), dim3(256), 0, st, c.rcounts2.as<uint32_t>(),
-                                   c.roff2.as<uint32_t>(), c.rtstart.as<uint32_t>(), sizes, nsegs, bits, dmax);
-        };
-        const uint32_t* seg_start = c.rbinstart.as<uint32_t>();
-        uint32_t nseg = nbins;
-        const uint32_t* v_in = c.rv1.as<uint32_t>();
-        if (wide) {
-            phase_begin("msm_sort_level2");
-            const uint32_t ngroups = nseg << 7;
-            const size_t tmax = E_max / SORT_TILE + nseg + 1;
-            c.rv2.ensure(E_max * 4);
-            c.rl2.ensure(E_max);
-            c.rmid_size.ensure(((size_t)ngroups + 3) * 4);
-            c.rmid_boff.ensure(((size_t)ngroups + 3) * 4);
-            c.scan_tmp.ensure(scan_tmp_elems((size_t)ngroups + 2) * 4);
-            uint32_t* msize = c.rmid_size.as<uint32_t>();
-            uint32_t* mboff = c.rmid_boff.as<uint32_t>();
-            tile_segments(seg_start, nseg);
-            hipLaunchKernelGGL((radix_hist2_kernel<uint16_t>), dim3((unsigned)tmax), dim3(SORT_THREADS), 0, st, c.rl1.as<uint16_t>(), seg_start,
-                               c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), nseg, 7, 7);
-            HIP_TRY(hipMemsetAsync(msize + ngroups + 1, 0, 4, st));
-            colscan(msize, nseg, 7, msize + ngroups + 1);
-            exclusive_scan_u32(st, msize, mboff, (size_t)ngroups + 1, c.scan_tmp.as<uint32_t>());
-            hipLaunchKernelGGL((radix_scatter2_kernel<uint16_t, uint8_t>), dim3((unsigned)tmax), dim3(SORT_THREADS), 0, st, v_in, c.rl1.as<uint16_t>(),
-                               seg_start, c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), c.roff2.as<uint32_t>(), mboff, c.rv2.as<uint32_t>(),
-                               c.rl2.as<uint8_t>(), nseg, 7, 7, (uint32_t)tuning().xcd);
-            phase_end();
-            seg_start = mboff;
-            nseg = ngroups;
-            v_in = c.rv2.as<uint32_t>();
-        }
-        phase_begin(wide ? "msm_sort_level3" : "msm_sort_level2");
-        tile_segments(seg_start, nseg);
-        const uint8_t* rem_last = wide ? c.rl2.as<uint8_t>() : c.rl1.as<uint8_t>();
-        hipLaunchKernelGGL((radix_hist2_kernel<uint8_t>), dim3((unsigned)tiles2_max), dim3(SORT_THREADS), 0, st, rem_last, seg_start,
-                           c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), nseg, LBL, 0);
-        HIP_TRY(hipMemsetAsync(d_max, 0, 4, st));
-        colscan(bsize, nseg, LBL, d_max);
-        exclusive_scan_u32(st, bsize, boffp, (size_t)nbt + 1, c.scan_tmp.as<uint32_t>());
-        hipLaunchKernelGGL((radix_scatter2_kernel<uint8_t, uint8_t>), dim3((unsigned)tiles2_max), dim3(SORT_THREADS), 0, st, v_in, rem_last, seg_start,
-                           c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), c.roff2.as<uint32_t>(), boffp, c.sorted.as<uint32_t>(),
-                           (uint8_t*)nullptr, nseg, LBL, 0, (uint32_t)tuning().xcd);
-        phase_end();
-        // A single-round MSM (<= 2^22 digit entries: at most 2^16 accumulate threads) leaves at most 2^16 + nbt partial sums
-        // whatever the scalars are, and the tail kernels walk them position by position (msm.hip.h 7a/7b): no reduce round.
-        // Bigger MSMs run a FIXED number of reduce rounds (round 4: ONE round that shrinks a bucket's partial sums 16x; rounds 2-3: two of 8x) before the fold reads
-        // them twice - what uniform scalars need anyway (the top digit row of a 253-bit scalar fills only 2^(253 mod c) buckets,
-        // thousands of entries each) - and the flattened-list fold takes whatever is left of a heavier bucket (all scalars
-        // equal at 2^24: 2 048 partial sums in one bucket, 32 additions per lane of its row and column).  Nothing is read back:
-        // an MSM of any size is one uninterrupted enqueue (round 2 sized the rounds by the largest bucket: a 4-byte copy and
-        // a stream synchronisation between sort and accumulate).
-        // ---- 5. accumulate
-        phase_begin("msm_accumulate");
-        {
-            // a bucket of s entries is touched by at most (s - 1) / S + 2 segment threads
-            const int env_rounds = tuning().reduce_rounds;
-            if (!single_round) rounds = env_rounds < 0 ? 0 : (env_rounds > 8 ? 8 : env_rounds);
-            // fused groups: optional reduce rounds (tuning fuse_reduce).  They bound what one fold workgroup can meet when an instance's
-            // scalars are all equal (a 2^18-pair instance then leaves ~70 000 partial sums in ONE bucket: 1 100 dependent additions per
-            // lane of its row) at the price of one more pass over the partial sums of well-behaved instances.
-            if (mu && tuning().fuse_reduce > 0) rounds = tuning().fuse_reduce > 4 ? 4 : tuning().fuse_reduce;
-            if (mu && tuning().fuse_reduce < 0) rounds = mu->K >= 8 ? 1 : 0;
-            hipLaunchKernelGGL(msm_alloc_seg_kernel, dim3((nbt + 1 + 255) / 256), dim3(256), 0, st, boffp, c.cnt_a.as<uint32_t>(), nbt, pl.S);
-            exclusive_scan_u32(st, c.cnt_a.as<uint32_t>(), c.start_a.as<uint32_t>(), (size_t)nbt + 1, c.scan_tmp.as<uint32_t>());
-            msm_launch_accumulate<F>(c, pl, vbase, boffp, nbt, (E_max + pl.S - 1) / pl.S, single_round && prefetch_ok, ltail);
-        }
-        phase_end();
+    L.single_round = mu || (size_t)pl.Wd * n <= ((size_t)1 << 22);
+    L.prefetch_ok = (size_t)pl.Wd * n <= ((size_t)1 << 22);  // one wave per SIMD: nothing else hides the gather
+
+    msm_radix_params_t& rp = L.rp;
+    rp.n = n;
+    rp.c = pl.c;
+    rp.W = pl.W;
+    rp.J = pl.J;
+    // virtual indices = slots relative to vbase (msm_radix_params_t): the lower of the two base ranges, or the handle's table array
+    if (mu) {
+        rp.inst = mu->d_inst;
+        rp.ninst = mu->K;
+        rp.vstride = (uint32_t)mu->hn;
+    } else {
+        rp.vn0 = (uint32_t)n0;
+        rp.vr0 = (uint32_t)(j.bases - L.vbase);
+        rp.vr1 = (uint32_t)(vb1 - L.vbase);
+        rp.vstride = (uint32_t)j.table_stride;
     }
-    // 6.-9. reduce rounds, then the bucket merge (a chunk of a bigger MSM) or fold -> bit-plane sums -> (host) Horner: on the lazy arithmetic
-    // when the accumulate kernel left raw partial sums (G1, tuning lazy_tail), else on F's exact arithmetic
+    const int K = pl.c - 1;           // bucket-index bits
+    L.LBL = K < 7 ? K : 7;            // key bits of the last level
+    rp.LB = L.wide ? 14 : L.LBL;      // bits left below the level-1 key
+    rp.HB = K - rp.LB;
+    rp.nb = pl.nb;
+    rp.xcd = (uint32_t)tuning().xcd;
+    rp.tiles_per_row = L.fused ? (uint32_t)((n + FUSED_TILE - 1) / FUSED_TILE) : (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+    rp.TPW = (uint32_t)pl.J * rp.tiles_per_row;
+    L.B1 = 1u << rp.HB;
+    L.nbins = nwin * L.B1;
+    // single: W windows x B1 bins x TPW tiles; multi: the windows (instances) partition the J * npad / TILE tiles among themselves
+    L.ncounts1 = (size_t)(mu ? L.B1 : L.nbins) * rp.TPW;
+    L.tiles1 = (size_t)(mu ? 1 : pl.W) * rp.TPW;
+    L.nseg_last = L.wide ? L.nbins << 7 : L.nbins;
+    L.tiles2_max = E_max / SORT_TILE + L.nseg_last + 1;
+    return L;
+}
+// 1. scalar read, unless the level-1 partition does it (L.fused): the stand-alone digit kernel writes the [rows][n] digit matrix.
+template <class F>
+static void msm_stage_digits(lane_t& c, const msm_layout_t<F>& L, const msm_job_t<F>& j, msm_phases_t& ph) {
+    hipStream_t st = c.stream;
+    ph.begin("msm_digits");
+    c.digits.ensure(L.E_max * (L.wide ? sizeof(uint32_t) : sizeof(uint16_t)));
+    size_t blocks = (j.n + 255) / 256;
+    if (j.multi) {
+        hipLaunchKernelGGL(msm_digits_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, st, j.multi->d_inst, j.multi->K, c.digits.as<uint16_t>(), L.dp);
+    } else {
+        if (blocks > 256 * 16) blocks = 256 * 16;
+        if (L.wide)
+            hipLaunchKernelGGL((msm_digits_kernel<uint32_t>), dim3((unsigned)blocks), dim3(256), 0, st, j.scalars, c.digits.as<uint32_t>(), L.dp);
+        else
+            hipLaunchKernelGGL((msm_digits_kernel<uint16_t>), dim3((unsigned)blocks), dim3(256), 0, st, j.scalars, c.digits.as<uint16_t>(), L.dp);
+    }
+    ph.end();
+    if (j.scalars_read) HIP_TRY(hipEventRecord(j.scalars_read, st));
+}
+// fn(std::integral_constant<int, c>) for the window widths the fused level-1 kernels exist for
+template <class Fn>
+static void msm_fused_width(int c, Fn&& fn) {
+    switch (c) {
+        case 17: return fn(std::integral_constant<int, 17>{});
+        case 18: return fn(std::integral_constant<int, 18>{});
+        case 19: return fn(std::integral_constant<int, 19>{});
+        case 20: return fn(std::integral_constant<int, 20>{});
+        case 21: return fn(std::integral_constant<int, 21>{});
+        case 22: return fn(std::integral_constant<int, 22>{});
+    }
+}
+// 1. + 2. wide windows: the scalar-read phase proper - a read-only pass over the scalars (32 B each) that leaves the level-1 histograms - then the
+// level-1 scatter reads them again and writes (v1, rem1); the digits never exist in memory
+template <class F>
+static void msm_stage_level1_fused(lane_t& c, const msm_layout_t<F>& L, const msm_job_t<F>& j, msm_phases_t& ph) {
+    hipStream_t st = c.stream;
+    const msm_plan_t& pl = L.pl;
+    const uint32_t ntiles = L.rp.tiles_per_row, keys = (uint32_t)pl.Wd * L.B1;
+    const uint32_t nchunks = (ntiles + FUSED_CHUNK - 1) / FUSED_CHUNK;
+    const size_t ngroups = (size_t)keys * nchunks;
+    c.counts.ensure((size_t)ntiles * keys * 4);
+    c.offsets.ensure((size_t)ntiles * keys * 4);
+    c.fchunk.ensure(2 * ngroups * 4);
+    c.scan_tmp.ensure(scan_tmp_elems(ngroups > (size_t)L.nbt + 2 ? ngroups : (size_t)L.nbt + 2) * 4);
+    uint32_t* counts1 = c.counts.as<uint32_t>();
+    uint32_t* off1 = c.offsets.as<uint32_t>();
+    uint32_t* csum = c.fchunk.as<uint32_t>();
+    uint32_t* choff = csum + ngroups;
+    ph.begin("msm_scalar_read");
+    const size_t hist_lds = (size_t)keys * 4;
+    // 1 024-thread workgroups with four private histogram copies (msm_sort.hip.h)
+    msm_fused_width(pl.c, [&](auto cb) {
+        hipLaunchKernelGGL((radix_hist1_wide_kernel<decltype(cb)::value>), dim3(ntiles), dim3(HISTW_THREADS), hist_lds * HISTW_COPIES, st, j.scalars, counts1, L.rp, L.dp);
+    });
+    ph.end();
+    ph.begin("msm_sort_level1");
+    const unsigned key_blocks = (keys + FUSED_THREADS - 1) / FUSED_THREADS;
+    hipLaunchKernelGGL(fused_chunk_sums_kernel, dim3(nchunks, key_blocks), dim3(FUSED_THREADS), 0, st, (const uint32_t*)counts1, csum, ntiles, nchunks, keys, L.B1,
+                       (uint32_t)pl.W, (uint32_t)pl.J);
+    exclusive_scan_u32(st, csum, choff, ngroups, c.scan_tmp.as<uint32_t>());
+    hipLaunchKernelGGL(fused_tile_offsets_kernel, dim3(nchunks, key_blocks), dim3(FUSED_THREADS), 0, st, (const uint32_t*)counts1, (const uint32_t*)choff,
+                       (const uint32_t*)csum, off1, c.rbinstart.as<uint32_t>(), ntiles, nchunks, keys, L.B1, (uint32_t)pl.W, (uint32_t)pl.J);
+    msm_fused_width(pl.c, [&](auto cb) {
+        hipLaunchKernelGGL((radix_scatter1_fused_kernel<decltype(cb)::value>), dim3(ntiles), dim3(FUSED_THREADS), 0, st, j.scalars, (const uint32_t*)counts1,
+                           (const uint32_t*)off1, c.rv1.as<uint32_t>(), c.rl1.as<uint16_t>(), L.rp, L.dp);
+    });
+    if (j.scalars_read) HIP_TRY(hipEventRecord(j.scalars_read, st));
+    ph.end();
+}
+// 2. LDS-staged radix partition (msm_sort.hip.h), level 1: the workspace of the whole sort, then the entries grouped by the top key bits
+// (v1, rem1) and the bin layout rbinstart
+template <class F>
+static void msm_stage_level1(lane_t& c, const msm_layout_t<F>& L, const msm_job_t<F>& j, msm_phases_t& ph) {
+    hipStream_t st = c.stream;
+    c.counts.ensure(L.ncounts1 * 4);
+    c.offsets.ensure(L.ncounts1 * 4);
+    c.scan_tmp.ensure(scan_tmp_elems(L.ncounts1 > (size_t)L.nbt + 2 ? L.ncounts1 : (size_t)L.nbt + 2) * 4);
+    c.rv1.ensure(L.E_max * 4);
+    c.rl1.ensure(L.E_max * (L.wide ? 2 : 1));
+    c.rcounts2.ensure(L.tiles2_max * 128 * 4);
+    c.roff2.ensure(L.tiles2_max * 128 * 4);
+    c.rbinstart.ensure(((size_t)L.nbins + 2) * 4);
+    c.rntiles.ensure(((size_t)L.nseg_last + 2) * 4);
+    c.rtstart.ensure(((size_t)L.nseg_last + 2) * 4);
+    c.rbsize.ensure(((size_t)L.nbt + 3) * 4);
+    c.sorted.ensure(L.E_max * 4);
+    if (L.fused) return msm_stage_level1_fused(c, L, j, ph);
+    uint32_t* counts1 = c.counts.as<uint32_t>();
+    uint32_t* off1 = c.offsets.as<uint32_t>();
+    ph.begin("msm_sort_level1");
+    if (L.wide) {
+        hipLaunchKernelGGL((radix_hist1_kernel<uint32_t>), dim3((unsigned)L.tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint32_t>(), counts1, L.rp);
+        exclusive_scan_u32(st, counts1, off1, L.ncounts1, c.scan_tmp.as<uint32_t>());
+        hipLaunchKernelGGL((radix_scatter1_kernel<uint32_t, uint16_t>), dim3((unsigned)L.tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint32_t>(),
+                           counts1, off1, c.rv1.as<uint32_t>(), c.rl1.as<uint16_t>(), L.rp);
+    } else {
+        hipLaunchKernelGGL((radix_hist1_kernel<uint16_t>), dim3((unsigned)L.tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint16_t>(), counts1, L.rp);
+        exclusive_scan_u32(st, counts1, off1, L.ncounts1, c.scan_tmp.as<uint32_t>());
+        hipLaunchKernelGGL((radix_scatter1_kernel<uint16_t, uint8_t>), dim3((unsigned)L.tiles1), dim3(SORT_THREADS), 0, st, c.digits.as<uint16_t>(),
+                           counts1, off1, c.rv1.as<uint32_t>(), c.rl1.as<uint8_t>(), L.rp);
+    }
+    if (j.multi)
+        hipLaunchKernelGGL(radix_bin_layout_multi_kernel, dim3((L.nbins + 1 + 255) / 256), dim3(256), 0, st, off1, counts1, L.ncounts1,
+                           c.rbinstart.as<uint32_t>(), L.nbins, L.rp);
+    else
+        hipLaunchKernelGGL(radix_bin_layout_kernel, dim3((L.nbins + 1 + 255) / 256), dim3(256), 0, st, off1, counts1, L.ncounts1, c.rbinstart.as<uint32_t>(),
+                           L.nbins, L.rp.TPW);
+    ph.end();
+}
+// one further level: items grouped in `nseg` segments -> their tiles (rntiles, rtstart)
+static void msm_tile_segments(lane_t& c, const uint32_t* seg_start, uint32_t nseg) {
+    hipLaunchKernelGGL(radix_bin_tiles_kernel, dim3((nseg + 1 + 255) / 256), dim3(256), 0, c.stream, seg_start, c.rntiles.as<uint32_t>(), nseg);
+    exclusive_scan_u32(c.stream, c.rntiles.as<uint32_t>(), c.rtstart.as<uint32_t>(), (size_t)nseg + 1, c.scan_tmp.as<uint32_t>());
+}
+// per (segment, key): exclusive prefix of the tile counts + group sizes; few big segments -> one workgroup per segment
+static void msm_colscan(lane_t& c, uint32_t* sizes, uint32_t nsegs, int bits, uint32_t* dmax) {
+    if (nsegs <= 4096)
+        hipLaunchKernelGGL(radix_colscan2_seg_kernel, dim3(nsegs), dim3(1024), 0, c.stream, c.rcounts2.as<uint32_t>(), c.roff2.as<uint32_t>(),
+                           c.rtstart.as<uint32_t>(), sizes, nsegs, bits, dmax);
+    else
+        hipLaunchKernelGGL(radix_colscan2_kernel, dim3(((nsegs << bits) + 1 + 255) / 256), dim3(256), 0, c.stream, c.rcounts2.as<uint32_t>(),
+                           c.roff2.as<uint32_t>(), c.rtstart.as<uint32_t>(), sizes, nsegs, bits, dmax);
+}
+// 3.-4. the further levels: items (v_in, rem_in) grouped in `nseg` segments -> grouped by (segment, next key bits); wide windows take a middle
+// level of 7 bits first.  Leaves the bucket-major `sorted` and the bucket offsets boff.
+template <class F>
+static void msm_stage_sort_rest(lane_t& c, const msm_layout_t<F>& L, msm_phases_t& ph) {
+    hipStream_t st = c.stream;
+    const size_t E_max = L.E_max;
+    const uint32_t nbt = L.nbt;
+    uint32_t* bsize = c.rbsize.as<uint32_t>();
+    uint32_t* d_max = bsize + nbt + 1;
+    uint32_t* boffp = c.boff.as<uint32_t>();
+    const uint32_t* seg_start = c.rbinstart.as<uint32_t>();
+    uint32_t nseg = L.nbins;
+    const uint32_t* v_in = c.rv1.as<uint32_t>();
+    if (L.wide) {
+        ph.begin("msm_sort_level2");
+        const uint32_t ngroups = nseg << 7;
+        const size_t tmax = E_max / SORT_TILE + nseg + 1;
+        c.rv2.ensure(E_max * 4);
+        c.rl2.ensure(E_max);
+        c.rmid_size.ensure(((size_t)ngroups + 3) * 4);
+        c.rmid_boff.ensure(((size_t)ngroups + 3) * 4);
+        c.scan_tmp.ensure(scan_tmp_elems((size_t)ngroups + 2) * 4);
+        uint32_t* msize = c.rmid_size.as<uint32_t>();
+        uint32_t* mboff = c.rmid_boff.as<uint32_t>();
+        msm_tile_segments(c, seg_start, nseg);
+        hipLaunchKernelGGL((radix_hist2_kernel<uint16_t>), dim3((unsigned)tmax), dim3(SORT_THREADS), 0, st, c.rl1.as<uint16_t>(), seg_start,
+                           c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), nseg, 7, 7);
+        HIP_TRY(hipMemsetAsync(msize + ngroups + 1, 0, 4, st));
+        msm_colscan(c, msize, nseg, 7, msize + ngroups + 1);
+        exclusive_scan_u32(st, msize, mboff, (size_t)ngroups + 1, c.scan_tmp.as<uint32_t>());
+        hipLaunchKernelGGL((radix_scatter2_kernel<uint16_t, uint8_t>), dim3((unsigned)tmax), dim3(SORT_THREADS), 0, st, v_in, c.rl1.as<uint16_t>(),
+                           seg_start, c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), c.roff2.as<uint32_t>(), mboff, c.rv2.as<uint32_t>(),
+                           c.rl2.as<uint8_t>(), nseg, 7, 7, (uint32_t)tuning().xcd);
+        ph.end();
+        seg_start = mboff;
+        nseg = ngroups;
+        v_in = c.rv2.as<uint32_t>();
+    }
+    ph.begin(L.wide ? "msm_sort_level3" : "msm_sort_level2");
+    msm_tile_segments(c, seg_start, nseg);
+    const uint8_t* rem_last = L.wide ? c.rl2.as<uint8_t>() : c.rl1.as<uint8_t>();
+    hipLaunchKernelGGL((radix_hist2_kernel<uint8_t>), dim3((unsigned)L.tiles2_max), dim3(SORT_THREADS), 0, st, rem_last, seg_start,
+                       c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), nseg, L.LBL, 0);
+    HIP_TRY(hipMemsetAsync(d_max, 0, 4, st));
+    msm_colscan(c, bsize, nseg, L.LBL, d_max);
+    exclusive_scan_u32(st, bsize, boffp, (size_t)nbt + 1, c.scan_tmp.as<uint32_t>());
+    hipLaunchKernelGGL((radix_scatter2_kernel<uint8_t, uint8_t>), dim3((unsigned)L.tiles2_max), dim3(SORT_THREADS), 0, st, v_in, rem_last, seg_start,
+                       c.rtstart.as<uint32_t>(), c.rcounts2.as<uint32_t>(), c.roff2.as<uint32_t>(), boffp, c.sorted.as<uint32_t>(),
+                       (uint8_t*)nullptr, nseg, L.LBL, 0, (uint32_t)tuning().xcd);
+    ph.end();
+}
+// 5. accumulate; returns the number of reduce rounds the tail runs in front of the fold.
+// A single-round MSM (<= 2^22 digit entries: at most 2^16 accumulate threads) leaves at most 2^16 + nbt partial sums
+// whatever the scalars are, and the tail kernels walk them position by position (msm.hip.h 7a/7b): no reduce round.
+// Bigger MSMs run a FIXED number of reduce rounds (round 4: ONE round that shrinks a bucket's partial sums 16x; rounds 2-3: two of 8x) before the fold reads
+// them twice - what uniform scalars need anyway (the top digit row of a 253-bit scalar fills only 2^(253 mod c) buckets,
+// thousands of entries each) - and the flattened-list fold takes whatever is left of a heavier bucket (all scalars
+// equal at 2^24: 2 048 partial sums in one bucket, 32 additions per lane of its row and column).  Nothing is read back:
+// an MSM of any size is one uninterrupted enqueue (round 2 sized the rounds by the largest bucket: a 4-byte copy and
+// a stream synchronisation between sort and accumulate).
+template <class F>
+static int msm_stage_accumulate(lane_t& c, const msm_layout_t<F>& L, const msm_job_t<F>& j, msm_phases_t& ph) {
+    hipStream_t st = c.stream;
+    const msm_multi_t* mu = j.multi;
+    const uint32_t nbt = L.nbt;
+    uint32_t* boffp = c.boff.as<uint32_t>();
+    int rounds = 0;
+    ph.begin("msm_accumulate");
+    // a bucket of s entries is touched by at most (s - 1) / S + 2 segment threads
+    const int env_rounds = tuning().reduce_rounds;
+    if (!L.single_round) rounds = env_rounds < 0 ? 0 : (env_rounds > 8 ? 8 : env_rounds);
+    // fused groups: optional reduce rounds (tuning fuse_reduce).  They bound what one fold workgroup can meet when an instance's
+    // scalars are all equal (a 2^18-pair instance then leaves ~70 000 partial sums in ONE bucket: 1 100 dependent additions per
+    // lane of its row) at the price of one more pass over the partial sums of well-behaved instances.
+    if (mu && tuning().fuse_reduce > 0) rounds = tuning().fuse_reduce > 4 ? 4 : tuning().fuse_reduce;
+    if (mu && tuning().fuse_reduce < 0) rounds = mu->K >= 8 ? 1 : 0;
+    hipLaunchKernelGGL(msm_alloc_seg_kernel, dim3((nbt + 1 + 255) / 256), dim3(256), 0, st, boffp, c.cnt_a.as<uint32_t>(), nbt, L.pl.S);
+    exclusive_scan_u32(st, c.cnt_a.as<uint32_t>(), c.start_a.as<uint32_t>(), (size_t)nbt + 1, c.scan_tmp.as<uint32_t>());
+    msm_launch_accumulate<F>(c, L.pl, L.vbase, boffp, nbt, (L.E_max + L.pl.S - 1) / L.pl.S, L.single_round && L.prefetch_ok, L.ltail);
+    ph.end();
+    return rounds;
+}
+template <class T>
+struct msm_field_tag {
+    using type = T;
+};
+// fn(msm_field_tag<T>) for the arithmetic T the tail of an MSM over F runs on: fqz_t when a G1 accumulate kernel left raw lazy partial sums
+// (`lazy`: tuning lazy_tail), else F's exact arithmetic
+template <class F, class Fn>
+static void msm_on_tail_field(bool lazy, Fn&& fn) {
     if constexpr (sizeof(F) == sizeof(fq_t)) {
-        if (ltail) {
-            msm_reduce_and_tail<fqz_t>(c, pl, tg, nwin, nbt, rounds, T0_max, T1_max, sink, pd, host_planes, phase_begin, phase_end);
-            return pd;
-        }
+        if (lazy) return fn(msm_field_tag<fqz_t>{});
     }
-    msm_reduce_and_tail<F>(c, pl, tg, nwin, nbt, rounds, T0_max, T1_max, sink, pd, host_planes, phase_begin, phase_end);
+    fn(msm_field_tag<F>{});
+}
+// Device side of one MSM on lane `c`.  Everything is enqueued on the lane's stream, ending with the copy of the bit-plane sums into
+// j.host_planes; the caller synchronises the stream and runs msm_collect / msm_accum_t::finish.  The steps, by number:
+// 1. msm_stage_digits (or fused into 2.), 2. msm_stage_level1, 3.-4. msm_stage_sort_rest, 5. msm_stage_accumulate, 6.-9. msm_reduce_and_tail.
+template <class F>
+static msm_pending_t msm_run(lane_t& c, const msm_job_t<F>& j) {
+    msm_pending_t pd;
+    pd.planes = j.host_planes;
+    if (j.n == 0) return pd;  // no planes: the sum is the point at infinity
+    msm_phases_t ph{c, j.profile, msm_trace_level(), j.n};
+    const msm_layout_t<F> L = msm_layout(c, j, pd);
+    if (!L.fused) msm_stage_digits(c, L, j, ph);
+    msm_stage_level1(c, L, j, ph);
+    msm_stage_sort_rest(c, L, ph);
+    const int rounds = msm_stage_accumulate(c, L, j, ph);
+    // 6.-9. reduce rounds, then the bucket merge (a chunk of a bigger MSM) or fold -> bit-plane sums -> (host) Horner
+    msm_on_tail_field<F>(L.ltail, [&](auto t) {
+        msm_reduce_and_tail<typename decltype(t)::type>(c, L.pl, L.tg, L.nwin, L.nbt, rounds, L.T0_max, L.T1_max, j.sink, pd, j.host_planes, ph);
+    });
     return pd;
 }
-// The tail of a chunked MSM: fold + bit planes over the bucket sink (every bucket holds L partial sums, one per lane).
+// The tail of a chunked MSM: fold + bit planes over the bucket sink (every bucket holds L partial sums, one per lane).  Of the job it reads what the chunks'
+// plan came from - n (the largest chunk), window_bits, tables, table_bits - and host_planes.
 template <class F>
-static msm_pending_t msm_tail_from_sink(lane_t& c, size_t chunk_n, int window_bits, const msm_bucket_sink_t& sink, void* host_planes, int tables = 1,
-                                        int table_bits = 0) {
+static msm_pending_t msm_tail_from_sink(lane_t& c, const msm_job_t<F>& j, const msm_bucket_sink_t& sink) {
     msm_pending_t pd;
-    pd.planes = host_planes;
-    const msm_plan_t pl = msm_make_plan(chunk_n, window_bits, tables, table_bits);
+    pd.planes = j.host_planes;
+    const msm_plan_t pl = msm_make_plan(j.n, j.window_bits, j.tables, j.table_bits);
     const uint32_t nwin = (uint32_t)pl.W, nbt = nwin * pl.nb;
     if (nbt != sink.nbt) throw hip_failure{hipErrorInvalidValue, "msm: bucket sink does not match the plan", __LINE__};
     const msm_tail_geom_t tg = msm_tail_geometry(pl, nwin, pd, 0);
@@ -1380,27 +1482,23 @@ static msm_pending_t msm_tail_from_sink(lane_t& c, size_t chunk_n, int window_bi
     hipLaunchKernelGGL(msm_sink_lists_kernel, dim3((nbt + 1 + 255) / 256), dim3(256), 0, c.stream, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), nbt, sink.L);
     pd.lazy = msm_lazy_tail_on<F>();  // the sink holds what the chunks' merges left: raw lazy points then
     c.phase_begin("msm_bucket_reduce");
-    if constexpr (sizeof(F) == sizeof(fq_t)) {
-        if (pd.lazy) {
-            msm_tail_launch<fqz_t>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<fqz_t>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), pd, host_planes);
-            c.phase_end();
-            return pd;
-        }
-    }
-    msm_tail_launch<F>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<F>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), pd, host_planes);
+    msm_on_tail_field<F>(pd.lazy, [&](auto t) {
+        using T = typename decltype(t)::type;
+        msm_tail_launch<T>(c, pl, tg, nwin, nbt, (const xyzz_mem_t<T>*)sink.acc, c.start_a.as<uint32_t>(), c.cnt_a.as<uint32_t>(), pd, j.host_planes);
+    });
     c.phase_end();
     return pd;
 }
-// synchronous single MSM: run, wait, finish on the host into `out` (Jacobian memory image)
+// synchronous single MSM: run, wait, finish on the host into `out` (Jacobian memory image); the planes are staged in the lane's pinned block
 template <class F>
-static void msm_run_sync(lane_t& c, const aff_mem_t<F>* d_bases, const uint4* d_scalars, size_t n, void* out, int window_bits,
-                         const aff_mem_t<F>* d_bases1 = nullptr, size_t n0 = ~(size_t)0, int scalars_montgomery = 0, int tables = 1,
-                         size_t table_stride = 0, int table_bits = 0) {
+static void msm_run_sync(lane_t& c, const msm_job_t<F>& j, void* out) {
     // A lane borrowed from the calling thread's scope: MSMs the scope enqueued on it (in-stream, or with no further lane free) keep their bit planes in
     // `pin` from offset 0 until the scope's flush has read them - this call stages at offset 0 too (and ensure() may move the block): deliver them first.
     if (c.in_scope && c.pin_used) scope_flush();
     c.pin.ensure(msm_plane_bytes<F>());
-    const msm_pending_t pd = msm_run<F>(c, d_bases, d_scalars, n, c.pin.p, window_bits, d_bases1, n0, scalars_montgomery, tables, table_stride, true, table_bits);
+    msm_job_t<F> staged = j;
+    staged.host_planes = c.pin.p;
+    const msm_pending_t pd = msm_run<F>(c, staged);
     HIP_TRY(hipStreamSynchronize(c.stream));
     const double t0 = host_now_ms();
     msm_accum_t<F>* acc = new msm_accum_t<F>();
@@ -1675,9 +1773,15 @@ static void msm_host_chunked(void* out, const void* points, size_t npoints, cons
             if (prof) c.phase_end();
             msm_bucket_sink_t mine_sink = sink;
             mine_sink.slot = (uint32_t)(j % L);
-            const msm_pending_t pd = msm_run<F>(c, c.bases_tmp.template as<aff_mem_t<F>>(), c.scalars_tmp.template as<uint4>(), chunk_cnt(j),
-                                                c.pin.template as<uint8_t>() + (use_sink ? 0 : slot * (j / L)), chunk_c, nullptr, ~(size_t)0, 0, 1, 0, prof, 0, nullptr,
-                                                use_sink ? &mine_sink : nullptr);
+            msm_job_t<F> job;
+            job.bases = c.bases_tmp.template as<aff_mem_t<F>>();
+            job.scalars = c.scalars_tmp.template as<uint4>();
+            job.n = chunk_cnt(j);
+            job.window_bits = chunk_c;
+            job.host_planes = c.pin.template as<uint8_t>() + (use_sink ? 0 : slot * (j / L));
+            job.profile = prof;
+            job.sink = use_sink ? &mine_sink : nullptr;
+            const msm_pending_t pd = msm_run<F>(c, job);
             if (!use_sink) pend[j] = pd;
         };
         if (mine.size() == 1) {
@@ -1696,7 +1800,11 @@ static void msm_host_chunked(void* out, const void* points, size_t npoints, cons
                 HIP_TRY(hipEventRecord(e, lg.lanes[l]->stream));
                 HIP_TRY(hipStreamWaitEvent(c0.stream, e, 0));
             }
-            pend[0] = msm_tail_from_sink<F>(c0, max_cnt, chunk_c, sink, c0.pin.p);
+            msm_job_t<F> tail;  // the chunks' plan: the largest chunk, no tables
+            tail.n = max_cnt;
+            tail.window_bits = chunk_c;
+            tail.host_planes = c0.pin.p;
+            pend[0] = msm_tail_from_sink<F>(c0, tail, sink);
         }
         for (int l = 0; l < L; l++) {
             HIP_TRY(hipStreamSynchronize(lg.lanes[l]->alt));
@@ -1738,6 +1846,19 @@ struct msm_req_t {
     const void* scalars = nullptr;
     void* out = nullptr;
 };
+// A job over registered bases: its bases group - request r's ranges on logical device `dev`, the handle's tables - and n = n0 + n1.
+template <class F>
+static msm_job_t<F> msm_handle_job(const bases_handle_t<F>& h, int dev, const msm_req_t& r) {
+    msm_job_t<F> j;
+    j.bases = h.d[dev] + r.off0;
+    j.bases1 = r.n1 ? h.d[dev] + r.off1 : nullptr;
+    j.n0 = r.n0;
+    j.tables = h.tables;
+    j.table_stride = h.n;
+    j.table_bits = h.table_bits;
+    j.n = r.n0 + r.n1;
+    return j;
+}
 // fn(i) for i < n on up to `max_threads` host threads (the calling thread is one of them).  Used for the Horner finishes of a fused
 // group: 25 - 35 us each on one core, 64 of them per group.
 template <class Fn>
@@ -1827,8 +1948,14 @@ static msm_pending_t msm_enqueue_job(lane_t& c, const bases_handle_t<F>& h, int 
             HIP_TRY(hipMemcpyAsync(c.scalars.p, r.scalars, n * 32, hipMemcpyHostToDevice, c.stream));
             d_sc = c.scalars.template as<uint4>();
         }
-        return msm_run<F>(c, h.d[dev] + r.off0, d_sc, n, host_planes, window_bits, r.n1 ? h.d[dev] + r.off1 : nullptr, r.n1 ? r.n0 : ~(size_t)0, scalars_montgomery,
-                          h.tables, h.n, false, h.table_bits, nullptr, nullptr, scalars_read);
+        msm_job_t<F> one = msm_handle_job(h, dev, r);
+        one.scalars = d_sc;
+        one.scalars_montgomery = scalars_montgomery;
+        one.window_bits = window_bits;
+        one.host_planes = host_planes;
+        one.profile = false;
+        one.scalars_read = scalars_read;
+        return msm_run<F>(c, one);
     }
     // fused group: instance table (pinned -> device), scalars of host callers packed into the lane's scalar buffer
     const size_t K = job.size();
@@ -1865,7 +1992,14 @@ static msm_pending_t msm_enqueue_job(lane_t& c, const bases_handle_t<F>& h, int 
     mu.npad = npad;
     mu.hn = h.n;
     mu.plane_capacity = K * msm_fuse_planes(h);  // checked by msm_run BEFORE it enqueues the copy into the staging area
-    return msm_run<F>(c, h.d[dev], nullptr, npad, host_planes, 0, nullptr, ~(size_t)0, scalars_montgomery, h.tables, h.n, false, h.table_bits, &mu, nullptr, scalars_read);
+    msm_job_t<F> group = msm_handle_job(h, dev, msm_req_t{});  // the whole table array: the instance table names the ranges
+    group.n = npad;
+    group.scalars_montgomery = scalars_montgomery;
+    group.host_planes = host_planes;
+    group.profile = false;
+    group.multi = &mu;
+    group.scalars_read = scalars_read;
+    return msm_run<F>(c, group);
 }
 // the host finish of job `job` (its planes have arrived): one Horner chain per instance, the instances of a fused group on several threads
 template <class F>
