@@ -424,7 +424,8 @@ RustError snarkvm_hip_synchronize(void);
 
 /* The device arithmetic (ff.hip.h / ec.hip.h) compiled for the host and run on the CPU, so that the
  * limb arithmetic can be checked without a GPU.  field: 0 = Fr, 1 = Fq.  op: 0 add, 1 sub, 2 mul,
- * 3 sqr, 4 inverse, 5 neg, 6 from_bigint, 7 to_bigint.  Operands / results are in the reference's
+ * 3 sqr, 4 inverse, 5 neg, 6 from_bigint, 7 to_bigint, 8 the NTT's lazy chain ((a + b) - b + 2r) * b (Fr; Fq: a * b),
+ * 9 diff_of_products(a, b, b, a + b) = a*b - b*(a + b).  Operands / results are in the reference's
  * memory form (Montgomery R = 2^256 / 2^384), n elements of 32 / 48 bytes. */
 int snarkvm_hip_selftest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 /* op: 0 = out(Jacobian 144 B) = sum_i (xyzz) points[i] * small_scalars[i] via mixed adds and doublings;
@@ -479,6 +480,18 @@ int snarkvm_hip_selftest_ntt_host(void *inout, uint32_t lg, const int32_t *plan,
 int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
+/* Field arithmetic that the two operands of snarkvm_hip_selftest_field cannot express, one case per record, operands and results in memory
+ * form.  op (input record -> output record, in field elements of 32 B (Fr) / 48 B (Fq), an Fq2 element = c0 then c1):
+ *   0  Fq diff_of_products: a, b, c, d -> a*b - c*d          1  the same over Fr
+ *   2  Fq2 mul: a, b -> a*b      3  Fq2 sqr: a -> a^2        4  Fq2 inverse: a -> 1/a (a != 0)
+ *   5  Fq2 diff_of_products: a, b, c, d -> a*b - c*d
+ *   6  Fq sqrt: a -> root (48 B), then ok as four 32-bit words {ok, 0, 0, 0}: ok = 0 and root = 0 for a non-residue
+ *   7  Fq2 sqrt: a -> root (96 B), then {ok, 0, 0, 0}: ok = 0 where the reference's Fp2::sqrt returns None
+ *   8  Fq raw: a, b -> a + b, a - b, -a, 2a, a * b, 0 * 0 - a * b as the arithmetic's INTERNAL limbs (a 2^377 mod q, 29-bit limbs packed into 48 B)
+ *      without the conversion back to memory form, so that a result that is not canonical (q instead of 0) shows      9  the same over Fr (2^261)
+ * selftest: on the host (the same source as the kernels, square roots included), returns 0, or 1 for a bad argument; devtest: one GPU thread per case. */
+int snarkvm_hip_selftest_field_ext(int op, const void *in, void *out, size_t n);
+RustError snarkvm_hip_devtest_field_ext(int op, const void *in, void *out, size_t n);
 
 #ifdef __cplusplus
 }

@@ -20,10 +20,16 @@ enum { SERDE_BAD_FLAGS = 1, SERDE_NOT_CANONICAL = 2, SERDE_NOT_ON_CURVE = 4, SER
 
 // (T - 1) / 2 with q - 1 = 2^46 T (fq.rs T_MINUS_ONE_DIV_TWO), the 2^46-th root of unity (fq.rs TWO_ADIC_ROOT_OF_UNITY,
 // canonical integer) and r (fr.rs MODULUS); 32-bit words, little endian.  Re-derived from tests/golden/constants.json by
-// tests/test_host_arith.py.
-__device__ static const uint32_t FQ_T_MINUS_ONE_DIV_TWO[12] = {0x00010a11u, 0xba886000u, 0x90002e16u, 0xc45f7412u, 0x271e3de6u, 0xb3e601eau,
+// tests/test_serialize_cpu.py.  fq_sqrt / fq2_sqrt also run on the host (snarkvm_hip_selftest_field_ext), where a __device__
+// variable holds nothing: the host pass sees the square root's two tables as plain constants, the device pass as before.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SV_SQRT_TABLE __device__ static const
+#else
+#define SV_SQRT_TABLE static const
+#endif
+SV_SQRT_TABLE uint32_t FQ_T_MINUS_ONE_DIV_TWO[12] = {0x00010a11u, 0xba886000u, 0x90002e16u, 0xc45f7412u, 0x271e3de6u, 0xb3e601eau,
                                                               0x92763445u, 0x0b80d942u, 0x21d58c76u, 0x748c2f8au, 0x0000035cu, 0x00000000u};
-__device__ static const uint32_t FQ_TWO_ADIC_ROOT_INT[12] = {0x94ff4419u, 0xca9d610du, 0x6386ae79u, 0xf86b201bu, 0x63e6bd3bu, 0x5808bf73u,
+SV_SQRT_TABLE uint32_t FQ_TWO_ADIC_ROOT_INT[12] = {0x94ff4419u, 0xca9d610du, 0x6386ae79u, 0xf86b201bu, 0x63e6bd3bu, 0x5808bf73u,
                                                             0x90d30280u, 0x48d30f28u, 0xc20ffe30u, 0x365126d9u, 0x7df7548du, 0x01760d08u};
 __device__ static const uint32_t FR_MODULUS_WORDS[8] = {0x00000001u, 0x0a118000u, 0xd0000001u, 0x59aa76feu,
                                                         0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu};
@@ -69,7 +75,7 @@ __device__ __forceinline__ bool fq_int_gt(const fq_t& a, const fq_t& b) {
 }
 // Tonelli-Shanks square root in Fq (internal Montgomery form); false for a non-residue.  Either root may come back -
 // the caller picks by comparison, exactly like the reference does after its own sqrt (fields/src/macros.rs:85-180).
-__device__ inline bool fq_sqrt(const fq_t& a, fq_t& root) {
+__host__ __device__ inline bool fq_sqrt(const fq_t& a, fq_t& root) {
     if (a.is_zero()) {
         root = a;
         return true;
@@ -212,7 +218,7 @@ __device__ static const uint32_t G2_B_C1_INT[12] = {0x9999999au, 0x1c9ed999u, 0x
                                                    0xcd5fd889u, 0xdc7b4f91u, 0x7460c589u, 0x43bd0373u, 0xdb0fd6f3u, 0x010222f6u};
 // `Fp2::sqrt` (fields/src/fp2.rs:208-230; complex method, eprint 2012/685 algorithm 8).  false where the reference returns None
 // - including an element of the base field that is a non-residue THERE (fp2.rs:210-212 only tries `c0.sqrt()`).
-__device__ inline bool fq2_sqrt(const fq2_t& a, fq2_t& root) {
+__host__ __device__ inline bool fq2_sqrt(const fq2_t& a, fq2_t& root) {
     if (a.c1.is_zero()) {
         fq_t r;
         if (!fq_sqrt(a.c0, r)) return false;

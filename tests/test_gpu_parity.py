@@ -29,12 +29,17 @@ def test_field_ops_on_device(field):
     ofn = oracle.fr_op if field == 0 else oracle.fq_op
     a = _rand_mont(field, 1000, 30 + field)
     b = _rand_mont(field, 1000, 40 + field)[::-1].copy()
-    for op in ("add", "sub", "mul", "sqr", "neg", "from_bigint", "to_bigint", "inverse"):
+    for op in ("add", "sub", "mul", "sqr", "neg", "from_bigint", "to_bigint", "inverse", "lazy_chain", "diff_of_products"):
         aa = a[1:200] if op == "inverse" else a
         bb = b[1:200] if op == "inverse" else b
         out = np.zeros_like(aa)
         _lib.check(L.snarkvm_hip_devtest_field(ctypes.c_int(field), ctypes.c_int(OPS[op]), _p(aa), _p(bb), _p(out), ctypes.c_size_t(aa.shape[0])))
-        want = ofn(op, aa, bb) if op in ("add", "sub", "mul") else ofn(op, aa)
+        if op == "lazy_chain":  # ((a + b) - b + 2r) * b, reduced (Fr; over Fq the op is the plain product)
+            want = ofn("mul", aa, bb)
+        elif op == "diff_of_products":  # a*b - b*(a + b) with one signed-accumulator reduction
+            want = ofn("sub", ofn("mul", aa, bb), ofn("mul", bb, ofn("add", aa, bb)))
+        else:
+            want = ofn(op, aa, bb) if op in ("add", "sub", "mul") else ofn(op, aa)
         assert np.array_equal(out, want), (field, op)
 
 
