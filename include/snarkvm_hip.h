@@ -171,7 +171,9 @@ RustError snarkvm_hip_polymul_device(void *d_out, size_t pcount, const void *con
  * to use, or NULL for any GPU) and snarkvm_hip_scope_end, calls of THIS thread whose operands and results live in device memory
  * - snarkvm_hip_ntt_device, _ntt_device_batch, _polymul_device, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
  * kernels (snarkvm_hip_fr_lincomb among them) with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
- * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end.  Every other call (MSMs,
+ * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end, and so are the host results of
+ * snarkvm_hip_fr_reduce[_strided] and snarkvm_hip_fr_support[_strided] over device operands (the same mechanism: parked in pinned memory, copied
+ * to the caller's buffer when the scope is flushed - the buffer must stay valid until then).  Every other call (MSMs,
  * host buffers, a pointer on another GPU) first waits for the scope's queued work, so results are the same as without a scope - and
  * then runs on the scope's own stream: a thread inside a scope never waits for a free stream.  Scopes do not nest; a scope must be
  * ended by the thread that began it (a thread that ENDS with its scope still open returns the scope's streams to the pool: the queued work is
@@ -381,6 +383,35 @@ RustError snarkvm_hip_fr_mul_by_vanishing(void *out, const void *poly, size_t le
 RustError snarkvm_hip_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs,
                                  int on_device);
 
+/* Reductions: a vector -> a value, in one streaming read (csrc/poly.hip.h: fr_reduce_kernel, fr_support_kernel; a second launch folds the
+ * per-workgroup partials - no atomics, and since field addition is exact the 32 bytes do not depend on the shape of the tree).
+ * fr_reduce: op SNARKVM_HIP_FR_REDUCE_SUM: *result = sum_i a[i] (`b` is ignored; the sum of a polynomial's evaluations over a domain,
+ * snark/varuna/ahp/prover/round_functions/first.rs:119); op SNARKVM_HIP_FR_REDUCE_DOT: *result = sum_i a[i] * b[i] - Evaluations::evaluate_with_coeffs
+ * (fft/evaluations.rs:90-92) with `b` the vector snarkvm_hip_fr_lagrange_coefficients left in device memory; the products go four at a time
+ * through one Montgomery reduction.
+ * fr_support: out3 = {trimmed_len, leading_zeros, nonzero}: the index of the last non-zero element + 1 (0 for the zero vector, so that
+ * DensePolynomial::degree (dense.rs:88-96) = max(trimmed_len, 1) - 1 and is_zero = trimmed_len == 0), the index of the first non-zero element
+ * (n for the zero vector: the count of skip_leading_zeros_and_convert_to_bigints, kzg10/mod.rs:455-467), and the number of non-zero elements.
+ *  - Results are HOST values (32 bytes / three uint64_t per vector).  With host operands (on_device = 0: staged like the other passes) they are
+ *    there on return.  With device operands inside a snarkvm_hip_scope the call is only enqueued on the scope's stream, in order, and the
+ *    values are delivered when the scope is flushed (snarkvm_hip_scope_end), like the `remainder` of snarkvm_hip_fr_divide_by_linear.
+ *  - n == 0: success, no device is needed; the Fr result is zero, the support is {0, 0, 0}.  A vector pointer may be NULL iff n == 0.
+ *  - Operands are never written; `a` may equal `b` (a sum of squares).
+ *  - Refused with hipErrorInvalidValue before anything is launched (and before a device is needed): an unknown op, a NULL result, a NULL `a`
+ *    (or, for DOT, `b`) with n > 0; device operands on different devices.
+ *  - Workspace (one partial per workgroup, at most 2048 per vector) comes from the calling lane; a repeated call grows nothing
+ *    (snarkvm_hip_alloc_stats).
+ * The strided forms are batches over device memory like the ones below: member y reads `a` (and `b`, `v`) advanced by y * stride elements,
+ * stride >= n, one launch sequence for all; results = count x 32 bytes, out = count x 3 uint64_t, member after member.  b_shared != 0: every
+ * member is multiplied by the SAME `b` (the three evaluate_with_coeffs of one matrix, snark/varuna/ahp/matrices.rs:117); otherwise `b`
+ * advances like `a`.  count == 0: success, nothing happens. */
+enum { SNARKVM_HIP_FR_REDUCE_SUM = 0, SNARKVM_HIP_FR_REDUCE_DOT = 1 };
+RustError snarkvm_hip_fr_reduce(int op, void *result, const void *a, const void *b, size_t n, int on_device);
+RustError snarkvm_hip_fr_reduce_strided(int op, void *results, const void *a, const void *b, size_t n, size_t count, size_t stride,
+                                        int b_shared);
+RustError snarkvm_hip_fr_support(uint64_t *out3, const void *v, size_t n, int on_device);
+RustError snarkvm_hip_fr_support_strided(uint64_t *out, const void *v, size_t n, size_t count, size_t stride);
+
 /* Strided batches of the passes above on device memory - the same pass over one vector of every proof of a batch proved in lock
  * step (VarunaSNARK::prove_batch, snark/varuna/varuna.rs:336): member y of the batch uses every vector pointer advanced by
  * y * stride elements (stride >= the vector length); ONE kernel launch sequence for the whole batch.  fr_vec_op_strided: `scalar`
@@ -478,6 +509,14 @@ int snarkvm_hip_selftest_ntt_host(void *inout, uint32_t lg, const int32_t *plan,
  * every launch a loop over i through the kernel's own per-element routine (csrc/poly.hip.h: fr_lincomb_at, Fp::sum_of_products).  0, or -1
  * when the arguments are refused. */
 int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs);
+/* snarkvm_hip_fr_reduce / snarkvm_hip_fr_support over host memory with the CPU in the kernels' place, over a GIVEN launch geometry (blocks >= 1
+ * workgroups of threads = 64, 128 or 256): every thread's private accumulation and every combine step through the kernels' own routines
+ * (csrc/poly.hip.h: fr_reduce_thread, fr_support_thread, fr_support_combine), the trees level by level over the lanes they exchange between, the
+ * second launch included.  0, or -1 when the arguments are refused.  fr_reduce_geometry: out4 = {workgroups, threads per workgroup} the device
+ * call launches for n elements, the cap on the workgroups, and the number of products per Montgomery reduction of the inner product. */
+int snarkvm_hip_selftest_fr_reduce(int op, void *out, const void *a, const void *b, size_t n, uint32_t blocks, uint32_t threads);
+int snarkvm_hip_selftest_fr_support(uint64_t *out3, const void *v, size_t n, uint32_t blocks, uint32_t threads);
+int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t *out4);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 /* Field arithmetic that the two operands of snarkvm_hip_selftest_field cannot express, one case per record, operands and results in memory

@@ -201,6 +201,19 @@ inline void fr_lincomb(void* out, size_t n_out, const std::vector<DevicePoly>& p
     check(snarkvm_hip_fr_lincomb(out, n_out, pptrs.size(), pptrs.data(), plens.data(), coeffs, on_device ? 1 : 0));
 }
 
+// Reductions in one device pass (snarkvm_hip.h: snarkvm_hip_fr_reduce, snarkvm_hip_fr_support): the sum of a vector, the inner product of two
+// (Evaluations::evaluate_with_coeffs with the Lagrange coefficients left in device memory), and the support of a coefficient vector.  `result`
+// is 32 bytes of HOST memory; with on_device inside a Scope the call is only enqueued and the value arrives when the Scope ends.
+inline void fr_sum(void* result, const void* a, size_t n, bool on_device) { check(snarkvm_hip_fr_reduce(SNARKVM_HIP_FR_REDUCE_SUM, result, a, nullptr, n, on_device ? 1 : 0)); }
+inline void fr_inner_product(void* result, const void* a, const void* b, size_t n, bool on_device) {
+    check(snarkvm_hip_fr_reduce(SNARKVM_HIP_FR_REDUCE_DOT, result, a, b, n, on_device ? 1 : 0));
+}
+// trimmed_len (0: the zero vector; degree = max(trimmed_len, 1) - 1), leading_zeros (n: the zero vector), nonzero
+struct FrSupport {
+    uint64_t trimmed_len, leading_zeros, nonzero;
+};
+inline void fr_support(FrSupport& out, const void* v, size_t n, bool on_device) { check(snarkvm_hip_fr_support(&out.trimmed_len, v, n, on_device ? 1 : 0)); }
+
 // Registered bases (an SRS resident in HBM with precomputed window tables): register once, commit per call.  `tables` x
 // `window_bits` must cover 254 bits (17 x 15 for proof-sized MSMs, 12 x 22 at 2^24).  Concurrent commit() calls of proof size
 // are fused inside the library (runtime.hip.h::msm_coalesced).

@@ -682,6 +682,158 @@ int snarkvm_hip_selftest_fr_lincomb(void* out, size_t n_out, size_t count, const
     return 0;
 }
 
+// ---- reductions (poly.hip.h: fr_reduce_kernel, fr_support_kernel) ---------------------------------------------------------------
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device
+static const char* fr_reduce_check(int op, const void* result, const void* a, const void* b, size_t n) {
+    if (op != FR_REDUCE_SUM && op != FR_REDUCE_DOT) return "unknown op";
+    if (!result) return "null result";
+    if (n && !a) return "null operand a";
+    if (n && op == FR_REDUCE_DOT && !b) return "null operand b of an inner product";
+    return nullptr;
+}
+// check_strided without a lane: the same refusal, before any device is needed
+static bool fr_strided_refused(size_t n, size_t count, size_t stride, RustError& err) {
+    try {
+        check_strided(n, count, stride, 1, "fr_reduce");
+    } catch (const hip_failure& f) {
+        err = from_failure(f);
+        return true;
+    }
+    return false;
+}
+static void fr_same_device(lane_t& c, const void* p, const char* what) {
+    if (p && g_rt.devs[device_for(p, 1)]->physical != c.dev->physical) throw hip_failure{hipErrorInvalidValue, what, __LINE__};
+}
+static RustError fr_reduce_impl(int op, void* results, const void* a, const void* b, size_t n, int on_device, size_t count, size_t stride, int b_shared) {
+    if (count == 0) return ok();
+    if (const char* why = fr_reduce_check(op, results, a, b, n)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_reduce: ") + why);
+    RustError refused = ok();
+    if (fr_strided_refused(n, count, stride, refused)) return refused;
+    if (n == 0) {
+        memset(results, 0, sizeof(fr_mem_t) * count);
+        return ok();
+    }
+    API_BEGIN_DEV(device_for(a, on_device ? 1 : 0))
+    const bool dot = op == FR_REDUCE_DOT;
+    if (on_device && dot) fr_same_device(c, b, "fr_reduce: b lives on another device than a");
+    const fr_mem_t* da = fr_stage_in(c, 0, a, n, on_device);
+    const fr_mem_t* db = !dot ? nullptr : ((b == a && !on_device) ? da : fr_stage_in(c, 1, b, n, on_device));
+    const unsigned blocks = fr_reduce_blocks(n);
+    // workspace: count x blocks partials, then the count results
+    c.poly[4].ensure(sizeof(fr_mem_t) * count * ((size_t)blocks + 1));
+    fr_mem_t* parts = c.poly[4].as<fr_mem_t>();
+    fr_mem_t* dres = parts + count * (size_t)blocks;
+    const dim3 grid(blocks, (unsigned)count);
+    if (dot)
+        hipLaunchKernelGGL(fr_reduce_kernel<FR_REDUCE_DOT>, grid, dim3(FR_REDUCE_B), 0, c.stream, da, db, n, stride, b_shared ? (size_t)0 : stride, parts);
+    else
+        hipLaunchKernelGGL(fr_reduce_kernel<FR_REDUCE_SUM>, grid, dim3(FR_REDUCE_B), 0, c.stream, da, db, n, stride, (size_t)0, parts);
+    hipLaunchKernelGGL(fr_reduce_final_kernel, dim3(1, (unsigned)count), dim3(FR_REDUCE_B), 0, c.stream, op, (const fr_mem_t*)parts, (size_t)blocks, dres);
+    HIP_TRY(hipGetLastError());
+    // device operands inside a scope: delivered by snarkvm_hip_scope_end; host operands: the call waits below, the value is there on return
+    c.host_result(results, dres, sizeof(fr_mem_t) * count, on_device != 0);
+    fr_call_done(c, on_device);
+    API_END
+}
+RustError snarkvm_hip_fr_reduce(int op, void* result, const void* a, const void* b, size_t n, int on_device) {
+    return fr_reduce_impl(op, result, a, b, n, on_device, 1, 0, 0);
+}
+RustError snarkvm_hip_fr_reduce_strided(int op, void* results, const void* a, const void* b, size_t n, size_t count, size_t stride, int b_shared) {
+    return fr_reduce_impl(op, results, a, b, n, 1, count, stride, b_shared);
+}
+static RustError fr_support_impl(uint64_t* out, const void* v, size_t n, int on_device, size_t count, size_t stride) {
+    if (count == 0) return ok();
+    if (!out || (n && !v)) return fail((int)hipErrorInvalidValue, "snarkvm_hip: fr_support: missing argument");
+    RustError refused = ok();
+    if (fr_strided_refused(n, count, stride, refused)) return refused;
+    if (n == 0) {
+        memset(out, 0, 3 * sizeof(uint64_t) * count);
+        return ok();
+    }
+    API_BEGIN_DEV(device_for(v, on_device ? 1 : 0))
+    const fr_mem_t* dv = fr_stage_in(c, 0, v, n, on_device);
+    const unsigned blocks = fr_reduce_blocks(n);
+    c.poly[4].ensure(3 * sizeof(uint64_t) * count * ((size_t)blocks + 1));
+    uint64_t* parts = c.poly[4].as<uint64_t>();
+    uint64_t* dres = parts + 3 * count * (size_t)blocks;
+    hipLaunchKernelGGL(fr_support_kernel, dim3(blocks, (unsigned)count), dim3(FR_REDUCE_B), 0, c.stream, dv, n, stride, parts);
+    hipLaunchKernelGGL(fr_support_final_kernel, dim3(1, (unsigned)count), dim3(FR_REDUCE_B), 0, c.stream, (const uint64_t*)parts, (size_t)blocks, n, dres);
+    HIP_TRY(hipGetLastError());
+    c.host_result(out, dres, 3 * sizeof(uint64_t) * count, on_device != 0);
+    fr_call_done(c, on_device);
+    API_END
+}
+RustError snarkvm_hip_fr_support(uint64_t* out3, const void* v, size_t n, int on_device) { return fr_support_impl(out3, v, n, on_device, 1, 0); }
+RustError snarkvm_hip_fr_support_strided(uint64_t* out, const void* v, size_t n, size_t count, size_t stride) { return fr_support_impl(out, v, n, 1, count, stride); }
+
+// The two passes on host memory with the CPU in the kernels' place, over a GIVEN geometry (blocks workgroups of `threads` threads, threads = 64, 128
+// or 256): every thread through the kernels' own per-thread routine, every tree level a loop over the lanes it exchanges between, the second launch
+// with FR_REDUCE_B threads.  0, or -1 when the arguments are refused.
+static bool fr_reduce_geometry_ok(uint32_t blocks, uint32_t threads) { return blocks >= 1 && (threads == 64 || threads == 128 || threads == 256); }
+// the butterflies of fr_block_sum / fr_block_support over `vals` (one per thread): lanes l and l ^ off meet, then the waves' values
+extern "C++" {
+template <class T, class Combine>
+static T fr_block_tree_host(std::vector<T> vals, const T& identity, Combine combine) {
+    const size_t nw = vals.size() / 64;
+    auto butterfly = [&](T* lanes, size_t from) {
+        for (size_t off = from; off >= 1; off >>= 1) {
+            T next[64];
+            for (size_t l = 0; l < 64; l++) next[l] = combine(lanes[l], lanes[l ^ off]);
+            std::copy(next, next + 64, lanes);
+        }
+    };
+    for (size_t w = 0; w < nw; w++) butterfly(vals.data() + 64 * w, 32);
+    if (nw == 1) return vals[0];
+    T u[64];
+    for (size_t l = 0; l < 64; l++) u[l] = l < nw ? vals[64 * l] : identity;
+    butterfly(u, nw >> 1);
+    return u[0];
+}
+}  // extern "C++"
+int snarkvm_hip_selftest_fr_reduce(int op, void* out, const void* a, const void* b, size_t n, uint32_t blocks, uint32_t threads) {
+    if (fr_reduce_check(op, out, a, b, n) || !fr_reduce_geometry_ok(blocks, threads)) return -1;
+    const fr_mem_t *pa = (const fr_mem_t*)a, *pb = (const fr_mem_t*)b;
+    const auto add = [](const fr_t& x, const fr_t& y) { return x + y; };
+    std::vector<fr_mem_t> parts(blocks);
+    for (uint32_t x = 0; x < blocks; x++) {
+        std::vector<fr_t> vals(threads);
+        for (uint32_t t = 0; t < threads; t++) {
+            const size_t first = (size_t)x * threads + t, step = (size_t)blocks * threads;
+            vals[t] = op == FR_REDUCE_DOT ? fr_reduce_thread<FR_REDUCE_DOT>(pa, pb, n, first, step) : fr_reduce_thread<FR_REDUCE_SUM>(pa, pb, n, first, step);
+        }
+        fr_block_tree_host(vals, fr_t::zero(), add).store(&parts[x]);
+    }
+    std::vector<fr_t> vals(FR_REDUCE_B);
+    for (uint32_t t = 0; t < (uint32_t)FR_REDUCE_B; t++) vals[t] = fr_reduce_thread<FR_REDUCE_SUM>(parts.data(), nullptr, blocks, t, FR_REDUCE_B);
+    fr_mem_t res;
+    fr_reduce_finish(op, fr_block_tree_host(vals, fr_t::zero(), add)).store(&res);
+    memcpy(out, &res, sizeof res);
+    return 0;
+}
+int snarkvm_hip_selftest_fr_support(uint64_t* out3, const void* v, size_t n, uint32_t blocks, uint32_t threads) {
+    if (!out3 || (n && !v) || !fr_reduce_geometry_ok(blocks, threads)) return -1;
+    const fr_support_t id = fr_support_identity(n);
+    std::vector<uint64_t> parts(3 * (size_t)blocks);
+    for (uint32_t x = 0; x < blocks; x++) {
+        std::vector<fr_support_t> vals(threads);
+        for (uint32_t t = 0; t < threads; t++) vals[t] = fr_support_thread((const fr_mem_t*)v, n, (size_t)x * threads + t, (size_t)blocks * threads);
+        const fr_support_t s = fr_block_tree_host(vals, id, fr_support_combine);
+        parts[3 * x] = s.trimmed_len, parts[3 * x + 1] = s.leading_zeros, parts[3 * x + 2] = s.nonzero;
+    }
+    std::vector<fr_support_t> vals(FR_REDUCE_B);
+    for (uint32_t t = 0; t < (uint32_t)FR_REDUCE_B; t++) vals[t] = fr_support_fold(parts.data(), blocks, n, t, FR_REDUCE_B);
+    const fr_support_t s = fr_block_tree_host(vals, id, fr_support_combine);
+    out3[0] = s.trimmed_len, out3[1] = s.leading_zeros, out3[2] = s.nonzero;
+    return 0;
+}
+// what snarkvm_hip_fr_reduce / _fr_support launch for n elements: out4 = {workgroups, threads per workgroup, the cap on workgroups, the group size G
+// of the inner product's sum_of_products}
+int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t* out4) {
+    if (!out4) return -1;
+    out4[0] = fr_reduce_blocks(n), out4[1] = FR_REDUCE_B, out4[2] = FR_REDUCE_BLOCKS_MAX, out4[3] = FR_REDUCE_G;
+    return 0;
+}
+
 // ---- setup-time group operations (group.hip.h) -------------------------------------------------------
 RustError snarkvm_hip_g1_fixed_base_msm(void* out_projective, const void* g_affine, const void* scalars, size_t n) {
     API_BEGIN

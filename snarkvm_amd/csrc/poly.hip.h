@@ -10,6 +10,8 @@
 //   fr_fold_vanishing_kernel    quotient / remainder by X^D - 1                  dense.rs:161-169 (divide_by_vanishing_poly)
 //   fr_mul_vanishing_kernel     p * (X^D - 1)                                    dense.rs:153-159
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
+//   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
+//   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
 //
 // Representation note (ff.hip.h): the raw memory limbs of a, read as an internal value, are the internal Montgomery form of
 // a * 2^-5 ("shifted").  Sums and differences of shifted values are shifted values; the product of a TRUE internal
@@ -349,5 +351,188 @@ static __global__ void fr_mul_vanishing_kernel(const fr_mem_t* __restrict__ a, s
     const fr_t lo = (i < len) ? fr_t::load(&a[i]) : fr_t::zero();
     (hi - lo).store(&out[i]);
 }
+
+// ---- reductions: a vector -> a value ----------------------------------------------------------------------------------------
+// The third family of Fr passes beside the maps and the scans: ONE streaming read with a tree at the end, so that a question about a
+// device-resident vector - its inner product with the Lagrange coefficients (Evaluations::evaluate_with_coeffs, fft/evaluations.rs:85-92), its sum
+// over a domain (first.rs:119), its degree, whether it is zero, how many leading zeros a commitment may skip (dense.rs:66-96, kzg10/mod.rs:455-467)
+// - costs a 32-byte or 24-byte answer instead of a download.
+//   launch 1  fr_reduce_kernel / fr_support_kernel: grid (blocks, batch members).  Threads stride over the vector through the grid and accumulate
+//             privately; a wave folds its 64 values by a butterfly of __shfl_xor exchanges (every lane ends with the wave's value), the waves of the
+//             workgroup meet through LDS (one value per wave, the same butterfly over the first lanes); thread 0 writes ONE partial per workgroup
+//             and batch member into lane workspace.
+//   launch 2  fr_reduce_final_kernel / fr_support_final_kernel: one workgroup per batch member folds the partials by the same routines.
+// Two launches and no "last block done" counter: which workgroup finishes last never enters the result, not even as the shape of the tree.  Field
+// addition is exact and Fr elements have one representation, so ANY tree gives the same 32 bytes; min, max and integer sums likewise.  The trees
+// here are chosen for speed alone.
+// Inner product: both operands are streamed raw ("shifted", see the top of this file); raw(a) * raw(b) is the internal form of a b 2^-10, sums of
+// such values are such values, and ONE from_mem_mont at the very end (launch 2, thread 0) turns the total into the memory form of sum a_i b_i.
+// Terms go FR_REDUCE_G at a time through Fp::sum_of_products: one Montgomery reduction per group (its operand conditions hold: memory images of
+// field elements are canonical, so the first factor is < r and the second < 2^256).  G = 4 and not the 6 the accumulator allows: both factors are
+// vector registers here (fr_lincomb keeps its coefficients in scalar registers), 2 x 9 x G limbs in flight: 122 VGPRs.  Measured at 2^24 elements:
+// 0.232 ms against 0.301 (G = 1), 0.243 (G = 2) and 0.233 (G = 6); the grid cap makes no measurable difference between 512 and 8192
+// (profiles/fr_reduce.md; tools/bench_fr_reduce.py is the tool).
+// Geometry: FR_REDUCE_B threads, ceil(n / FR_REDUCE_B) workgroups up to FR_REDUCE_BLOCKS_MAX (2048 x 256 threads = every wave slot of the 256 CUs
+// once); the kernels themselves take any power-of-two number of waves up to FR_REDUCE_B / 64 and any number of workgroups (the host replay,
+// snarkvm_hip_selftest_fr_reduce / _fr_support, walks a given geometry through the same per-thread and combine routines).
+enum { FR_REDUCE_SUM = 0, FR_REDUCE_DOT = 1 };
+static constexpr int FR_REDUCE_B = 256;
+static constexpr int FR_REDUCE_G = 4;
+static constexpr unsigned FR_REDUCE_BLOCKS_MAX = 2048;
+SV_HD unsigned fr_reduce_blocks(size_t n) {
+    const size_t b = (n + FR_REDUCE_B - 1) / FR_REDUCE_B;
+    return (unsigned)(b < 1 ? 1 : (b > FR_REDUCE_BLOCKS_MAX ? FR_REDUCE_BLOCKS_MAX : b));
+}
+// G terms at i, i + step, ...: their sum (OP = SUM) or the sum of their products, unreduced to memory form (OP = DOT)
+template <int OP, int G>
+SV_HD fr_t fr_reduce_group(const fr_mem_t* a, const fr_mem_t* b, size_t i, size_t step) {
+    fr_t x[G], y[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        x[g] = fr_t::load(&a[i + g * step]);
+        if (OP == FR_REDUCE_DOT) y[g] = fr_t::load(&b[i + g * step]);
+    }
+    if (OP == FR_REDUCE_DOT) return fr_t::sum_of_products<G>(x, y);
+    fr_t s = x[0];
+#pragma unroll
+    for (int g = 1; g < G; g++) s = s + x[g];
+    return s;
+}
+// the private accumulation of one thread over i = first, first + step, ... < n: whole groups, then single terms
+template <int OP>
+SV_HD fr_t fr_reduce_thread(const fr_mem_t* a, const fr_mem_t* b, size_t n, size_t first, size_t step) {
+    fr_t acc = fr_t::zero();
+    size_t i = first;
+#pragma unroll 1
+    for (; i < n && n - i > (FR_REDUCE_G - 1) * step; i += FR_REDUCE_G * step) acc = acc + fr_reduce_group<OP, FR_REDUCE_G>(a, b, i, step);
+#pragma unroll 1
+    for (; i < n; i += step) acc = acc + fr_reduce_group<OP, 1>(a, b, i, step);
+    return acc;
+}
+// what launch 2 does to the total
+SV_HD fr_t fr_reduce_finish(int op, const fr_t& total) { return op == FR_REDUCE_DOT ? total.from_mem_mont() : total; }
+
+// trimmed_len: index of the last non-zero element + 1 (0: the zero vector; degree = max(trimmed_len, 1) - 1); leading_zeros: index of the first
+// non-zero element (n: the zero vector); nonzero: how many.  An element is zero iff all of its 8 words are (Montgomery 0 is 0).
+struct fr_support_t {
+    uint64_t trimmed_len, leading_zeros, nonzero;
+};
+SV_HD fr_support_t fr_support_identity(size_t n) { return fr_support_t{0, (uint64_t)n, 0}; }
+SV_HD fr_support_t fr_support_combine(const fr_support_t& x, const fr_support_t& y) {
+    return fr_support_t{x.trimmed_len > y.trimmed_len ? x.trimmed_len : y.trimmed_len, x.leading_zeros < y.leading_zeros ? x.leading_zeros : y.leading_zeros,
+                        x.nonzero + y.nonzero};
+}
+SV_HD bool fr_mem_is_zero(const fr_mem_t* p) {
+    const uint4* q = (const uint4*)p;
+    const uint4 lo = q[0], hi = q[1];
+    return ((lo.x | lo.y | lo.z | lo.w) | (hi.x | hi.y | hi.z | hi.w)) == 0;
+}
+SV_HD fr_support_t fr_support_thread(const fr_mem_t* v, size_t n, size_t first, size_t step) {
+    fr_support_t s = fr_support_identity(n);
+    for (size_t i = first; i < n; i += step) {
+        if (fr_mem_is_zero(&v[i])) continue;
+        if (!s.nonzero) s.leading_zeros = i;  // a thread walks upwards
+        s.trimmed_len = i + 1;
+        s.nonzero++;
+    }
+    return s;
+}
+// launch 2's walk over the partials of launch 1
+SV_HD fr_support_t fr_support_fold(const uint64_t* parts, size_t nparts, size_t n, size_t first, size_t step) {
+    fr_support_t s = fr_support_identity(n);
+    for (size_t k = first; k < nparts; k += step) s = fr_support_combine(s, fr_support_t{parts[3 * k], parts[3 * k + 1], parts[3 * k + 2]});
+    return s;
+}
+
+#if defined(__HIPCC__)
+// Butterfly over the lanes l ^ off, off = from .. 1: every lane ends with the combination of its aligned group of 2 * from lanes.  All 64 lanes of
+// the wave take part (no thread of these kernels leaves before the trees).  The nine 29-bit limbs travel as they are: packing them into the 8
+// memory words and back costs more VALU work than the ninth exchange saves.
+__device__ __forceinline__ fr_t fr_lanes_sum(fr_t v, int from) {
+#pragma unroll 1
+    for (int off = from; off >= 1; off >>= 1) {
+        fr_t o;
+#pragma unroll
+        for (int l = 0; l < 9; l++) o.v[l] = (uint32_t)__shfl_xor((int)v.v[l], off);
+        v = v + o;
+    }
+    return v;
+}
+__device__ __forceinline__ fr_support_t fr_lanes_support(fr_support_t s, int from) {
+#pragma unroll 1
+    for (int off = from; off >= 1; off >>= 1) {
+        fr_support_t o;
+        o.trimmed_len = (uint64_t)__shfl_xor((unsigned long long)s.trimmed_len, off);
+        o.leading_zeros = (uint64_t)__shfl_xor((unsigned long long)s.leading_zeros, off);
+        o.nonzero = (uint64_t)__shfl_xor((unsigned long long)s.nonzero, off);
+        s = fr_support_combine(s, o);
+    }
+    return s;
+}
+// the workgroup's value in (at least) thread 0; blockDim.x = 64, 128 or 256; sh: 9 words per wave, limb-major like horner2_lds_put
+__device__ __forceinline__ fr_t fr_block_sum(fr_t v, uint32_t* sh) {
+    v = fr_lanes_sum(v, 32);
+    const uint32_t nw = blockDim.x >> 6, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (nw == 1) return v;
+    if (lane == 0) {
+#pragma unroll
+        for (int l = 0; l < 9; l++) sh[l * nw + w] = v.v[l];
+    }
+    __syncthreads();
+    fr_t u = fr_t::zero();
+    if (lane < nw) {
+#pragma unroll
+        for (int l = 0; l < 9; l++) u.v[l] = sh[l * nw + lane];
+    }
+    return fr_lanes_sum(u, (int)(nw >> 1));
+}
+__device__ __forceinline__ fr_support_t fr_block_support(fr_support_t s, uint64_t* sh, size_t n) {
+    s = fr_lanes_support(s, 32);
+    const uint32_t nw = blockDim.x >> 6, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (nw == 1) return s;
+    if (lane == 0) sh[3 * w] = s.trimmed_len, sh[3 * w + 1] = s.leading_zeros, sh[3 * w + 2] = s.nonzero;
+    __syncthreads();
+    fr_support_t u = fr_support_identity(n);
+    if (lane < nw) u = fr_support_t{sh[3 * lane], sh[3 * lane + 1], sh[3 * lane + 2]};
+    return fr_lanes_support(u, (int)(nw >> 1));
+}
+// partials[y * gridDim.x + x]: the value of workgroup x over batch member y, internal limbs stored raw; b == nullptr for OP = SUM;
+// stride_b == 0: every member is multiplied by the same b
+template <int OP>
+static __global__ void __launch_bounds__(FR_REDUCE_B) fr_reduce_kernel(const fr_mem_t* __restrict__ a, const fr_mem_t* __restrict__ b, size_t n, size_t stride_a,
+                                                                       size_t stride_b, fr_mem_t* __restrict__ partials) {
+    __shared__ uint32_t sh[9 * (FR_REDUCE_B / 64)];
+    a += (size_t)blockIdx.y * stride_a;
+    if (OP == FR_REDUCE_DOT) b += (size_t)blockIdx.y * stride_b;
+    fr_t v = fr_reduce_thread<OP>(a, b, n, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+    v = fr_block_sum(v, sh);
+    if (threadIdx.x == 0) v.store(&partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x]);
+}
+// out[y] = the sum of member y's nparts partials, as a memory-form element; grid (1, members)
+static __global__ void __launch_bounds__(FR_REDUCE_B) fr_reduce_final_kernel(int op, const fr_mem_t* __restrict__ partials, size_t nparts, fr_mem_t* __restrict__ out) {
+    __shared__ uint32_t sh[9 * (FR_REDUCE_B / 64)];
+    fr_t v = fr_reduce_thread<FR_REDUCE_SUM>(partials + (size_t)blockIdx.y * nparts, nullptr, nparts, threadIdx.x, blockDim.x);
+    v = fr_block_sum(v, sh);
+    if (threadIdx.x == 0) fr_reduce_finish(op, v).store(&out[blockIdx.y]);
+}
+static __global__ void __launch_bounds__(FR_REDUCE_B) fr_support_kernel(const fr_mem_t* __restrict__ v, size_t n, size_t stride, uint64_t* __restrict__ partials) {
+    __shared__ uint64_t sh[3 * (FR_REDUCE_B / 64)];
+    fr_support_t s = fr_support_thread(v + (size_t)blockIdx.y * stride, n, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+    s = fr_block_support(s, sh, n);
+    if (threadIdx.x == 0) {
+        uint64_t* p = partials + 3 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
+        p[0] = s.trimmed_len, p[1] = s.leading_zeros, p[2] = s.nonzero;
+    }
+}
+static __global__ void __launch_bounds__(FR_REDUCE_B) fr_support_final_kernel(const uint64_t* __restrict__ partials, size_t nparts, size_t n, uint64_t* __restrict__ out) {
+    __shared__ uint64_t sh[3 * (FR_REDUCE_B / 64)];
+    fr_support_t s = fr_support_fold(partials + 3 * (size_t)blockIdx.y * nparts, nparts, n, threadIdx.x, blockDim.x);
+    s = fr_block_support(s, sh, n);
+    if (threadIdx.x == 0) {
+        uint64_t* p = out + 3 * (size_t)blockIdx.y;
+        p[0] = s.trimmed_len, p[1] = s.leading_zeros, p[2] = s.nonzero;
+    }
+}
+#endif
 
 }  // namespace sv

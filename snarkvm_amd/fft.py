@@ -173,6 +173,47 @@ class Evaluations:
     def interpolate_with_pc(self, pc=None):  # evaluations.rs:64-74: the precomputation is the device's own table
         return self.interpolate()
 
+    def evaluate_with_coeffs(self, lagrange_coefficients_at_point):
+        """evaluations.rs:90-92: sum_i e_i * L_i - one device inner product (`snarkvm_hip_fr_reduce`); the two vectors must have the same
+        length (zip_eq).  -> (1, 4)."""
+        from . import poly
+
+        return poly.inner_product(self.evaluations, lagrange_coefficients_at_point)
+
+    def evaluate(self, point):
+        """evaluations.rs:85-88: the interpolated polynomial at `point` without interpolating: every L_i(point) of the domain
+        (`snarkvm_hip_fr_lagrange_coefficients`, its point-in-domain branch included), then the inner product.  Evaluations shorter than
+        the domain count as zero-padded (from_vec_and_domain resizes, evaluations.rs:42-46)."""
+        from . import poly
+
+        coeffs = poly.evaluate_all_lagrange_coefficients(self.domain.size, point)
+        return poly.inner_product(self.domain._resized(self.evaluations), coeffs)
+
+    @staticmethod
+    def evaluate_with_coeffs_device(d_evaluations, d_lagrange_coefficients, n):
+        """`evaluate_with_coeffs` over two n-element vectors that live in device memory (raw pointers or objects with `.ptr`): nothing but
+        the 32-byte value returns to the host.  Inside a scope the call is only enqueued and the returned (1, 4) array is filled when the
+        scope ends."""
+        return plugin.fr_reduce_device(plugin.FR_REDUCE_DOT, _dev_ptr(d_evaluations), _dev_ptr(d_lagrange_coefficients), n)
+
+    @staticmethod
+    def evaluate_device(domain, d_evaluations, point, d_lagrange_coefficients):
+        """`evaluate` for evaluations resident in HBM: the domain's Lagrange coefficients at `point` are written to the device vector
+        `d_lagrange_coefficients` (domain.size elements, the caller's; they stay there for further `evaluate_with_coeffs_device` calls with the
+        same point - the three per matrix of snark/varuna/ahp/matrices.rs:117) and multiplied into `d_evaluations` (domain.size elements)."""
+        import ctypes
+
+        from . import _lib
+
+        tau = np.ascontiguousarray(point, dtype=np.uint64).reshape(1, 4)
+        _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(ctypes.c_void_p(_dev_ptr(d_lagrange_coefficients)), ctypes.c_uint32(domain.log_size_of_group),
+                                                                  ctypes.c_void_p(tau.ctypes.data), ctypes.c_int(1)))
+        return Evaluations.evaluate_with_coeffs_device(d_evaluations, d_lagrange_coefficients, domain.size)
+
+
+def _dev_ptr(x):
+    return int(getattr(x, "ptr", x))
+
 
 def evaluate_over_domain(coeffs, domain):
     """`Polynomial::evaluate_over_domain` for a dense polynomial (fft/polynomial/mod.rs:261-300).

@@ -186,6 +186,60 @@ class KZG10:
         return out, randomness
 
     @staticmethod
+    def commit_resident(powers, d_coeffs, n, hiding_bound=None, rng=None, degree_bound=None):
+        """`commit` for a coefficient vector that lives in HBM and is owned through the C ABI: `d_coeffs` is a device pointer (an int) or a
+        `devmem.HipMem`, `n` the number of Fr elements of the BUFFER - which may be longer than the polynomial (a full-domain product of
+        `polymul_device` always fills 2^lg elements; the reference trims it, multiplier.rs:93).  No torch.  One `snarkvm_hip_fr_support` pass
+        asks the device what `commit` asks the host vector:
+          - check_degree_is_too_large on the TRIMMED degree (mod.rs:104, 407-415);
+          - with `degree_bound`: the enforced-bound check `bound < degree` (mod.rs:439, IncorrectDegreeBound);
+          - skip_leading_zeros (mod.rs:455-467): the MSM runs over powers[lz .. trimmed_len) and the scalars from element lz on.
+        With hiding, the trimmed coefficients and the blinding coefficients are gathered into one scratch block (the two base ranges of the
+        MSM read consecutive scalars).  Same result as `commit` on the downloaded, trimmed vector.  The support is needed on the host at once,
+        so the call is refused inside a deferred-synchronisation scope."""
+        from . import plugin
+        from .devmem import HipMem
+
+        L = _lib.lib()
+        if L.snarkvm_hip_scope_stream():
+            raise PCError("commit_resident: the support of the polynomial is needed at once - not inside a scope")
+        ptr = int(getattr(d_coeffs, "ptr", d_coeffs))
+        trimmed_len, lz, _ = (int(x) for x in plugin.fr_support_device(ptr, n))
+        degree = max(trimmed_len, 1) - 1
+        if trimmed_len and degree + 1 > powers.size():  # check_degree_is_too_large (mod.rs:407-415)
+            raise PCError(f"TooManyCoefficients: {degree + 1} > {powers.size()}")
+        if degree_bound is not None and degree_bound < degree:  # check_degrees_and_bounds (mod.rs:439)
+            raise PCError(f"IncorrectDegreeBound: poly_degree {degree}, degree_bound {degree_bound}")
+        n0 = trimmed_len - lz if trimmed_len else 0
+        randomness = KZGRandomness.empty()
+        if hiding_bound is not None:
+            if rng is None:
+                raise PCError("MissingRng")
+            randomness = KZGRandomness.rand(hiding_bound, rng)
+            check_hiding_bound(randomness.degree(), powers.powers_of_beta_times_gamma_g.shape[0])
+        blind = np.ascontiguousarray(randomness.blinding_polynomial, dtype=np.uint64).reshape(-1, 4)
+        k = blind.shape[0]
+        out = np.zeros(1, dtype=G1_PROJECTIVE)
+        scratch = None
+        if n0 == 0:  # the zero polynomial: what `commit` does with it (host scalars: only the blinding coefficients, if any)
+            scalars, on_device, lz = ctypes.c_void_p(blind.ctypes.data), 0, 0
+        elif k:
+            scratch = HipMem(32 * (n0 + k))
+            scratch.copy_from(0, ptr + 32 * lz, 32 * n0)
+            scratch.upload(blind, 32 * n0)
+            scalars, on_device = ctypes.c_void_p(scratch.ptr), 1
+        else:
+            scalars, on_device = ctypes.c_void_p(ptr + 32 * lz), 1
+        try:
+            _lib.check(L.snarkvm_hip_msm_registered_ex(
+                ctypes.c_void_p(out.ctypes.data), powers._h, ctypes.c_size_t(lz), ctypes.c_size_t(n0), ctypes.c_size_t(powers._gamma_offset), ctypes.c_size_t(k),
+                scalars, ctypes.c_int(on_device), ctypes.c_int(1), ctypes.c_int(0)))
+        finally:
+            if scratch is not None:
+                scratch.free()
+        return out, randomness
+
+    @staticmethod
     def commit_lagrange(lagrange_basis, evaluations, hiding_bound=None, rng=None):
         """mod.rs:159-206: same MSM shape over `lagrange_basis_at_beta_g` (pass it as `Powers.powers_of_beta_g`);
         the evaluation vector is not trimmed and must fill the basis' power-of-two size."""

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -90,6 +90,47 @@ def fr_lincomb_device(d_out, n_out, d_polys, lens, coeffs):
     pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
     pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
     _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(ctypes.c_void_p(int(d_out) if d_out else None), int(n_out), k, pp, pl, _ptr(cs), 1))
+
+
+FR_REDUCE_SUM, FR_REDUCE_DOT = 0, 1  # include/snarkvm_hip.h: SNARKVM_HIP_FR_REDUCE_*
+
+
+def _dp(p):
+    return ctypes.c_void_p(int(p) if p else None)
+
+
+def fr_reduce_device(op, d_a, d_b, n):
+    """Extension (no reference counterpart): sum_i a[i] (op FR_REDUCE_SUM, d_b ignored) or sum_i a[i] * b[i] (FR_REDUCE_DOT) over n-element
+    vectors that live in device memory (`snarkvm_hip_fr_reduce`, on_device = 1) -> (1, 4) Montgomery limbs on the host.  No operand is
+    written; d_a may equal d_b.  Inside a scope the call is only enqueued and the returned array is filled when the scope ends: keep it
+    alive until then."""
+    out = np.zeros((1, 4), dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_reduce(int(op), _ptr(out), _dp(d_a), _dp(d_b), int(n), 1))
+    return out
+
+
+def fr_reduce_strided_device(op, d_a, d_b, n, count, stride, b_shared=False):
+    """The same over `count` vectors `stride` >= n elements apart (`snarkvm_hip_fr_reduce_strided`) -> (count, 4).  b_shared: every member
+    is multiplied by the one vector at d_b (the three `evaluate_with_coeffs` of one matrix); otherwise d_b advances like d_a."""
+    out = np.zeros((int(count), 4), dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_reduce_strided(int(op), _ptr(out), _dp(d_a), _dp(d_b), int(n), int(count), int(stride), 1 if b_shared else 0))
+    return out
+
+
+def fr_support_device(d_v, n):
+    """Extension: (trimmed_len, leading_zeros, nonzero) of an n-element device vector as a (3,) uint64 array (`snarkvm_hip_fr_support`,
+    on_device = 1): index of the last non-zero element + 1 (0: the zero vector), index of the first non-zero element (n: the zero vector),
+    number of non-zero elements.  Inside a scope the array is filled when the scope ends."""
+    out = np.zeros(3, dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_support(_ptr(out), _dp(d_v), int(n), 1))
+    return out
+
+
+def fr_support_strided_device(d_v, n, count, stride):
+    """The same over `count` vectors `stride` >= n elements apart (`snarkvm_hip_fr_support_strided`) -> (count, 3) uint64."""
+    out = np.zeros((int(count), 3), dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_support_strided(_ptr(out), _dp(d_v), int(n), int(count), int(stride)))
+    return out
 
 
 def msm(points, scalars):

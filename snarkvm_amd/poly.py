@@ -5,6 +5,8 @@ Host mirror of the reference functions the Varuna prover runs between its NTTs a
     DensePolynomial::{evaluate, mul_by_vanishing_poly, divide_by_vanishing_poly}   fft/polynomial/dense.rs:98-114, 153-169
     `polynomial / (X - point)` (Polynomial::divide_with_q_and_r)                    fft/polynomial/mod.rs:222-256
     `poly += (coeff, cur_poly)` over the terms of a linear combination              polycommit/sonic_pc/mod.rs:413-473, 548-564
+    Evaluations::evaluate_with_coeffs (an inner product), sums over a domain        fft/evaluations.rs:90-92, round_functions/first.rs:119
+    DensePolynomial::{degree, is_zero}, skip_leading_zeros_and_convert_to_bigints   fft/polynomial/dense.rs:66-96, kzg10/mod.rs:455-467
     batch_inversion / batch_inversion_and_mul                                       fields/src/lib.rs:66-129
     EvaluationDomain::{distribute_powers_and_mul_by_const,
                        evaluate_all_lagrange_coefficients}                          fft/domain.rs:224-292
@@ -66,6 +68,35 @@ def lincomb(coeffs, polys):
     lens = (ctypes.c_size_t * max(1, k))(*[p.shape[0] for p in polys])
     _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(_p(out), n, k, ptrs, lens, _p(cs), 0))
     return trim(out)
+
+
+def inner_product(a, b):
+    """sum_i a[i] * b[i] in one device pass (`snarkvm_hip_fr_reduce`, op DOT): Evaluations::evaluate_with_coeffs (evaluations.rs:90-92,
+    which zips with zip_eq).  -> (1, 4)."""
+    a, b = _v(a), _v(b)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("length mismatch")
+    out = np.zeros((1, 4), dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_reduce(1, _p(out), _p(a) if a.shape[0] else None, _p(b) if a.shape[0] else None, a.shape[0], 0))
+    return out
+
+
+def vec_sum(a):
+    """sum_i a[i] in one device pass (`snarkvm_hip_fr_reduce`, op SUM) -> (1, 4)."""
+    a = _v(a)
+    out = np.zeros((1, 4), dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_reduce(0, _p(out), _p(a) if a.shape[0] else None, None, a.shape[0], 0))
+    return out
+
+
+def support(v):
+    """(trimmed_len, leading_zeros, nonzero) of a coefficient vector in one device pass (`snarkvm_hip_fr_support`): the length
+    DensePolynomial::from_coefficients_vec would keep (degree = max(trimmed_len, 1) - 1, is_zero = trimmed_len == 0), the number of leading
+    zero coefficients a commitment skips (len(v) for the zero vector), the number of non-zero coefficients."""
+    v = _v(v)
+    out = np.zeros(3, dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_support(_p(out), _p(v) if v.shape[0] else None, v.shape[0], 0))
+    return tuple(int(x) for x in out)
 
 
 def divide_by_linear(coeffs, point):
