@@ -170,7 +170,7 @@ RustError snarkvm_hip_polymul_device(void *d_out, size_t pcount, const void *con
 /* Deferred synchronisation for device-resident operands.  Between snarkvm_hip_scope_begin (d_any: any device pointer on the GPU
  * to use, or NULL for any GPU) and snarkvm_hip_scope_end, calls of THIS thread whose operands and results live in device memory
  * - snarkvm_hip_ntt_device, _ntt_device_batch, _polymul_device, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
- * kernels (snarkvm_hip_fr_lincomb among them) with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
+ * kernels (snarkvm_hip_fr_lincomb and snarkvm_hip_fr_spmv among them) with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
  * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end, and so are the host results of
  * snarkvm_hip_fr_reduce[_strided] and snarkvm_hip_fr_support[_strided] over device operands (the same mechanism: parked in pinned memory, copied
  * to the caller's buffer when the scope is flushed - the buffer must stay valid until then).  Every other call (MSMs,
@@ -412,6 +412,43 @@ RustError snarkvm_hip_fr_reduce_strided(int op, void *results, const void *a, co
 RustError snarkvm_hip_fr_support(uint64_t *out3, const void *v, size_t n, int on_device);
 RustError snarkvm_hip_fr_support_strided(uint64_t *out, const void *v, size_t n, size_t count, size_t stride);
 
+/* Sparse matrix times vector over a REGISTERED matrix (csrc/poly.hip.h: fr_spmv_seg_kernel, fr_spmv_fix_kernel): the one product of the Varuna
+ * prover that is not dense - z_M = M z for M in {A, B, C} (snark/varuna/ahp/prover/round_functions/mod.rs:131-188) and M(alpha, .) = M^T l_alpha
+ * (third.rs:303-306, with l_alpha left in device memory by snarkvm_hip_fr_lagrange_coefficients and the result going on to snarkvm_hip_ntt_device).
+ * The matrices are circuit data, fixed for the life of a proving key like the SRS: register once, multiply many times.
+ * fr_matrix_register: CSR - row r owns entries row_ptr[r] .. row_ptr[r+1]-1 (row_ptr: rows + 1 values); entry k is vals[k] (32 bytes, Montgomery
+ * form) at column col_idx[k].  Host arrays, not retained.  Duplicate columns inside a row, rows of any length (empty ones too), rows == 0 and no
+ * entries at all are legal; values are not checked to be < r (they are treated like every other Fr operand).  At registration every row is cut
+ * into segments of at most S entries and the segment table is uploaded with the entries; one replica per device of the current device set, like
+ * registered bases.
+ *  - Refused with hipErrorInvalidValue BEFORE a device is needed and before anything is allocated (*handle, when given, is NULL afterwards): a NULL
+ *    handle; a NULL row_ptr, or NULL col_idx / vals of a matrix with entries; row_ptr[0] != 0; a decreasing row_ptr; row_ptr[rows] > 2^32 - 1;
+ *    rows or cols > 2^28; any col_idx[k] >= cols.  So no index the kernels ever see points outside x.
+ * fr_matrix_free: NULL is a no-op.  The replicas are released with hipFree, which returns only when every stream of their device is idle - what
+ * snarkvm_hip_free does for device blocks: freeing a handle while a scope of the calling thread still has a product enqueued is safe (the call
+ * waits for that product; its result is delivered as usual).
+ * fr_spmv: y[r] = sum_k vals[k] * x[col_idx[k]] over row r for r < rows, y[r] = 0 for rows <= r < n_out - ALL n_out elements of every member are
+ * written (empty rows give zero), so that z_M lands in a domain-sized buffer that goes straight into snarkvm_hip_ntt_device.  Member m of a batch
+ * of `count` reads x + m * stride_x and writes y + m * stride_y (elements); stride_x == 0: every member reads the one x.  count == 1: the strides
+ * are ignored.
+ *  - on_device = 1: x and y are device pointers on one device; inside a snarkvm_hip_scope the call is only enqueued.  on_device = 0: host
+ *    operands, staged like the other passes, the result is there on return.  x is never written.
+ *  - Refused with hipErrorInvalidValue, y untouched: a NULL handle; n_out < rows; n_out > 2^28; count > 65535; count > 1 with
+ *    0 < stride_x < cols or stride_y < n_out, or a stride of more than 2^40 elements; a NULL y, or a NULL x of a matrix with entries; with on_device = 1 a y that overlaps x (rows are
+ *    owned by different waves: an in-place product races) and operands on different devices.
+ *  - count == 0, or n_out == 0 for a matrix without rows: success, nothing is touched, no device is needed (n_out == 0 for a matrix WITH rows is
+ *    n_out < rows and refused like it).
+ *  - No atomics, a fixed order of additions; since field addition is exact and results canonical the 32 bytes of y[r] depend on neither the
+ *    segment size, the lane-group width nor the grid.
+ *  - Workspace (one partial sum per segment of every row with more than one, per member) comes from the calling lane; a repeated call grows
+ *    nothing (snarkvm_hip_alloc_stats). */
+typedef struct snarkvm_hip_fr_matrix snarkvm_hip_fr_matrix_t;
+RustError snarkvm_hip_fr_matrix_register(snarkvm_hip_fr_matrix_t **handle, size_t rows, size_t cols, const uint64_t *row_ptr, const uint32_t *col_idx,
+                                         const void *vals);
+void snarkvm_hip_fr_matrix_free(snarkvm_hip_fr_matrix_t *handle);
+RustError snarkvm_hip_fr_spmv(void *y, size_t n_out, const snarkvm_hip_fr_matrix_t *handle, const void *x, size_t count, size_t stride_x, size_t stride_y,
+                              int on_device);
+
 /* Strided batches of the passes above on device memory - the same pass over one vector of every proof of a batch proved in lock
  * step (VarunaSNARK::prove_batch, snark/varuna/varuna.rs:336): member y of the batch uses every vector pointer advanced by
  * y * stride elements (stride >= the vector length); ONE kernel launch sequence for the whole batch.  fr_vec_op_strided: `scalar`
@@ -517,6 +554,14 @@ int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const
 int snarkvm_hip_selftest_fr_reduce(int op, void *out, const void *a, const void *b, size_t n, uint32_t blocks, uint32_t threads);
 int snarkvm_hip_selftest_fr_support(uint64_t *out3, const void *v, size_t n, uint32_t blocks, uint32_t threads);
 int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t *out4);
+/* snarkvm_hip_fr_spmv (count = 1) over host memory with the CPU in the kernels' place, for a GIVEN segment size `seg` >= 1 and lane-group width
+ * (4, 8, 16 or 64): the validation and the segmentation of snarkvm_hip_fr_matrix_register, every lane through the kernels' own accumulate routine
+ * (csrc/poly.hip.h: fr_spmv_lane over Fp::sum_of_products), the butterfly level by level, the partials and the fix-up launch in the same order.  0, or
+ * -1 when the arguments are refused.  fr_spmv_geometry: out4 = {segment size S, lane-group width, threads per workgroup, segments} of what
+ * registration lays out for a matrix of `rows` rows whose nnz entries are spread evenly (the first nnz % rows rows hold one more). */
+int snarkvm_hip_selftest_fr_spmv(void *y, size_t n_out, size_t rows, size_t cols, const uint64_t *row_ptr, const uint32_t *col_idx, const void *vals,
+                                 const void *x, uint32_t seg, uint32_t width);
+int snarkvm_hip_selftest_fr_spmv_geometry(size_t rows, size_t nnz, uint32_t *out4);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 /* Field arithmetic that the two operands of snarkvm_hip_selftest_field cannot express, one case per record, operands and results in memory

@@ -243,4 +243,27 @@ private:
     size_t n_;
 };
 
+// A registered sparse matrix (snarkvm_hip.h: snarkvm_hip_fr_matrix_register, snarkvm_hip_fr_spmv): the CSR arrays of an R1CS matrix or of its
+// transpose go to HBM once per proving key; mul() is z_M = M z (round_functions/mod.rs:131-188) or M(alpha, .) = M^T l_alpha (third.rs:303-306)
+// on host or device vectors.  All n_out >= rows elements of y are written; y must not overlap x.
+class RegisteredMatrix {
+public:
+    RegisteredMatrix(size_t rows, size_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals) : rows_(rows), cols_(cols) {
+        check(snarkvm_hip_fr_matrix_register(&h_, rows, cols, row_ptr, col_idx, vals));
+    }
+    RegisteredMatrix(const RegisteredMatrix&) = delete;
+    RegisteredMatrix& operator=(const RegisteredMatrix&) = delete;
+    ~RegisteredMatrix() { snarkvm_hip_fr_matrix_free(h_); }  // waits for the device: safe with a product still enqueued in this thread's Scope
+    size_t rows() const { return rows_; }
+    size_t cols() const { return cols_; }
+    const snarkvm_hip_fr_matrix_t* handle() const { return h_; }
+    void mul(void* y, size_t n_out, const void* x, bool on_device, size_t count = 1, size_t stride_x = 0, size_t stride_y = 0) const {
+        check(snarkvm_hip_fr_spmv(y, n_out, h_, x, count, stride_x, stride_y, on_device ? 1 : 0));
+    }
+
+private:
+    snarkvm_hip_fr_matrix_t* h_ = nullptr;
+    size_t rows_, cols_;
+};
+
 }  // namespace snarkvm_hip

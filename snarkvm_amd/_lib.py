@@ -22,13 +22,14 @@ SYMBOLS = [
     "snarkvm_hip_fr_distribute_powers", "snarkvm_hip_fr_lagrange_coefficients", "snarkvm_hip_fr_divide_by_vanishing",
     "snarkvm_hip_fr_mul_by_vanishing", "snarkvm_hip_fr_lincomb",
     "snarkvm_hip_fr_reduce", "snarkvm_hip_fr_reduce_strided", "snarkvm_hip_fr_support", "snarkvm_hip_fr_support_strided",
+    "snarkvm_hip_fr_matrix_register", "snarkvm_hip_fr_matrix_free", "snarkvm_hip_fr_spmv",
     "snarkvm_hip_fr_vec_op_strided", "snarkvm_hip_fr_divide_by_linear_strided", "snarkvm_hip_fr_divide_by_vanishing_strided",
     "snarkvm_hip_register_bases_serialized", "snarkvm_hip_g1_deserialize", "snarkvm_hip_g1_serialize", "snarkvm_hip_g1_sum", "snarkvm_hip_g2_deserialize", "snarkvm_hip_g2_serialize", "snarkvm_hip_g2_deserialize_compressed", "snarkvm_hip_g2_serialize_compressed",
     "snarkvm_hip_register_bases_g2", "snarkvm_hip_free_bases_g2", "snarkvm_hip_msm_g2_registered", "snarkvm_hip_msm_g2_registered_batch",
     "snarkvm_hip_g1_fixed_base_msm", "snarkvm_hip_g1_group_ntt",
     "snarkvm_hip_set_profiling", "snarkvm_hip_get_phase_count", "snarkvm_hip_get_phase_name",
     "snarkvm_hip_get_phase_ms", "snarkvm_hip_synchronize", "snarkvm_hip_coalescer_stats",
-    "snarkvm_hip_selftest_field", "snarkvm_hip_selftest_g1_msm_naive", "snarkvm_hip_selftest_msm_plan", "snarkvm_hip_selftest_g1_finish", "snarkvm_hip_selftest_fq_lazy", "snarkvm_hip_selftest_g1_lazy_tail", "snarkvm_hip_selftest_ntt_plan", "snarkvm_hip_selftest_ntt_twiddle", "snarkvm_hip_selftest_ntt_index", "snarkvm_hip_selftest_ntt_host", "snarkvm_hip_selftest_fq2_pair", "snarkvm_hip_selftest_g2_hex", "snarkvm_hip_selftest_fr_lincomb", "snarkvm_hip_selftest_fr_reduce", "snarkvm_hip_selftest_fr_support", "snarkvm_hip_selftest_fr_reduce_geometry", "snarkvm_hip_devtest_field", "snarkvm_hip_devtest_g2_tail_repeat", "snarkvm_hip_selftest_field_ext", "snarkvm_hip_devtest_field_ext",
+    "snarkvm_hip_selftest_field", "snarkvm_hip_selftest_g1_msm_naive", "snarkvm_hip_selftest_msm_plan", "snarkvm_hip_selftest_g1_finish", "snarkvm_hip_selftest_fq_lazy", "snarkvm_hip_selftest_g1_lazy_tail", "snarkvm_hip_selftest_ntt_plan", "snarkvm_hip_selftest_ntt_twiddle", "snarkvm_hip_selftest_ntt_index", "snarkvm_hip_selftest_ntt_host", "snarkvm_hip_selftest_fq2_pair", "snarkvm_hip_selftest_g2_hex", "snarkvm_hip_selftest_fr_lincomb", "snarkvm_hip_selftest_fr_reduce", "snarkvm_hip_selftest_fr_support", "snarkvm_hip_selftest_fr_reduce_geometry", "snarkvm_hip_selftest_fr_spmv", "snarkvm_hip_selftest_fr_spmv_geometry", "snarkvm_hip_devtest_field", "snarkvm_hip_devtest_g2_tail_repeat", "snarkvm_hip_selftest_field_ext", "snarkvm_hip_devtest_field_ext",
 ]
 
 
@@ -73,6 +74,7 @@ def lib():
                    "snarkvm_hip_fr_convert_device", "snarkvm_hip_g1_generate_bases_device", "snarkvm_hip_synchronize",
                    "snarkvm_hip_fr_vec_op", "snarkvm_hip_fr_divide_by_linear", "snarkvm_hip_fr_batch_inversion_and_mul", "snarkvm_hip_fr_distribute_powers", "snarkvm_hip_fr_lagrange_coefficients", "snarkvm_hip_fr_divide_by_vanishing", "snarkvm_hip_fr_mul_by_vanishing", "snarkvm_hip_fr_lincomb",
                    "snarkvm_hip_fr_reduce", "snarkvm_hip_fr_reduce_strided", "snarkvm_hip_fr_support", "snarkvm_hip_fr_support_strided",
+                   "snarkvm_hip_fr_matrix_register", "snarkvm_hip_fr_spmv",
                    "snarkvm_hip_fr_vec_op_strided", "snarkvm_hip_fr_divide_by_linear_strided", "snarkvm_hip_fr_divide_by_vanishing_strided",
                    "snarkvm_hip_register_bases_serialized", "snarkvm_hip_g1_deserialize", "snarkvm_hip_g1_serialize", "snarkvm_hip_g1_sum", "snarkvm_hip_g2_deserialize", "snarkvm_hip_g2_serialize", "snarkvm_hip_g2_deserialize_compressed", "snarkvm_hip_g2_serialize_compressed",
                    "snarkvm_hip_register_bases_g2", "snarkvm_hip_msm_g2_registered", "snarkvm_hip_msm_g2_registered_batch",
@@ -132,6 +134,15 @@ def lib():
         L.snarkvm_hip_selftest_fr_reduce_geometry.argtypes = [ctypes.c_size_t, ctypes.c_void_p]
         for name in ("snarkvm_hip_selftest_fr_reduce", "snarkvm_hip_selftest_fr_support", "snarkvm_hip_selftest_fr_reduce_geometry"):
             getattr(L, name).restype = ctypes.c_int
+        L.snarkvm_hip_fr_matrix_register.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.snarkvm_hip_fr_matrix_free.argtypes = [ctypes.c_void_p]
+        L.snarkvm_hip_fr_matrix_free.restype = None
+        L.snarkvm_hip_fr_spmv.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]
+        L.snarkvm_hip_selftest_fr_spmv.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint32, ctypes.c_uint32]
+        L.snarkvm_hip_selftest_fr_spmv_geometry.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+        L.snarkvm_hip_selftest_fr_spmv.restype = ctypes.c_int
+        L.snarkvm_hip_selftest_fr_spmv_geometry.restype = ctypes.c_int
         _libc = ctypes.CDLL(None)
         _libc.free.argtypes = [ctypes.c_void_p]
         _lib = L

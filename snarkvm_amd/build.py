@@ -65,7 +65,7 @@ def _kept_object_is_current(obj, src, flags):
 TSAN_LIB = os.path.join(LIBDIR, "libsnarkvm_hip_tsan.so")
 
 
-def build(force=False, verbose=False, fast=False, only=None, ool=False, tsan=False):
+def build(force=False, verbose=False, fast=False, only=None, ool=False, tsan=False, defines=(), out=None):
     """fast=True (development only) compiles without the G2 / Fq2 instantiations.  ool=True (A/B switch): every exceptional
     path out of line (-DSV_COLD_OOL): kernels a few percent slower, see ff.hip.h.  only=[...] (development only): recompile just
     the listed translation units and link them with the objects kept from the last build of THIS checkout with THESE flags -
@@ -73,9 +73,14 @@ def build(force=False, verbose=False, fast=False, only=None, ool=False, tsan=Fal
     always compiles everything.
     tsan=True (diagnostics: tools/soak.py --tsan): the HOST side of every unit compiled with -fsanitize=thread (device code untouched) into a SEPARATE library,
     lib/libsnarkvm_hip_tsan.so - never the product library; a process that loads it needs the ThreadSanitizer runtime (an instrumented executable, or
-    LD_PRELOAD of clang's libclang_rt.tsan-x86_64.so)."""
-    out_lib = TSAN_LIB if tsan else LIB
-    if not tsan and not force and not only and not needs_build():
+    LD_PRELOAD of clang's libclang_rt.tsan-x86_64.so).
+    defines=["NAME=VALUE", ...] with out=PATH (measurement variants: tools/bench_fr_spmv.py --variant): every unit compiled with -DNAME=VALUE into the
+    library PATH - never the product library; objects in a directory of their own (the flags are part of its key)."""
+    defines = list(defines)
+    if bool(defines) != bool(out) or (defines and (tsan or only)):
+        raise ValueError("build: defines and out go together, and with neither tsan nor only")
+    out_lib = os.path.abspath(out) if out else (TSAN_LIB if tsan else LIB)
+    if not tsan and not force and not only and not defines and not needs_build():
         return LIB
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -86,6 +91,9 @@ def build(force=False, verbose=False, fast=False, only=None, ool=False, tsan=Fal
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-pass-failed"] + (["-DSV_NO_G2"] if fast else []) + (["-DSV_COLD_OOL"] if ool else [])
     if tsan:
         flags += ["-Xarch_host", "-fsanitize=thread", "-Xarch_host", "-g"]
+    flags += ["-D" + d for d in defines]
+    if out:
+        os.makedirs(os.path.dirname(out_lib), exist_ok=True)
     objdir = _objdir(flags)
     os.makedirs(objdir, mode=0o700, exist_ok=True)
     if os.path.islink(objdir) or os.stat(objdir).st_uid != os.getuid():
@@ -120,4 +128,6 @@ def build(force=False, verbose=False, fast=False, only=None, ool=False, tsan=Fal
 
 if __name__ == "__main__":
     only = [a for a in sys.argv[1:] if a.endswith(".hip")]
-    print(build(force="--force" in sys.argv, verbose=True, fast="--fast" in sys.argv, only=only or None, ool="--ool" in sys.argv, tsan="--tsan" in sys.argv))
+    defines = [a[2:] for a in sys.argv[1:] if a.startswith("-D")]  # python -m snarkvm_amd.build -DFR_SPMV_SEG=512 --out=PATH
+    out = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
+    print(build(force="--force" in sys.argv, verbose=True, fast="--fast" in sys.argv, only=only or None, ool="--ool" in sys.argv, tsan="--tsan" in sys.argv, defines=defines, out=out))

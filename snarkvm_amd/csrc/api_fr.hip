@@ -834,6 +834,217 @@ int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t* out4) {
     return 0;
 }
 
+// ---- sparse matrix times vector over a registered matrix (poly.hip.h: fr_spmv_seg_kernel, fr_spmv_fix_kernel) ----------------------
+static constexpr size_t FR_SPMV_DIM_MAX = (size_t)1 << NTT_LG_MAX;  // rows, cols, n_out: the SRS maximum the transforms stop at
+// nullptr, or why the CSR arrays are refused (hipErrorInvalidValue).  Needs no device and touches nothing: after it no index the kernels will
+// ever see can point outside x (cols elements), vals or col_idx.
+static const char* fr_spmv_matrix_check(size_t rows, size_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals) {
+    if (rows > FR_SPMV_DIM_MAX || cols > FR_SPMV_DIM_MAX) return "more than 2^28 rows or columns";
+    if (!row_ptr) return "null row_ptr";
+    if (row_ptr[0] != 0) return "row_ptr[0] != 0";
+    for (size_t r = 0; r < rows; r++)
+        if (row_ptr[r + 1] < row_ptr[r]) return "row_ptr decreases";
+    const uint64_t nnz = row_ptr[rows];
+    if (nnz > 0xFFFFFFFFull) return "more than 2^32 - 1 entries";
+    if (nnz && (!col_idx || !vals)) return "null col_idx or vals of a matrix with entries";
+    for (uint64_t k = 0; k < nnz; k++)
+        if (col_idx[k] >= cols) return "a column index is not below cols";
+    return nullptr;
+}
+// the work layout of a checked matrix for segments of at most `seg` entries -> number of partial-sum slots
+static size_t fr_spmv_layout(size_t rows, const uint64_t* row_ptr, uint32_t seg, std::vector<fr_spmv_seg_t>& segs, std::vector<fr_spmv_fix_t>& fix) {
+    size_t nparts = 0;
+    for (size_t r = 0; r < rows; r++) {
+        const uint64_t first = row_ptr[r], len = row_ptr[r + 1] - first;
+        const uint64_t pieces = (len + seg - 1) / seg;
+        if (pieces != 1) fix.push_back({(uint32_t)r, (uint32_t)nparts, (uint32_t)pieces, 0});
+        for (uint64_t p = 0; p < pieces; p++) {
+            const uint64_t at = p * seg;
+            segs.push_back({(uint32_t)r, (uint32_t)(first + at), (uint32_t)(len - at < seg ? len - at : seg), pieces == 1 ? FR_SPMV_SOLE : (uint32_t)(nparts + p)});
+        }
+        if (pieces > 1) nparts += pieces;
+    }
+    return nparts;
+}
+}  // extern "C"
+// one replica per logical device, like registered bases: ONE block holding vals | segment table | fix-up table | col_idx
+struct snarkvm_hip_fr_matrix {
+    size_t rows = 0, cols = 0, nnz = 0, nseg = 0, nfix = 0, nparts = 0;
+    uint32_t seg = 0, width = 0;
+    std::vector<uint8_t*> d;  // [logical device]
+    size_t off_segs = 0, off_fix = 0, off_col = 0, bytes = 0;
+    const fr_mem_t* vals(int dev) const { return (const fr_mem_t*)d[dev]; }
+    const fr_spmv_seg_t* segs(int dev) const { return (const fr_spmv_seg_t*)(d[dev] + off_segs); }
+    const fr_spmv_fix_t* fix(int dev) const { return (const fr_spmv_fix_t*)(d[dev] + off_fix); }
+    const uint32_t* col(int dev) const { return (const uint32_t*)(d[dev] + off_col); }
+    void free_all() {
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        for (size_t i = 0; i < d.size(); i++)
+            if (d[i]) {
+                (void)hipSetDevice(g_rt.devs[i]->physical);
+                (void)hipFree(d[i]);  // waits for every stream of the device: nothing queued - an open scope's product included - can still use the block
+                d[i] = nullptr;
+            }
+        (void)hipSetDevice(prev);
+    }
+};
+template <int W>
+static void fr_spmv_launch(lane_t& c, const snarkvm_hip_fr_matrix& h, int dev, const fr_mem_t* dx, size_t stride_x, fr_mem_t* dy, size_t stride_y, size_t n_out,
+                           size_t count, fr_mem_t* parts) {
+    const size_t per_block = FR_SPMV_B / W;
+    if (h.nseg)
+        hipLaunchKernelGGL(fr_spmv_seg_kernel<W>, dim3((unsigned)((h.nseg + per_block - 1) / per_block), (unsigned)count), dim3(FR_SPMV_B), 0, c.stream, h.segs(dev), h.nseg,
+                           h.vals(dev), h.col(dev), dx, stride_x, dy, stride_y, parts, h.nparts);
+    const size_t groups = h.nfix + (n_out - h.rows);
+    if (groups)
+        hipLaunchKernelGGL(fr_spmv_fix_kernel<W>, dim3((unsigned)((groups + per_block - 1) / per_block), (unsigned)count), dim3(FR_SPMV_B), 0, c.stream, h.fix(dev), h.nfix,
+                           (const fr_mem_t*)parts, h.nparts, dy, stride_y, h.rows, n_out);
+}
+extern "C" {
+RustError snarkvm_hip_fr_matrix_register(snarkvm_hip_fr_matrix_t** handle, size_t rows, size_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals) {
+    if (!handle) return fail((int)hipErrorInvalidValue, "snarkvm_hip: fr_matrix_register: null handle");
+    *handle = nullptr;
+    if (const char* why = fr_spmv_matrix_check(rows, cols, row_ptr, col_idx, vals)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_matrix_register: ") + why);
+    API_TRY
+    std::unique_ptr<snarkvm_hip_fr_matrix> h(new snarkvm_hip_fr_matrix());
+    std::vector<fr_spmv_seg_t> segs;
+    std::vector<fr_spmv_fix_t> fix;
+    h->rows = rows, h->cols = cols, h->nnz = (size_t)row_ptr[rows], h->seg = FR_SPMV_SEG;
+    h->nparts = fr_spmv_layout(rows, row_ptr, h->seg, segs, fix);
+    h->nseg = segs.size(), h->nfix = fix.size();
+    h->width = fr_spmv_width(h->nnz, h->nseg);
+    h->off_segs = sizeof(fr_mem_t) * h->nnz;
+    h->off_fix = h->off_segs + sizeof(fr_spmv_seg_t) * h->nseg;
+    h->off_col = h->off_fix + sizeof(fr_spmv_fix_t) * h->nfix;
+    h->bytes = h->off_col + sizeof(uint32_t) * h->nnz;
+    const int nd = g_rt.ndev();
+    h->d.assign(nd, nullptr);
+    try {
+        std::vector<int> all;
+        for (int d = 0; d < nd; d++) all.push_back(d);
+        for_each_device(all, [&](int dev) {  // every device uploads its own replica
+            lane_guard lg(dev);
+            lane_t& c = lg.c();
+            HIP_TRY(hipMalloc((void**)&h->d[dev], h->bytes ? h->bytes : 32));
+            uint8_t* d = h->d[dev];
+            if (h->nnz) HIP_TRY(hipMemcpyAsync(d, vals, sizeof(fr_mem_t) * h->nnz, hipMemcpyHostToDevice, c.stream));
+            if (h->nseg) HIP_TRY(hipMemcpyAsync(d + h->off_segs, segs.data(), sizeof(fr_spmv_seg_t) * h->nseg, hipMemcpyHostToDevice, c.stream));
+            if (h->nfix) HIP_TRY(hipMemcpyAsync(d + h->off_fix, fix.data(), sizeof(fr_spmv_fix_t) * h->nfix, hipMemcpyHostToDevice, c.stream));
+            if (h->nnz) HIP_TRY(hipMemcpyAsync(d + h->off_col, col_idx, sizeof(uint32_t) * h->nnz, hipMemcpyHostToDevice, c.stream));
+            HIP_TRY(hipStreamSynchronize(c.stream));
+        });
+    } catch (...) {
+        h->free_all();
+        throw;
+    }
+    *handle = h.release();
+    API_CATCH
+}
+void snarkvm_hip_fr_matrix_free(snarkvm_hip_fr_matrix_t* h) {
+    if (!h) return;
+    h->free_all();
+    delete h;
+}
+// nullptr, or why the product is refused (hipErrorInvalidValue); needs no device
+static const char* fr_spmv_check(const void* y, size_t n_out, const snarkvm_hip_fr_matrix* h, const void* x, size_t count, size_t stride_x, size_t stride_y, int on_device) {
+    if (!h) return "null handle";
+    if (n_out < h->rows) return "n_out is less than the number of rows";
+    if (n_out > FR_SPMV_DIM_MAX) return "n_out > 2^28";
+    if (count > 65535) return "more than 65535 batch members";
+    if (count > 1 && ((stride_x && stride_x < h->cols) || stride_y < n_out)) return "a stride is shorter than its vector";
+    // count < 2^16 members of at most 2^40 elements apart: no span below can wrap, in elements or in bytes
+    if (count > 1 && (stride_x > ((size_t)1 << 40) || stride_y > ((size_t)1 << 40))) return "a stride of more than 2^40 elements";
+    if (!y || (!x && h->nnz)) return "null operand";
+    if (on_device) {
+        const size_t span_x = h->cols ? (count - 1) * stride_x + h->cols : 0, span_y = (count - 1) * stride_y + n_out;
+        const uint8_t *px = (const uint8_t*)x, *py = (const uint8_t*)y;
+        if (px && span_x && px < py + sizeof(fr_mem_t) * span_y && py < px + sizeof(fr_mem_t) * span_x) return "y overlaps x (rows are owned by different waves: an in-place product races)";
+    }
+    return nullptr;
+}
+RustError snarkvm_hip_fr_spmv(void* y, size_t n_out, const snarkvm_hip_fr_matrix_t* h, const void* x, size_t count, size_t stride_x, size_t stride_y, int on_device) {
+    if (h && (count == 0 || (n_out == 0 && h->rows == 0))) return ok();
+    if (const char* why = fr_spmv_check(y, n_out, h, x, count, stride_x, stride_y, on_device)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_spmv: ") + why);
+    if (count == 1) stride_x = stride_y = 0;
+    API_BEGIN_DEV(device_for(y, on_device ? 1 : 0))
+    const int dev = c.dev->logical;
+    if (dev >= (int)h->d.size() || !h->d[dev]) throw hip_failure{hipErrorInvalidValue, "fr_spmv: the matrix has no replica on this device", __LINE__};
+    const fr_mem_t* dx = (const fr_mem_t*)x;
+    fr_mem_t* dy = (fr_mem_t*)y;
+    size_t sx = stride_x, sy = stride_y;
+    if (on_device) {
+        fr_same_device(c, x, "fr_spmv: x lives on another device than y");
+    } else {
+        // host operands: x as it lies (members and the gaps between them), y packed member after member and downloaded member by member
+        dx = fr_stage_in(c, 0, x, h->cols ? (count - 1) * stride_x + h->cols : 0, 0);
+        dy = fr_stage_out(c, 1, y, count * n_out, 0);
+        sy = n_out;
+    }
+    c.poly[4].ensure(sizeof(fr_mem_t) * (count * h->nparts ? count * h->nparts : 1));
+    fr_mem_t* parts = c.poly[4].as<fr_mem_t>();
+    switch (h->width) {
+        case 4: fr_spmv_launch<4>(c, *h, dev, dx, sx, dy, sy, n_out, count, parts); break;
+        case 8: fr_spmv_launch<8>(c, *h, dev, dx, sx, dy, sy, n_out, count, parts); break;
+        case 16: fr_spmv_launch<16>(c, *h, dev, dx, sx, dy, sy, n_out, count, parts); break;
+        default: fr_spmv_launch<64>(c, *h, dev, dx, sx, dy, sy, n_out, count, parts); break;
+    }
+    HIP_TRY(hipGetLastError());
+    if (!on_device)
+        for (size_t m = 0; m < count; m++) HIP_TRY(hipMemcpyAsync((fr_mem_t*)y + m * stride_y, dy + m * n_out, sizeof(fr_mem_t) * n_out, hipMemcpyDeviceToHost, c.stream));
+    fr_call_done(c, on_device);
+    API_END
+}
+// The product on host memory with the CPU in the kernels' place, for a GIVEN segment size and lane-group width: the same validation and layout,
+// every lane of every segment through fr_spmv_lane, the butterfly level by level over the lanes it exchanges between, the partials, the fix-up
+// launch with its own lanes and butterfly, the zero tail.  0, or -1 when refused.
+static fr_t fr_spmv_tree_host(std::vector<fr_t>& lanes) {
+    const size_t w = lanes.size();
+    for (size_t off = w / 2; off >= 1; off >>= 1) {
+        std::vector<fr_t> next(w);
+        for (size_t l = 0; l < w; l++) next[l] = lanes[l] + lanes[l ^ off];
+        lanes.swap(next);
+    }
+    return lanes[0];
+}
+int snarkvm_hip_selftest_fr_spmv(void* y, size_t n_out, size_t rows, size_t cols, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals, const void* x,
+                                 uint32_t seg, uint32_t width) {
+    if (fr_spmv_matrix_check(rows, cols, row_ptr, col_idx, vals)) return -1;
+    if (seg < 1 || (width != 4 && width != 8 && width != 16 && width != 64)) return -1;
+    if (n_out < rows || n_out > FR_SPMV_DIM_MAX || (n_out && !y) || (row_ptr[rows] && !x)) return -1;
+    std::vector<fr_spmv_seg_t> segs;
+    std::vector<fr_spmv_fix_t> fix;
+    const size_t nparts = fr_spmv_layout(rows, row_ptr, seg, segs, fix);
+    std::vector<fr_mem_t> parts(nparts ? nparts : 1);
+    fr_mem_t* py = (fr_mem_t*)y;
+    std::vector<fr_t> lanes(width);
+    for (const fr_spmv_seg_t& s : segs) {
+        lanes.resize(width);
+        for (uint32_t l = 0; l < width; l++) lanes[l] = fr_spmv_lane((const fr_mem_t*)vals + s.first, col_idx + s.first, (const fr_mem_t*)x, s.count, l, width);
+        const fr_t v = fr_spmv_tree_host(lanes);
+        if (s.part == FR_SPMV_SOLE)
+            fr_spmv_finish(v).store(&py[s.row]);
+        else
+            v.store(&parts[s.part]);
+    }
+    for (const fr_spmv_fix_t& f : fix) {
+        lanes.resize(width);
+        for (uint32_t l = 0; l < width; l++) lanes[l] = fr_reduce_thread<FR_REDUCE_SUM>(parts.data() + f.first, nullptr, f.count, l, width);
+        fr_spmv_finish(fr_spmv_tree_host(lanes)).store(&py[f.row]);
+    }
+    for (size_t r = rows; r < n_out; r++) fr_t::zero().store(&py[r]);
+    return 0;
+}
+// what registration lays out for a matrix of `rows` rows and nnz entries spread evenly (the first nnz % rows rows one entry longer): out4 = {segment
+// size S, lane-group width, threads per workgroup, segments}
+int snarkvm_hip_selftest_fr_spmv_geometry(size_t rows, size_t nnz, uint32_t* out4) {
+    if (!out4 || nnz > 0xFFFFFFFFull || rows > FR_SPMV_DIM_MAX || (nnz && !rows)) return -1;
+    const size_t S = FR_SPMV_SEG, lo = rows ? nnz / rows : 0, longer = rows ? nnz % rows : 0;
+    const size_t nseg = longer * ((lo + 1 + S - 1) / S) + (rows - longer) * ((lo + S - 1) / S);
+    out4[0] = (uint32_t)S, out4[1] = fr_spmv_width(nnz, nseg), out4[2] = FR_SPMV_B, out4[3] = (uint32_t)nseg;
+    return 0;
+}
+
 // ---- setup-time group operations (group.hip.h) -------------------------------------------------------
 RustError snarkvm_hip_g1_fixed_base_msm(void* out_projective, const void* g_affine, const void* scalars, size_t n) {
     API_BEGIN

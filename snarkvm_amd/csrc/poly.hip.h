@@ -12,6 +12,7 @@
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
 //   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
 //   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
+//   fr_spmv_seg_kernel          y = M x over a registered CSR matrix, segment by segment  round_functions/mod.rs:131-188 (z_M), third.rs:303-306 (M(alpha, .))
 //
 // Representation note (ff.hip.h): the raw memory limbs of a, read as an internal value, are the internal Montgomery form of
 // a * 2^-5 ("shifted").  Sums and differences of shifted values are shifted values; the product of a TRUE internal
@@ -532,6 +533,111 @@ static __global__ void __launch_bounds__(FR_REDUCE_B) fr_support_final_kernel(co
         uint64_t* p = out + 3 * (size_t)blockIdx.y;
         p[0] = s.trimmed_len, p[1] = s.leading_zeros, p[2] = s.nonzero;
     }
+}
+#endif
+
+// ---- sparse matrix times vector over a registered matrix -----------------------------------------------------------------
+// y = M x for an R1CS matrix M in CSR form (z_M = M z, snark/varuna/ahp/prover/round_functions/mod.rs:131-188) or for its transpose
+// (M(alpha, .) = M^T l_alpha, third.rs:303-306).  R1CS rows hold a handful of entries, but a transposed matrix has a few rows - the column of
+// the constant one, of heavily used variables - that collect a large share of all non-zeros, so work is laid out by ENTRIES, on the host, once,
+// when the matrix is registered (api_fr.hip: fr_spmv_layout):
+//   segments  every row is cut into segments of at most `seg` entries: table of fr_spmv_seg_t {row, first entry, count, part}.  part ==
+//             FR_SPMV_SOLE: the only segment of its row; otherwise the slot of this segment's partial sum (a row's slots are consecutive, in
+//             segment order).
+//   fix-ups   table of fr_spmv_fix_t {row, first slot, slots}: every row that has no segment (slots == 0) or more than one.
+//   launch 1  fr_spmv_seg_kernel<W>: one group of W lanes (4, 8, 16 or 64: chosen per matrix from its mean segment length, fr_spmv_width) per
+//             segment.  Lanes stride over the segment's entries: vals[k] is read coalesced (32 B per lane), x[col_idx[k]] is gathered; raw
+//             products go FR_REDUCE_G at a time through Fp::sum_of_products like the inner product's (fr_reduce_group: the same operand
+//             conditions, the value is the first factor), the group folds by the butterfly of fr_lanes_sum.  A sole segment's lane 0 stores
+//             y[row]; any other stores its partial, internal limbs raw.
+//   launch 2  fr_spmv_fix_kernel<W>: one group per fix-up adds that row's partials (none: zero) and stores y[row]; the groups behind the table
+//             store the zeros of the tail y[rows .. n_out).  So every element of y is written exactly once, by exactly one lane, without a fill.
+// blockIdx.y is the batch member (x + y * stride_x, stride_x == 0: one shared x; y + y * stride_y; partial slots + y * nparts).  No atomics: which
+// group finishes first never enters a result, and since field addition is exact and results canonical the 32 bytes of y[r] depend on neither
+// `seg`, W nor the grid (the host replay, snarkvm_hip_selftest_fr_spmv, walks any seg and W through the routines below).
+// As in fr_reduce, raw(val) * raw(x) is the internal form of val x 2^-10 and one from_mem_mont per stored y[r] undoes it (multiplication by a
+// constant commutes with the sums, so partials stay raw).
+// Registers (gfx950, -O3): fr_spmv_seg_kernel 128 VGPRs for every W, fr_spmv_fix_kernel 62, no scratch, no call (tools/device_calls.sh).
+static constexpr uint32_t FR_SPMV_SOLE = 0xFFFFFFFFu;
+static constexpr int FR_SPMV_B = 256;  // threads per workgroup of both launches
+#ifndef FR_SPMV_SEG
+#define FR_SPMV_SEG 128  // entries per segment: measured against 256 and 512 (profiles/fr_spmv.md); a -D override builds the variants tools/bench_fr_spmv.py compares
+#endif
+struct fr_spmv_seg_t {
+    uint32_t row, first, count, part;
+};
+struct fr_spmv_fix_t {
+    uint32_t row, first, count, pad;
+};
+// lanes per segment for a matrix of nnz entries in nseg segments: the narrowest group whose lanes each get at most one sum_of_products group
+// out of a segment of the mean length
+SV_HD uint32_t fr_spmv_width(size_t nnz, size_t nseg) {
+#ifdef FR_SPMV_WIDTH  // a -D override, like FR_SPMV_SEG: one width for every matrix
+    return FR_SPMV_WIDTH;
+#else
+    const size_t mean = nseg ? (nnz + nseg - 1) / nseg : 0;
+    return mean <= 4 * FR_REDUCE_G ? 4 : (mean <= 8 * FR_REDUCE_G ? 8 : (mean <= 16 * FR_REDUCE_G ? 16 : 64));
+#endif
+}
+// G entries at k, k + step, ... of one segment: sum of vals[k] * x[col[k]], unreduced to memory form
+template <int G>
+SV_HD fr_t fr_spmv_group(const fr_mem_t* vals, const uint32_t* col, const fr_mem_t* x, size_t k, size_t step) {
+    fr_t a[G], b[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        a[g] = fr_t::load(&vals[k + g * step]);
+        b[g] = fr_t::load(&x[col[k + g * step]]);
+    }
+    return fr_t::sum_of_products<G>(a, b);
+}
+// the private accumulation of lane `lane` of a group of `width` over a segment of `count` entries (vals, col: at the segment's first entry):
+// whole groups, then single entries
+SV_HD fr_t fr_spmv_lane(const fr_mem_t* vals, const uint32_t* col, const fr_mem_t* x, size_t count, size_t lane, size_t width) {
+    fr_t acc = fr_t::zero();
+    size_t k = lane;
+#pragma unroll 1
+    for (; k < count && count - k > (FR_REDUCE_G - 1) * width; k += FR_REDUCE_G * width) acc = acc + fr_spmv_group<FR_REDUCE_G>(vals, col, x, k, width);
+#pragma unroll 1
+    for (; k < count; k += width) acc = acc + fr_spmv_group<1>(vals, col, x, k, width);
+    return acc;
+}
+// what turns a (sum of) raw product(s) into the memory form of y[r]
+SV_HD fr_t fr_spmv_finish(const fr_t& total) { return total.from_mem_mont(); }
+
+#if defined(__HIPCC__)
+// grid (ceil(nseg / (FR_SPMV_B / W)), members).  Every lane stays until after the butterfly (groups behind the table add zeros).
+template <int W>
+static __global__ void __launch_bounds__(FR_SPMV_B) fr_spmv_seg_kernel(const fr_spmv_seg_t* __restrict__ segs, size_t nseg, const fr_mem_t* __restrict__ vals,
+                                                                       const uint32_t* __restrict__ col, const fr_mem_t* __restrict__ x, size_t stride_x,
+                                                                       fr_mem_t* __restrict__ y, size_t stride_y, fr_mem_t* __restrict__ parts, size_t nparts) {
+    const size_t g = (blockIdx.x * (size_t)FR_SPMV_B + threadIdx.x) / W;
+    const uint32_t lane = threadIdx.x % W;
+    const bool live = g < nseg;
+    fr_spmv_seg_t s{0, 0, 0, FR_SPMV_SOLE};
+    if (live) s = segs[g];
+    fr_t v = fr_spmv_lane(vals + s.first, col + s.first, x + (size_t)blockIdx.y * stride_x, s.count, lane, W);
+    v = fr_lanes_sum(v, W / 2);
+    if (!live || lane) return;
+    if (s.part == FR_SPMV_SOLE)
+        fr_spmv_finish(v).store(&y[(size_t)blockIdx.y * stride_y + s.row]);
+    else
+        v.store(&parts[(size_t)blockIdx.y * nparts + s.part]);
+}
+// grid (ceil((nfix + n_out - rows) / (FR_SPMV_B / W)), members): group g < nfix folds fix-up g, group nfix + t zeroes y[rows + t]
+template <int W>
+static __global__ void __launch_bounds__(FR_SPMV_B) fr_spmv_fix_kernel(const fr_spmv_fix_t* __restrict__ fix, size_t nfix, const fr_mem_t* __restrict__ parts,
+                                                                       size_t nparts, fr_mem_t* __restrict__ y, size_t stride_y, size_t rows, size_t n_out) {
+    const size_t g = (blockIdx.x * (size_t)FR_SPMV_B + threadIdx.x) / W;
+    const uint32_t lane = threadIdx.x % W;
+    fr_spmv_fix_t f{0, 0, 0, 0};
+    if (g < nfix) f = fix[g];
+    fr_t v = fr_reduce_thread<FR_REDUCE_SUM>(parts + (size_t)blockIdx.y * nparts + f.first, nullptr, f.count, lane, W);
+    v = fr_lanes_sum(v, W / 2);
+    if (lane) return;
+    if (g < nfix)
+        fr_spmv_finish(v).store(&y[(size_t)blockIdx.y * stride_y + f.row]);
+    else if (g - nfix < n_out - rows)
+        fr_t::zero().store(&y[(size_t)blockIdx.y * stride_y + rows + (g - nfix)]);
 }
 #endif
 

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -131,6 +131,14 @@ def fr_support_strided_device(d_v, n, count, stride):
     out = np.zeros((int(count), 3), dtype=np.uint64)
     _lib.check(_lib.lib().snarkvm_hip_fr_support_strided(_ptr(out), _dp(d_v), int(n), int(count), int(stride)))
     return out
+
+
+def fr_spmv_device(handle, d_y, n_out, d_x, count=1, stride_x=0, stride_y=0):
+    """Extension (no reference counterpart): y = M x over a matrix registered with `snarkvm_hip_fr_matrix_register` (`handle`: its address, see
+    matrices.RegisteredMatrix) and vectors that live in device memory (`snarkvm_hip_fr_spmv`, on_device = 1).  All n_out >= rows elements of y are
+    written, the tail as zeros.  Member m of a batch reads d_x + m * stride_x elements (stride_x = 0: the one shared x) and writes
+    d_y + m * stride_y.  y must not overlap x.  Inside a scope the call is only enqueued."""
+    _lib.check(_lib.lib().snarkvm_hip_fr_spmv(_dp(d_y), int(n_out), _dp(handle), _dp(d_x), int(count), int(stride_x), int(stride_y), 1))
 
 
 def msm(points, scalars):

@@ -144,3 +144,52 @@ def g2_points(n, distinct=512):
         out[i]["y"] = limbs[2] + limbs[3]
     reps = (n + distinct - 1) // distinct
     return np.tile(out, reps)[:n].copy()
+
+
+# ------------------------------------------------------------------------------------------ R1CS-like sparse matrices
+FR_ONE_MONT = np.array([9015221291577245683, 8239323489949974514, 1646089257421115374, 958099254763297437], dtype=np.uint64)  # 2^256 mod r
+
+
+def r1cs_like_matrix(rows, cols, nnz, seed):
+    """CSR arrays (row_ptr (rows + 1,) uint64, col_idx (nnz,) uint32, vals (nnz, 4) uint64) of a rows x cols matrix with exactly nnz entries,
+    deterministic in its arguments, shaped the way an R1CS matrix is ASSUMED to be - the real row-length distribution of `credits.aleo` is not in
+    this repository, so this is an assumption, not a measurement:
+      - about 1 % of the rows (max(1, rows // 100), spread by the seed) are long: together they hold nnz // 4 entries, split in proportion to
+        random weights, each between 5 and 4096 entries;
+      - every other row holds 1 - 4 entries (random, then nudged one entry at a time until the total is nnz; rows may stay empty only when nnz is
+        too small for one entry each);
+      - a quarter of the non-empty rows have column 0 - the constant one - as their first entry; every other column is uniform in [0, cols), so
+        a row may name a column twice (legal for `snarkvm_hip_fr_matrix_register`);
+      - values are memory images: uniform integers below r (each the Montgomery form of some element), a quarter of them replaced by the
+        Montgomery form of exactly one.
+    Transposed (matrices.transpose), column 0 becomes one row of about rows / 4 entries: the skew the segment layout of the product exists for."""
+    if rows < 1 or cols < 1 or nnz < 0:
+        raise ValueError("r1cs_like_matrix: rows and cols must be positive")
+    lens = np.zeros(rows, dtype=np.int64)
+    n_long = max(1, rows // 100)
+    long_rows = np.argsort(splitmix64(seed ^ 0x10C6, rows), kind="stable")[:n_long]
+    w = (splitmix64(seed ^ 0x3E16, n_long) % np.uint64(1000)).astype(np.int64) + 1
+    lens[long_rows] = np.clip(w * (nnz // 4) // int(w.sum()), 5, 4096)
+    short = np.ones(rows, dtype=bool)
+    short[long_rows] = False
+    n_short = int(short.sum())
+    rem = nnz - int(lens.sum())
+    lo = 1 if rem >= n_short else 0
+    if rem < 0 or rem > 4 * n_short:
+        raise ValueError("r1cs_like_matrix: nnz does not fit rows of 1 - 4 entries beside the long rows")
+    s = (splitmix64(seed ^ 0x5807, n_short) % np.uint64(4)).astype(np.int64) + 1
+    diff = rem - int(s.sum())
+    while diff:
+        can = np.flatnonzero(s < 4) if diff > 0 else np.flatnonzero(s > lo)
+        take = can[: abs(diff)]
+        s[take] += 1 if diff > 0 else -1
+        diff = rem - int(s.sum())
+    lens[short] = s
+    row_ptr = np.zeros(rows + 1, dtype=np.uint64)
+    row_ptr[1:] = np.cumsum(lens).astype(np.uint64)
+    col_idx = (splitmix64(seed ^ 0xC015, nnz) % np.uint64(cols)).astype(np.uint32)
+    first = row_ptr[:-1][(lens > 0) & (splitmix64(seed ^ 0x0C01, rows) % np.uint64(4) == 0)].astype(np.int64)
+    col_idx[first] = 0
+    vals = random_fr_integers(nnz, seed)
+    vals[splitmix64(seed ^ 0x0A1E, nnz) % np.uint64(4) == 0] = FR_ONE_MONT
+    return row_ptr, col_idx, vals
