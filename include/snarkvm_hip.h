@@ -576,6 +576,16 @@ RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void
  * selftest: on the host (the same source as the kernels, square roots included), returns 0, or 1 for a bad argument; devtest: one GPU thread per case. */
 int snarkvm_hip_selftest_field_ext(int op, const void *in, void *out, size_t n);
 RustError snarkvm_hip_devtest_field_ext(int op, const void *in, void *out, size_t n);
+/* The scalar-read phase of a variable-base MSM on its own: n host scalars (32 B each; montgomery = 1: Fr memory images) go through the plan and the
+ * digit parameters a device-side MSM of this geometry gets (window_bits, tables, table_bits as a registered handle passes them; a fused batch asks
+ * for table_bits-wide windows) and through the stand-alone digit kernel that MSM would launch - u16 digits up to 16-bit windows, u32 digits above;
+ * `digits` receives the matrix [digit rows][columns] of raw digits u = ((s + bias) >> c * row) & (2^c - 1), signed digit d = u - 2^(c-1).
+ * multi = 1: the digit kernel of a fused batch over two instances, scalars [0, n) and scalars [n / 2, n), laid side by side in the padded
+ * concatenation (each starts on a multiple of 8 192 columns; the padding holds the zero digit u = 2^(c-1)).
+ * info[6] = {c, digit rows, bytes per digit, columns, first column of the second instance, scalars of the second instance} (the last two 0 unless
+ * multi).  digits_bytes must be digit rows * columns * bytes per digit exactly (the planner is snarkvm_hip_selftest_msm_plan), n >= 1. */
+RustError snarkvm_hip_devtest_msm_digits(const void *scalars, size_t n, int window_bits, int tables, int table_bits, int montgomery, int multi,
+                                         void *digits, size_t digits_bytes, uint32_t *info);
 
 #ifdef __cplusplus
 }
