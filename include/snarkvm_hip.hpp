@@ -216,7 +216,7 @@ inline void fr_support(FrSupport& out, const void* v, size_t n, bool on_device) 
 
 // Registered bases (an SRS resident in HBM with precomputed window tables): register once, commit per call.  `tables` x
 // `window_bits` must cover 254 bits (17 x 15 for proof-sized MSMs, 12 x 22 at 2^24).  Concurrent commit() calls of proof size
-// are fused inside the library (runtime.hip.h::msm_coalesced).
+// are fused inside the library (msm_batch.hip.h::msm_coalesced).
 template <class Affine, class Projective>
 class RegisteredBases {
 public:

@@ -5,9 +5,14 @@
 // pool of (device, stream) resource tokens handed to concurrent callers, staging of the caller's host buffers, the
 // point-range split of one MSM over the GPUs with a host-side combine, error reporting as RustError.
 // Fr entry points: api_fr.hip; point encoding + setup-time group operations: api_serde.hip; G2: api_g2.hip.
-#define SV_TU_G1
-#include "runtime.hip.h"
+#include "msm_batch.hip.h"
 #include "ffl.hip.h"
+
+// this unit launches the scans and the G1 MSMs (msm_acc_lds: the lazy accumulate kernel's LDS request)
+static void tu_set_kernel_attributes() {
+    HIP_TRY(hipFuncSetAttribute((const void*)scan_one_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SCAN_ONE_MAX * 4)));
+    HIP_TRY(hipFuncSetAttribute((const void*)msm_accumulate_lazy_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+}
 
 runtime_t g_rt;
 thread_local thread_scope_t g_tl_scope;
@@ -537,7 +542,7 @@ static void msm_registered_host_scalars(void* out, const snarkvm_hip_bases* h, s
     });
     acc->finish(out);
 }
-// one proof-sized MSM of one caller: a ticket on the handle's coalescer (runtime.hip.h::msm_coalesced) - concurrent callers are fused
+// one proof-sized MSM of one caller: a ticket on the handle's coalescer (msm_batch.hip.h::msm_coalesced) - concurrent callers are fused
 static void msm_single_coalesced(void* out, const snarkvm_hip_bases* h, size_t off0, size_t n0, size_t off1, size_t n1, const void* scalars,
                                  int scalars_on_device, int scalars_montgomery, int window_bits) {
     if (scalars_on_device && g_rt.device_of(scalars) < 0)
@@ -1065,6 +1070,46 @@ RustError snarkvm_hip_g1_generate_bases_device(void* d_out, uint64_t start, size
 }
 
 // ---- test hooks ----------------------------------------------------------------------------------
+}  // extern "C"
+// the field operation of snarkvm_hip_selftest_field (host) and snarkvm_hip_devtest_field (kernel); C++ linkage
+template <class F>
+SV_HD void field_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+    // operands are memory-form Montgomery residues: convert to internal, operate, convert back
+    F x = F::unpack(a).from_mem_mont();
+    F y = F::unpack(b).from_mem_mont();
+    F r;
+    switch (op) {
+        case 0: r = x + y; break;
+        case 1: r = x - y; break;
+        case 2: r = x * y; break;
+        case 3: r = x.sqr(); break;
+        case 4: r = x.inverse(); break;
+        case 5: r = x.neg(); break;
+        case 6: r = F::unpack(a).int_to_mont(); break;                  // from_bigint: integer -> Montgomery
+        case 7: (x.mont_to_int()).pack(out); return;                    // to_bigint: Montgomery -> integer
+        case 9: r = F::diff_of_products(x, y, y, x + y); break;  // x*y - y*(x+y) with one reduction
+        case 8: {  // lazy-arithmetic chain used by the NTT butterflies (Fr only): ((a + b) - b + 2r) * b == a * b
+            if (F::N != 9) { r = x * y; break; }
+            uint32_t kp[F::N];
+            F::mod_shl(kp, 1);
+            F t = F::add_lazy(x, y);         // < 2r
+            t = F::sub_lazy(t, y, kp);       // < 4r
+            r = t.mul_lazy(y).reduce_lazy();
+            break;
+        }
+        default: r = F::zero();
+    }
+    r.to_mem_mont().pack(out);
+}
+static __global__ void devtest_field_kernel(int field, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (field == 0)
+        field_op<fr_t>(op, a + 8 * i, b + 8 * i, out + 8 * i);
+    else
+        field_op<fq_t>(op, a + 12 * i, b + 12 * i, out + 12 * i);
+}
+extern "C" {
 int snarkvm_hip_selftest_field(int field, int op, const void* a, const void* b, void* out, size_t n) {
     const uint32_t* A = (const uint32_t*)a;
     const uint32_t* B = (const uint32_t*)(b ? b : a);
@@ -1300,7 +1345,7 @@ int snarkvm_hip_selftest_g1_lazy_tail(uint64_t seed, int iters) {
     if (!zq.is_zero() || !zq.neg().is_zero() || !(zq + zq).is_zero() || (zq + fqz_t::one()).is_zero()) return -1;
     return 0;
 }
-// The host-side finish of an MSM (runtime.hip.h msm_accum_t) on its own, no device needed: out (144 B) = sum_i 2^pos[i] *
+// The host-side finish of an MSM (msm_run.hip.h msm_accum_t) on its own, no device needed: out (144 B) = sum_i 2^pos[i] *
 // planes[i] for `n` G1 points given as Jacobian memory images.  Lets the CPU test-suite pin the Horner code on the oracle.
 int snarkvm_hip_selftest_g1_finish(const void* planes_jacobian, const int32_t* pos, size_t n, void* out) {
     try {

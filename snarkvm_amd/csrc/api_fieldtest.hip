@@ -1,9 +1,11 @@
 // api_fieldtest.hip - test hook for the field arithmetic that field_op's two operands cannot express (snarkvm_hip_selftest_field_ext /
 // snarkvm_hip_devtest_field_ext): four-operand diff_of_products, Fq2, the square roots of serde.hip.h.  A translation unit of its own, so that
 // these extra callers of fq_sqrt / fq2_sqrt leave the inlining decisions inside the decoder kernels of api_serde.hip as they were.
-// runtime.hip.h brings the lanes and the API_BEGIN / API_END frame, and with them every static kernel it defines: this unit's code object holds
-// unused copies of them (compile time; they are never launched from here - each is launched from the unit that owns its entry point).
+// runtime.hip.h brings the lanes and the API_BEGIN / API_END frame, serde.hip.h the square roots.
 #include "runtime.hip.h"
+#include "serde.hip.h"
+
+static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
 
 // One case per record, operands and results in memory form, converted like field_op does; the same routine on the host and in the kernel.
 enum { FX_FQ_DOP = 0, FX_FR_DOP, FX_FQ2_MUL, FX_FQ2_SQR, FX_FQ2_INV, FX_FQ2_DOP, FX_FQ_SQRT, FX_FQ2_SQRT, FX_FQ_RAW, FX_FR_RAW, FX_OPS };

@@ -1,10 +1,19 @@
 // api_fr.hip - the Fr-side entry points of the C ABI: NTT / polymul (the reference's snarkvm_ntt, snarkvm_polymul), the
 // prover-round polynomial kernels and the setup-time group operations that are built on them.  A separate translation unit so
 // that build.py can compile it next to api.hip (G1 MSM) and api_g2.hip.
-#define SV_TU_NTT
-#include "runtime.hip.h"
+#include "msm_run.hip.h"  // convert_bases (g1_fixed_base_msm)
+#include "group.hip.h"
+#include "poly.hip.h"
 
 #include <algorithm>
+
+// this unit launches the NTT passes
+static void tu_set_kernel_attributes() {
+    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<false, ntt_arith_u>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<true, ntt_arith_u>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<true, ntt_arith_u, ntt_load_bounded>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel_v2<false, ntt_arith_u, ntt_load_product>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+}
 
 extern "C" {
 

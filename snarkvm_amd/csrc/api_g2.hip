@@ -1,7 +1,13 @@
 // api_g2.hip - the G2 (Fq2) entry points of the C ABI: the MSM engine, table precomputation and point encoding instantiated
 // over fq2_t.  A separate translation unit only because these instantiations are half of the compile time: build.py compiles
 // the units in parallel.
-#include "runtime.hip.h"
+#include "msm_batch.hip.h"
+#include "serde.hip.h"
+
+// this unit launches the scans (the G2 MSMs)
+static void tu_set_kernel_attributes() {
+    HIP_TRY(hipFuncSetAttribute((const void*)scan_one_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SCAN_ONE_MAX * 4)));
+}
 
 struct snarkvm_hip_bases_g2 : bases_handle_t<fq2_t> {};
 
@@ -71,7 +77,7 @@ void snarkvm_hip_free_bases_g2(snarkvm_hip_bases_g2_t* h) {
     delete h;
 }
 #ifndef SV_NO_G2
-// a proof-sized G2 MSM of one caller: concurrent callers over the same handle are fused (runtime.hip.h::msm_coalesced)
+// a proof-sized G2 MSM of one caller: concurrent callers over the same handle are fused (msm_batch.hip.h::msm_coalesced)
 static RustError msm_g2_single_coalesced(void* out, const snarkvm_hip_bases_g2_t* h, size_t offset, size_t npoints, const void* scalars, int scalars_on_device,
                                          int window_bits) {
     API_TRY
@@ -84,7 +90,7 @@ static RustError msm_g2_single_coalesced(void* out, const snarkvm_hip_bases_g2_t
     msm_coalesced<fq2_t>(*h, &t, 1);
     API_CATCH
 }
-// the same call from a thread inside an SNARKVM_HIP_SCOPE_ASYNC_MSM scope: only enqueued (runtime.hip.h::msm_scope_enqueue)
+// the same call from a thread inside an SNARKVM_HIP_SCOPE_ASYNC_MSM scope: only enqueued (msm_batch.hip.h::msm_scope_enqueue)
 static RustError msm_g2_scope_enqueue(void* out, const snarkvm_hip_bases_g2_t* h, size_t offset, size_t npoints, const void* scalars, int window_bits, bool* queued) {
     API_TRY
     msm_req_t one;

@@ -1,9 +1,11 @@
 // api_msmtest.hip - test hook for the scalar-read phase of the variable-base MSM (snarkvm_hip_devtest_msm_digits): the stand-alone digit kernels
-// launched on their own, the digit matrix copied back.  The plan and the digit parameters are built the way runtime.hip.h::msm_layout builds
+// launched on their own, the digit matrix copied back.  The plan and the digit parameters are built the way msm_run.hip.h::msm_layout builds
 // them, the launch shapes are those of msm_stage_digits, the instance table of the fused form is laid out like msm_enqueue_job's.  A translation
 // unit of its own (as api_fieldtest.hip): the units that own the MSM entry points compile exactly as before.  The wide-window fused read
 // (radix_hist1_wide_kernel, radix_scatter1_fused_kernel) leaves no digits in memory and has no hook; it is tested through whole MSMs.
-#include "runtime.hip.h"
+#include "msm_batch.hip.h"
+
+static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
 
 extern "C" {
 

@@ -1,7 +1,10 @@
 // api_serde.hip - canonical (de)serialisation of G1 points on the device (serde.hip.h): the reference's point encoding
 // (curves/src/templates/macros.rs:66-140, utilities/src/serialize/flags.rs:72-99) and `.usrs` bodies straight into registered
 // bases.  A separate translation unit so that build.py compiles the square-root / subgroup-check kernels beside the MSM units.
-#include "runtime.hip.h"
+#include "msm_batch.hip.h"  // register_bases_serialized fills a bases handle: bases_handle_t, check_tables, bases_to_lazy_form
+#include "serde.hip.h"
+
+static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
 
 snarkvm_hip_bases* sv_new_bases_handle(size_t npoints, int tables, int table_bits);  // api.hip
 void sv_precompute_tables(lane_t& c, snarkvm_hip_bases* h, g1_aff_mem_t* d);        // api.hip

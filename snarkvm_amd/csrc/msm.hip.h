@@ -7,7 +7,7 @@
 // reference's, the affine normalisation is identical (that is what the reference's tests compare,
 // variable_base/mod.rs:96-105,116-117).
 //
-// Pipeline (all on one stream of one lane; runtime.hip.h::msm_run enqueues it, DESIGN.md 3.2 has the sizes):
+// Pipeline (all on one stream of one lane; msm_run.hip.h::msm_run enqueues it, DESIGN.md 3.2 has the sizes):
 //   1 scalar read   wide windows (c > 16, registered tables): radix_hist1_wide_kernel (msm_sort.hip.h) reads every 32-byte
 //               scalar once, recodes it in registers into signed c-bit digits with the bias trick
 //               (s' = s + sum_w 2^(c-1+cw); digit_w = ((s' >> cw) & (2^c-1)) - 2^(c-1)) and counts level-1 bins in LDS -
@@ -18,7 +18,7 @@
 //               bases, XYZZ mixed additions, one partial sum per bucket touched.  Integer-ALU bound.
 //   6 reduce    msm_reduce_kernel rounds (only for > 2^22 digit entries): partial sums per bucket -> <= tail_partials.
 //   7 fold + bit planes  msm_fold_kernel (two-axis row / column sums of a window), msm_bitplane_kernel (sum_i (i+1) P_i as
-//               sum_j 2^j S_j); 8 the Horner chain over <= ~270 bit-plane sums runs on the host (runtime.hip.h msm_accum_t).
+//               sum_j 2^j S_j); 8 the Horner chain over <= ~270 bit-plane sums runs on the host (msm_run.hip.h msm_accum_t).
 // Digit zero is skipped (batched.rs:350: bucket index wraps to u32::MAX and is ignored).
 #pragma once
 #include <stdlib.h>
@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(256) msm_reduce_kernel(const xyzz_mem_t<F>* __
     store_xyzz<F>(&out[t], acc);
 }
 
-// acc[k * L + slot] += the partial sums of bucket k (the bucket sink of a chunked MSM, runtime.hip.h::msm_bucket_sink_t)
+// acc[k * L + slot] += the partial sums of bucket k (the bucket sink of a chunked MSM, msm_run.hip.h::msm_bucket_sink_t)
 template <class F>
 __global__ void __launch_bounds__(256) msm_bucket_merge_kernel(const xyzz_mem_t<F>* __restrict__ part, const uint32_t* __restrict__ start,
                                                                const uint32_t* __restrict__ cnt, xyzz_mem_t<F>* __restrict__ acc, uint32_t nbt, uint32_t L,
@@ -445,7 +445,7 @@ static __global__ void msm_sink_lists_kernel(uint32_t* __restrict__ start, uint3
 //                workgroup per (tail window, bit) sums its subset as a tree - no running sums, no double-and-add chains;
 //   9  the remaining sum_p 2^p (planes at bit position p) is a Horner chain of <= ~270 doublings with wave-uniform data: that
 //      is host work, like the reference's host-side collapse of the per-GPU results (algorithms/cuda/cuda/snarkvm.cu:290-295)
-//      - runtime.hip.h::msm_finish_host runs it with this same arithmetic compiled for the host (~1 us per operation on one
+//      - msm_run.hip.h::msm_accum_t::finish runs it with this same arithmetic compiled for the host (~1 us per operation on one
 //      core instead of ~10 us on one GPU lane).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ fq_t shfl_xor_field(const fq_t& a, int mask) {
@@ -799,7 +799,7 @@ __global__ void __launch_bounds__(256, TAIL_WAVES<F>::value) msm_fold_kernel(con
     }
     tail_store<F>(out, flags, slot, acc, dbl);
 }
-// The fold output `slot` again, for the outputs msm_fold_kernel flagged (Fq2: an addition met equal x coordinates - P + P or P - P): ONE wave per output and the plain law with its doubling, two
+// The fold output `slot` again, for the outputs msm_fold_kernel flagged (Fq2: an addition met equal x coordinates - P + P or P - P): ONE wave per output and the plain law with its doubling inlined (add_inlined_dbl: no device-function call in this unit either), two
 // sites.  Same grid as the fold; an unflagged workgroup returns at once (the common case: ~3 us per launch).  Equal partial sums are what a tiled or repeated base
 // vector produces (the reference's own MSM benches tile a handful of points, benches/msm/variable_base.rs:29-32) - rare per output, not per run.
 template <class F>
@@ -821,10 +821,10 @@ __global__ void __launch_bounds__(64) msm_fold_fix_kernel(const xyzz_mem_t<F>* _
         const uint32_t q0 = column ? start[k] : start[k0] + threadIdx.x;
         const uint32_t q1 = column ? q0 + cnt[k] : start[k0 + nlo - 1] + cnt[k0 + nlo - 1];
 #pragma unroll 1
-        for (uint32_t q = q0; q < q1; q += column ? 1u : 64u) acc.add(load_xyzz<F>(&sums[q]));
+        for (uint32_t q = q0; q < q1; q += column ? 1u : 64u) acc.add_inlined_dbl(load_xyzz<F>(&sums[q]));
     }
 #pragma unroll 1
-    for (int off = 1; off < 64; off <<= 1) acc.add(shfl_xor_point(acc, off));
+    for (int off = 1; off < 64; off <<= 1) acc.add_inlined_dbl(shfl_xor_point(acc, off));
     if (threadIdx.x == 0) store_xyzz<F>(&out[slot], acc);
 }
 // 7b. grid (nbits, tail windows).  Tail window tw holds N entries, entry i has weight i + 1:
@@ -910,10 +910,10 @@ __global__ void __launch_bounds__(64) msm_bitplane_fix_kernel(const xyzz_mem_t<F
 #pragma unroll 1
     for (uint32_t p = threadIdx.x; p < total; p += 64u) {
         const uint32_t i = DENSE ? p : find_segment(s_off, nb, p);
-        if (((i + 1) >> j) & 1) acc.add(load_xyzz<F>(&sums[first + p]));
+        if (((i + 1) >> j) & 1) acc.add_inlined_dbl(load_xyzz<F>(&sums[first + p]));
     }
 #pragma unroll 1
-    for (int off = 1; off < 64; off <<= 1) acc.add(shfl_xor_point(acc, off));
+    for (int off = 1; off < 64; off <<= 1) acc.add_inlined_dbl(shfl_xor_point(acc, off));
     if (threadIdx.x == 0) store_xyzz<F>(&planes[slot], acc);
 }
 
@@ -930,12 +930,10 @@ __global__ void __launch_bounds__(64) msm_bitplane_fix_kernel(const xyzz_mem_t<F
     PREFIX template __global__ void msm_fold_fix_kernel<F>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, int, int, const uint32_t*);          \
     PREFIX template __global__ void msm_bitplane_fix_kernel<F, true>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, uint32_t, int, int, const uint32_t*); \
     PREFIX template __global__ void msm_bitplane_fix_kernel<F, false>(const xyzz_mem_t<F>*, const uint32_t*, const uint32_t*, xyzz_mem_t<F>*, uint32_t, int, int, const uint32_t*);
-#ifndef SV_TU_TAIL
 SV_TAIL_KERNELS(extern, fq_t)
 SV_TAIL_KERNELS(extern, fqz_t)
 SV_TAIL_KERNELS(extern, fq2_t)
 SV_TAIL_FIX_KERNELS(extern, fq2_t)
-#endif
 
 // ------------------------------------------------------------------------------------------
 // Base tables for registered (static) bases: next[i] = 2^shift * prev[i], affine.  Lets one bucket window serve

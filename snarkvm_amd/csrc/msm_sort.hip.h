@@ -26,7 +26,7 @@ namespace sv {
 static constexpr int SORT_TILE = 8192;     // items per workgroup tile
 static constexpr int SORT_THREADS = 256;   // 32 items per thread
 
-// Fused multi-instance MSM (runtime.hip.h::msm_run, `multi`): K independent MSMs over slices of ONE registered base vector
+// Fused multi-instance MSM (msm_run.hip.h::msm_run, `multi`): K independent MSMs over slices of ONE registered base vector
 // (the commitments of a prover round, sonic_pc/mod.rs:186-245) share one launch sequence.  The instances are laid side by side
 // in a padded concatenation (every instance starts on a multiple of SORT_TILE positions; the padding holds zero digits, which
 // touch no bucket), the instance id is the top key of the radix partition (bucket window = instance: K x 2^(c-1) buckets), and
@@ -855,7 +855,7 @@ static __device__ __noinline__ void lazy_exceptional_add(xyzz_lazy_t* acc, const
     *acc = xyzz_lazy_t::from_exact(ex);
 }
 // ---- the same kernel on the lazily reduced arithmetic of ffl.hip.h (G1).  The base slots hold canonical residues of the
-// coordinates times 2^406 as unpacked limbs (g1_lazy_slot_t; runtime.hip.h::bases_to_lazy_form / convert_bases form406); the accumulator lives in signed limbs
+// coordinates times 2^406 as unpacked limbs (g1_lazy_slot_t; msm_run.hip.h::bases_to_lazy_form / convert_bases form406); the accumulator lives in signed limbs
 // without a canonical form; partial sums are flushed raw and converted to the exact representation by a dense pass afterwards.  The addition law's exceptional cases (the filter of xyzz_lazy_t::madd) are resolved on
 // the exact arithmetic: cold code.  Per addition: 3 046 multiply-adds + ~900 other instructions (exact kernel: 2 951 + 2 238).
 template <bool PREFETCH>  // (always true - the two-stage pipeline below; a template so that only the unit that launches it - api.hip - compiles it)

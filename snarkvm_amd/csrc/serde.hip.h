@@ -11,6 +11,9 @@
 //   Both bits set is rejected (flags.rs:90-93); coordinates >= q are rejected (read_le -> from_bigint == None).
 // `.usrs` files (parameters/src/mainnet/resources) are a u64 count followed by uncompressed points.
 #pragma once
+#include <stdexcept>
+#include <string>
+
 #include "ec.hip.h"
 #include "ff.hip.h"
 
@@ -341,6 +344,17 @@ static __global__ void g2_serialize_kernel(const uint8_t* __restrict__ affine, s
 #pragma unroll
         for (int k = 0; k < 4; k++) fq_to_le_bytes(c[k].mont_to_int(), (k == 3 && inf) ? (uint8_t)(1u << 6) : (uint8_t)0, dst + 48 * k);
     }
+}
+
+// the SERDE_* status bits a decoder kernel left, as the error its entry point reports (api_serde.hip: G1, api_g2.hip: G2)
+static void serde_throw_on_status(uint32_t st, const char* who) {
+    if (!st) return;
+    std::string m = std::string(who) + ":";
+    if (st & SERDE_BAD_FLAGS) m += " UnexpectedFlags (both flag bits set)";
+    if (st & SERDE_NOT_CANONICAL) m += " coordinate >= q";
+    if (st & SERDE_NOT_ON_CURVE) m += " InvalidData (point not on the curve)";
+    if (st & SERDE_NOT_IN_SUBGROUP) m += " InvalidData (point not in the prime-order subgroup)";
+    throw std::runtime_error(m);  // SerializationError: surfaces as RustError code 1 with this message
 }
 
 }  // namespace sv

@@ -1,5 +1,4 @@
 // tail_g2_planes.hip - the G2 bit-plane kernels (msm.hip.h::msm_bitplane_kernel over fq2_t), see tail_g2.hip.
-#define SV_TU_TAIL
 #include "msm.hip.h"
 
 namespace sv {

@@ -14,7 +14,7 @@ No circuit and no protocol logic: only the MSM / NTT / polynomial calls the prov
 `ProofBatch` replays many such proofs concurrently: worker threads (the reference's rayon workers, one commitment / proof
 each) call the C ABI at the same time and the backend hands every call its own (device, stream) lane; with several devices
 in use the proofs' working sets are spread over them and every call runs where its data lives.  Their proof-sized MSMs meet in
-the library's coalescer (csrc/runtime.hip.h::msm_coalesced) and travel as fused groups.
+the library's coalescer (csrc/msm_batch.hip.h::msm_coalesced) and travel as fused groups.
 
 `LockstepBatch` replays P proofs in LOCK STEP from one thread - `VarunaSNARK::prove_batch` (snark/varuna/varuna.rs:336) is a batch
 by construction: step k of all P proofs is issued together, i.e. round k's commitments of all proofs are ONE

@@ -1,4 +1,4 @@
-"""Pins the MSM enqueue path (csrc/runtime.hip.h::msm_run and its stages): for every entry point and window width the result
+"""Pins the MSM enqueue path (csrc/msm_run.hip.h::msm_run and its stages): for every entry point and window width the result
 equals the oracle's AND the ordered list of profiling phases equals a literal list.  With snarkvm_hip_set_profiling(1) the
 scope and the coalescer decline, so each call takes the synchronous path and leaves its phases behind
 (snarkvm_hip_get_phase_count / _name).  2^10 pairs everywhere: the paths differ by window width and entry point, not by size.

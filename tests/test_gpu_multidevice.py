@@ -188,7 +188,7 @@ print("RING_OK")
 
 def test_chunk_ring_single_device():
     """The pipelined host-buffer paths at test size: tuning msm_chunk_lg=16 cuts a 2^19 `snarkvm_msm` into chunks over the
-    three-lane ring (runtime.hip.h::lane_ring_run), scalar_chunk_lg=18 cuts the cached call's scalars into 3."""
+    three-lane ring (msm_batch.hip.h::lane_ring_run), scalar_chunk_lg=18 cuts the cached call's scalars into 3."""
     env = dict(os.environ, SNARKVM_HIP_DEVICES="0", SNARKVM_HIP_TUNING="msm_chunk_lg=16,scalar_chunk_lg=18", SNARKVM_HIP_BASE_CACHE="16")
     script = RING_SCRIPT % (util.ROOT, os.path.join(util.ROOT, "tests", "golden", "beta_h_g2.bin"))
     r = subprocess.run([sys.executable, "-u", "-c", script], capture_output=True, text=True, env=env, timeout=1200, cwd=util.ROOT)
@@ -233,7 +233,7 @@ print("RAMP_OK")
 def test_chunk_ramp_and_taper_uncached(tuning):
     """`snarkvm_msm` over host buffers with the default 2^21-pair chunks (no base cache: every call uploads): the first chunk is cut into a
     ramp (tuning ramp), the last into 1/2, 1/4, 1/4 (taper), every chunk adds into the shared bucket sink - same group element whatever
-    the cut (runtime.hip.h::msm_host_chunked).  Then host scalars over registered bases: equal or geometric scalar chunks into one
+    the cut (msm_batch.hip.h::msm_host_chunked).  Then host scalars over registered bases: equal or geometric scalar chunks into one
     sink with chained merges (api.hip::msm_registered_host_scalars)."""
     env = dict(os.environ, SNARKVM_HIP_DEVICES="0", SNARKVM_HIP_TUNING=tuning, SNARKVM_HIP_BASE_CACHE="0")
     r = subprocess.run([sys.executable, "-u", "-c", RAMP_SCRIPT % util.ROOT], capture_output=True, text=True, env=env, timeout=600, cwd=util.ROOT)

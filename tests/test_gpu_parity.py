@@ -322,7 +322,7 @@ def test_msm_batch_pipelined(golden):
 
 @pytest.mark.parametrize("tables,window_bits", [(17, 15), (16, 0), (20, 13)])
 def test_msm_batch_fused_multi_instance(golden, tables, window_bits):
-    """Batches of proof-sized instances over windowed tables run FUSED (runtime.hip.h::msm_batch_run: one launch sequence per
+    """Batches of proof-sized instances over windowed tables run FUSED (msm_batch.hip.h::msm_batch_run: one launch sequence per
     group, instance id = top sort key).  Ragged sizes (0, 1, tile boundaries 8191 / 8192 / 8193, > 2^16), base offsets, host and
     device scalars, Montgomery scalars, and an instance too big to fuse in the middle of the batch; every result against the
     oracle's batched::msm of that instance alone."""

@@ -1,6 +1,6 @@
 """Round-4 paths of the prover-shaped workload, all through the C ABI, all against the CPU oracle:
 
-* the in-library coalescer (csrc/runtime.hip.h::msm_coalesced): concurrent callers of proof-sized registered MSMs - the
+* the in-library coalescer (csrc/msm_batch.hip.h::msm_coalesced): concurrent callers of proof-sized registered MSMs - the
   reference's rayon fan-out, one `snarkvm_msm`-sized call per polynomial (sonic_pc/mod.rs:186-245) - are fused into groups;
   every caller still gets ITS result, bit-identical to the per-instance path;
 * the deferred-synchronisation scope (snarkvm_hip_scope_begin / _end) and the batched NTT launches (one launch per pass for up to

@@ -85,7 +85,7 @@ def test_limb_tables_match_reference_constants(golden):
     words = [int(x.rstrip("u"), 16) for x in re.findall(r"0x[0-9a-fA-F]+", m.group(1))]
     assert sum(w << (32 * i) for i, w in enumerate(words)) == pyref.from_limbs(golden["constants"]["fr"]["TWO_ADIC_ROOT_OF_UNITY"])
     csrc = os.path.join(util.ROOT, "snarkvm_amd", "csrc")
-    api = "".join(open(os.path.join(csrc, f)).read() for f in ("api.hip", "api_fr.hip", "api_g2.hip", "runtime.hip.h"))
+    api = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
     for name, key in (("G1_GEN_X", "GENERATOR_X_MONT"), ("G1_GEN_Y", "GENERATOR_Y_MONT")):
         m = re.search(name + r"\[6\] = \{(.*?)\}", api, re.S)
         assert [int(x) for x in re.findall(r"(\d+)ull", m.group(1))] == golden["constants"]["g1"][key]
@@ -159,7 +159,7 @@ def test_msm_planner_invariants():
 
 
 def test_msm_host_finish_matches_oracle():
-    """The host-side end of every MSM (runtime.hip.h msm_accum_t: bit-plane sums at bit positions -> one Horner chain; also the
+    """The host-side end of every MSM (msm_run.hip.h msm_accum_t: bit-plane sums at bit positions -> one Horner chain; also the
     combine step of a multi-device / chunked MSM, the reference's host `dadd`, snarkvm.cu:290-295) compiled for the host:
     sum_i 2^pos[i] * P_i == the oracle's MSM with scalars 2^pos[i] mod r, for repeated positions, infinity planes, position 0
     and positions beyond the scalar field's bit length."""

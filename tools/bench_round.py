@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Proof-sized commitment rounds over one registered SRS (17 x 15-bit tables): the 14 G1 MSMs of one transfer_private proof
 (snarkvm_amd/proofs.py: 2^16 - 2^17 pairs each) issued
-  all14     as ONE batched call (fused multi-instance launch sequence, runtime.hip.h::msm_batch_run)
+  all14     as ONE batched call (fused multi-instance launch sequence, msm_batch.hip.h::msm_batch_run)
   rounds    as the prover's rounds (1, 1, 2, 3, 4, 3 instances per call; sonic_pc/mod.rs:186-245)
   single    one synchronous call per instance
 Device-resident scalars; every result is checked against the closed form (bases (i + 1) G).  Run twice for the A/B:

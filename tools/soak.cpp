@@ -1,4 +1,4 @@
-// soak.cpp - randomized soak of the host runtime (csrc/runtime.hip.h: lanes, ticket coalescer, thread-local scopes with their further streams, pending
+// soak.cpp - randomized soak of the host runtime (csrc/runtime.hip.h, csrc/msm_batch.hip.h: lanes, ticket coalescer, thread-local scopes with their further streams, pending
 // finishes, deferred frees, the thread-exit clean-up) through the C ABI alone: T threads issue a seeded random mix of EVERY entry-point family for a
 // given time, and every result is compared with the same call issued alone (a single-threaded pass over all (operation, variant) pairs before the
 // threads start).  The reference's host logic is 314 lines behind a blocking token channel (algorithms/cuda/cuda/snarkvm.cu:73-312); this runtime is
