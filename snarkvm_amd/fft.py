@@ -206,8 +206,7 @@ class Evaluations:
         from . import _lib
 
         tau = np.ascontiguousarray(point, dtype=np.uint64).reshape(1, 4)
-        _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(ctypes.c_void_p(_dev_ptr(d_lagrange_coefficients)), ctypes.c_uint32(domain.log_size_of_group),
-                                                                  ctypes.c_void_p(tau.ctypes.data), ctypes.c_int(1)))
+        _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(_dev_ptr(d_lagrange_coefficients), domain.log_size_of_group, tau.ctypes.data, 1))
         return Evaluations.evaluate_with_coeffs_device(d_evaluations, d_lagrange_coefficients, domain.size)
 
 
@@ -231,7 +230,6 @@ def evaluate_over_domain(coeffs, domain):
         n = coeffs.shape[0]
         q = np.zeros((n - domain.size, 4), dtype=np.uint64)
         folded = np.zeros((domain.size, 4), dtype=np.uint64)
-        _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_vanishing(ctypes.c_void_p(q.ctypes.data), ctypes.c_void_p(folded.ctypes.data), ctypes.c_void_p(coeffs.ctypes.data),
-                                                                ctypes.c_size_t(n), ctypes.c_size_t(domain.size), ctypes.c_int(0)))
+        _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_vanishing(q.ctypes.data, folded.ctypes.data, coeffs.ctypes.data, n, domain.size, 0))
         coeffs = folded
     return Evaluations(domain.fft(coeffs), domain)

@@ -36,8 +36,7 @@ class FixedBase:
         """fixed_base.rs:87-97: [v_i * g] as G1_PROJECTIVE records; `v` are Fr elements ((n, 4) Montgomery limbs)."""
         v = np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros(v.shape[0], dtype=G1_PROJECTIVE)
-        _lib.check(_lib.lib().snarkvm_hip_g1_fixed_base_msm(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(table["g"].ctypes.data),
-                                                           ctypes.c_void_p(v.ctypes.data), ctypes.c_size_t(v.shape[0])))
+        _lib.check(_lib.lib().snarkvm_hip_g1_fixed_base_msm(out.ctypes.data, table["g"].ctypes.data, v.ctypes.data, v.shape[0]))
         return out
 
 
@@ -48,7 +47,7 @@ def group_ntt(points_projective, inverse=False):
     lg = n.bit_length() - 1
     if n == 0 or 1 << lg != n:
         raise ValueError("domain_size is not power of 2")
-    _lib.check(_lib.lib().snarkvm_hip_g1_group_ntt(ctypes.c_void_p(pts.ctypes.data), ctypes.c_uint32(lg), ctypes.c_int(1 if inverse else 0)))
+    _lib.check(_lib.lib().snarkvm_hip_g1_group_ntt(pts.ctypes.data, lg, 1 if inverse else 0))
     return pts
 
 

@@ -33,8 +33,7 @@ def to_affine(projective):
     """`From<Projective> for Affine` on the device (affine.rs:331-353)."""
     projective = np.ascontiguousarray(projective, dtype=G1_PROJECTIVE).reshape(-1)
     out = np.zeros(projective.shape[0], dtype=G1_AFFINE)
-    _lib.check(_lib.lib().snarkvm_hip_g1_to_affine(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(projective.ctypes.data),
-                                                   ctypes.c_size_t(projective.shape[0])))
+    _lib.check(_lib.lib().snarkvm_hip_g1_to_affine(out.ctypes.data, projective.ctypes.data, projective.shape[0]))
     return out
 
 
@@ -48,9 +47,7 @@ class Powers:
         self._gamma_offset = self.powers_of_beta_g.shape[0]
         both = np.concatenate([self.powers_of_beta_g, self.powers_of_beta_times_gamma_g])
         self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib().snarkvm_hip_register_bases_tables(ctypes.byref(self._h), ctypes.c_void_p(both.ctypes.data),
-                                                               ctypes.c_size_t(both.shape[0]), ctypes.c_size_t(G1_AFFINE.itemsize), ctypes.c_int(0),
-                                                               ctypes.c_int(int(tables))))
+        _lib.check(_lib.lib().snarkvm_hip_register_bases_tables(ctypes.byref(self._h), both.ctypes.data, both.shape[0], G1_AFFINE.itemsize, 0, int(tables)))
 
     def size(self):  # data_structures.rs:163-165
         return self.powers_of_beta_g.shape[0]
@@ -147,9 +144,7 @@ class KZG10:
         scalars = np.concatenate([plain, blind]) if blind.shape[0] else plain
         out = np.zeros(1, dtype=G1_PROJECTIVE)
         _lib.check(_lib.lib().snarkvm_hip_msm_registered_ex(
-            ctypes.c_void_p(out.ctypes.data), powers._h, ctypes.c_size_t(lz), ctypes.c_size_t(plain.shape[0]),
-            ctypes.c_size_t(powers._gamma_offset), ctypes.c_size_t(blind.shape[0]),
-            ctypes.c_void_p(np.ascontiguousarray(scalars).ctypes.data), ctypes.c_int(0), ctypes.c_int(1), ctypes.c_int(0)))
+            out.ctypes.data, powers._h, lz, plain.shape[0], powers._gamma_offset, blind.shape[0], np.ascontiguousarray(scalars).ctypes.data, 0, 1, 0))
         return out, randomness
 
     @staticmethod
@@ -179,10 +174,7 @@ class KZG10:
             flat = torch.cat([flat, blind])
         torch.cuda.current_stream().synchronize()  # the library runs on its own stream
         out = np.zeros(1, dtype=G1_PROJECTIVE)
-        _lib.check(_lib.lib().snarkvm_hip_msm_registered_ex(
-            ctypes.c_void_p(out.ctypes.data), powers._h, ctypes.c_size_t(0), ctypes.c_size_t(n),
-            ctypes.c_size_t(powers._gamma_offset), ctypes.c_size_t(k), ctypes.c_void_p(flat.data_ptr()), ctypes.c_int(1), ctypes.c_int(1),
-            ctypes.c_int(0)))
+        _lib.check(_lib.lib().snarkvm_hip_msm_registered_ex(out.ctypes.data, powers._h, 0, n, powers._gamma_offset, k, flat.data_ptr(), 1, 1, 0))
         return out, randomness
 
     @staticmethod
@@ -222,18 +214,16 @@ class KZG10:
         out = np.zeros(1, dtype=G1_PROJECTIVE)
         scratch = None
         if n0 == 0:  # the zero polynomial: what `commit` does with it (host scalars: only the blinding coefficients, if any)
-            scalars, on_device, lz = ctypes.c_void_p(blind.ctypes.data), 0, 0
+            scalars, on_device, lz = blind.ctypes.data, 0, 0
         elif k:
             scratch = HipMem(32 * (n0 + k))
             scratch.copy_from(0, ptr + 32 * lz, 32 * n0)
             scratch.upload(blind, 32 * n0)
-            scalars, on_device = ctypes.c_void_p(scratch.ptr), 1
+            scalars, on_device = scratch.ptr, 1
         else:
-            scalars, on_device = ctypes.c_void_p(ptr + 32 * lz), 1
+            scalars, on_device = ptr + 32 * lz, 1
         try:
-            _lib.check(L.snarkvm_hip_msm_registered_ex(
-                ctypes.c_void_p(out.ctypes.data), powers._h, ctypes.c_size_t(lz), ctypes.c_size_t(n0), ctypes.c_size_t(powers._gamma_offset), ctypes.c_size_t(k),
-                scalars, ctypes.c_int(on_device), ctypes.c_int(1), ctypes.c_int(0)))
+            _lib.check(L.snarkvm_hip_msm_registered_ex(out.ctypes.data, powers._h, lz, n0, powers._gamma_offset, k, scalars, on_device, 1, 0))
         finally:
             if scratch is not None:
                 scratch.free()
@@ -260,9 +250,7 @@ class KZG10:
         scalars = np.concatenate([evaluations, blind]) if blind.shape[0] else evaluations
         out = np.zeros(1, dtype=G1_PROJECTIVE)
         _lib.check(_lib.lib().snarkvm_hip_msm_registered_ex(
-            ctypes.c_void_p(out.ctypes.data), lagrange_basis._h, ctypes.c_size_t(0), ctypes.c_size_t(n),
-            ctypes.c_size_t(lagrange_basis._gamma_offset), ctypes.c_size_t(blind.shape[0]),
-            ctypes.c_void_p(np.ascontiguousarray(scalars).ctypes.data), ctypes.c_int(0), ctypes.c_int(1), ctypes.c_int(0)))
+            out.ctypes.data, lagrange_basis._h, 0, n, lagrange_basis._gamma_offset, blind.shape[0], np.ascontiguousarray(scalars).ctypes.data, 0, 1, 0))
         return out, randomness
 
     @staticmethod
@@ -294,9 +282,7 @@ class KZG10:
         scalars = np.concatenate([plain, blind]) if blind.shape[0] else plain
         out = np.zeros(1, dtype=G1_PROJECTIVE)
         _lib.check(_lib.lib().snarkvm_hip_msm_registered_ex(
-            ctypes.c_void_p(out.ctypes.data), powers._h, ctypes.c_size_t(lz), ctypes.c_size_t(plain.shape[0]),
-            ctypes.c_size_t(powers._gamma_offset), ctypes.c_size_t(blind.shape[0]),
-            ctypes.c_void_p(np.ascontiguousarray(scalars).ctypes.data), ctypes.c_int(0), ctypes.c_int(1), ctypes.c_int(0)))
+            out.ctypes.data, powers._h, lz, plain.shape[0], powers._gamma_offset, blind.shape[0], np.ascontiguousarray(scalars).ctypes.data, 0, 1, 0))
         return KZGProof(to_affine(out)[0], random_v)
 
     @staticmethod

@@ -152,6 +152,5 @@ def m_at_alpha_evals_device(reg_transposed, lg_constraint_domain, alpha, d_out, 
     if reg_transposed.cols > (1 << lg_constraint_domain):
         raise ValueError("m_at_alpha_evals_device: the matrix has more constraints than the constraint domain has elements")
     tau = np.ascontiguousarray(alpha, dtype=np.uint64).reshape(1, 4)
-    _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(ctypes.c_void_p(_dev_ptr(d_lagrange)), ctypes.c_uint32(lg_constraint_domain),
-                                                              ctypes.c_void_p(tau.ctypes.data), ctypes.c_int(1)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(_dev_ptr(d_lagrange), lg_constraint_domain, tau.ctypes.data, 1))
     reg_transposed.mul_device(d_out, reg_transposed.rows, d_lagrange)

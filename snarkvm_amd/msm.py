@@ -33,17 +33,15 @@ class RegisteredBases:
         self.window_bits = int(window_bits)
         if device_ptr is not None:
             self.n = int(npoints)
-            src, on_device = ctypes.c_void_p(device_ptr), 1
+            src, on_device = device_ptr, 1
         else:
             bases = np.ascontiguousarray(bases, dtype=G1_AFFINE).reshape(-1)
             self.n = bases.shape[0]
-            src, on_device = ctypes.c_void_p(bases.ctypes.data), 0
+            src, on_device = bases.ctypes.data, 0
         if self.window_bits:
-            err = L.snarkvm_hip_register_bases_windowed(ctypes.byref(self._h), src, ctypes.c_size_t(self.n), ctypes.c_size_t(G1_AFFINE.itemsize),
-                                                        ctypes.c_int(on_device), ctypes.c_int(self.tables), ctypes.c_int(self.window_bits))
+            err = L.snarkvm_hip_register_bases_windowed(ctypes.byref(self._h), src, self.n, G1_AFFINE.itemsize, on_device, self.tables, self.window_bits)
         else:
-            err = L.snarkvm_hip_register_bases_tables(ctypes.byref(self._h), src, ctypes.c_size_t(self.n), ctypes.c_size_t(G1_AFFINE.itemsize),
-                                                      ctypes.c_int(on_device), ctypes.c_int(self.tables))
+            err = L.snarkvm_hip_register_bases_tables(ctypes.byref(self._h), src, self.n, G1_AFFINE.itemsize, on_device, self.tables)
         _lib.check(err)
 
     @classmethod
@@ -65,13 +63,11 @@ class RegisteredBases:
         out = np.zeros(1, dtype=G1_PROJECTIVE)
         if device_ptr is not None:
             n = int(npoints)
-            err = L.snarkvm_hip_msm_registered(ctypes.c_void_p(out.ctypes.data), self._h, ctypes.c_size_t(offset), ctypes.c_size_t(n),
-                                               ctypes.c_void_p(device_ptr), ctypes.c_int(1), ctypes.c_int(window_bits))
+            err = L.snarkvm_hip_msm_registered(out.ctypes.data, self._h, offset, n, device_ptr, 1, window_bits)
         else:
             scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
             n = scalars.shape[0]
-            err = L.snarkvm_hip_msm_registered(ctypes.c_void_p(out.ctypes.data), self._h, ctypes.c_size_t(offset), ctypes.c_size_t(n),
-                                               ctypes.c_void_p(scalars.ctypes.data), ctypes.c_int(0), ctypes.c_int(window_bits))
+            err = L.snarkvm_hip_msm_registered(out.ctypes.data, self._h, offset, n, scalars.ctypes.data, 0, window_bits)
         _lib.check(err)
         return out
 
@@ -96,8 +92,7 @@ class RegisteredBases:
         c_offs = (ctypes.c_size_t * max(1, count))(*offs)
         c_ns = (ctypes.c_size_t * max(1, count))(*ns)
         c_ptrs = (ctypes.c_void_p * max(1, count))(*ptrs)
-        _lib.check(L.snarkvm_hip_msm_registered_batch(ctypes.c_void_p(out.ctypes.data), self._h, ctypes.c_size_t(count), c_offs, c_ns, c_ptrs,
-                                                      ctypes.c_int(on_dev), ctypes.c_int(1 if montgomery else 0), ctypes.c_int(window_bits)))
+        _lib.check(L.snarkvm_hip_msm_registered_batch(out.ctypes.data, self._h, count, c_offs, c_ns, c_ptrs, on_dev, 1 if montgomery else 0, window_bits))
         return out
 
     def close(self):
@@ -123,8 +118,7 @@ def msm_g2(bases, scalars):
     if n > bases.shape[0]:
         raise ValueError(f"length mismatch {bases.shape[0]} points < {n} scalars")
     out = np.zeros(1, dtype=G2_PROJECTIVE)
-    err = _lib.lib().snarkvm_hip_msm_g2(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(bases.ctypes.data), ctypes.c_size_t(n),
-                                        ctypes.c_void_p(scalars.ctypes.data), ctypes.c_size_t(G2_AFFINE.itemsize))
+    err = _lib.lib().snarkvm_hip_msm_g2(out.ctypes.data, bases.ctypes.data, n, scalars.ctypes.data, G2_AFFINE.itemsize)
     _lib.check(err)
     return out
 
@@ -138,8 +132,7 @@ class RegisteredBasesG2:
         bases = np.ascontiguousarray(bases, dtype=G2_AFFINE).reshape(-1)
         self.n = bases.shape[0]
         self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib().snarkvm_hip_register_bases_g2(ctypes.byref(self._h), ctypes.c_void_p(bases.ctypes.data), ctypes.c_size_t(self.n),
-                                                           ctypes.c_size_t(G2_AFFINE.itemsize), ctypes.c_int(int(tables)), ctypes.c_int(int(window_bits))))
+        _lib.check(_lib.lib().snarkvm_hip_register_bases_g2(ctypes.byref(self._h), bases.ctypes.data, self.n, G2_AFFINE.itemsize, int(tables), int(window_bits)))
 
     def msm(self, scalars=None, offset=0, window_bits=0, device_ptr=None, npoints=None):
         """sum_i scalars[i] * bases[offset + i]; scalars either a host (n,4) u64 array or a device pointer + npoints."""
@@ -147,14 +140,10 @@ class RegisteredBasesG2:
 
         out = np.zeros(1, dtype=G2_PROJECTIVE)
         if device_ptr is not None:
-            _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered(ctypes.c_void_p(out.ctypes.data), self._h, ctypes.c_size_t(offset),
-                                                               ctypes.c_size_t(int(npoints)), ctypes.c_void_p(device_ptr), ctypes.c_int(1),
-                                                               ctypes.c_int(window_bits)))
+            _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered(out.ctypes.data, self._h, offset, int(npoints), device_ptr, 1, window_bits))
             return out
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
-        _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered(ctypes.c_void_p(out.ctypes.data), self._h, ctypes.c_size_t(offset),
-                                                           ctypes.c_size_t(scalars.shape[0]), ctypes.c_void_p(scalars.ctypes.data), ctypes.c_int(0),
-                                                           ctypes.c_int(window_bits)))
+        _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered(out.ctypes.data, self._h, offset, scalars.shape[0], scalars.ctypes.data, 0, window_bits))
         return out
 
     def msm_batch(self, scalars_list=None, offsets=None, device_ptrs=None, npoints=None, window_bits=0):
@@ -171,8 +160,7 @@ class RegisteredBasesG2:
         c_offs = (ctypes.c_size_t * max(1, count))(*offs)
         c_ns = (ctypes.c_size_t * max(1, count))(*ns)
         c_ptrs = (ctypes.c_void_p * max(1, count))(*ptrs)
-        _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered_batch(ctypes.c_void_p(out.ctypes.data), self._h, ctypes.c_size_t(count), c_offs, c_ns, c_ptrs,
-                                                                 ctypes.c_int(on_dev), ctypes.c_int(window_bits)))
+        _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered_batch(out.ctypes.data, self._h, count, c_offs, c_ns, c_ptrs, on_dev, window_bits))
         return out
 
     def close(self):
@@ -191,7 +179,7 @@ def set_devices(ids):
     """Devices this process uses (snarkvm_hip_set_devices): before the first compute call.  A repeated id makes an independent
     logical device on the same GPU."""
     arr = (ctypes.c_int32 * len(ids))(*[int(i) for i in ids])
-    _lib.check(_lib.lib().snarkvm_hip_set_devices(arr, ctypes.c_size_t(len(ids))))
+    _lib.check(_lib.lib().snarkvm_hip_set_devices(arr, len(ids)))
 
 
 def num_devices():
@@ -206,5 +194,5 @@ def g1_sum(points):
         raise ValueError("g1_sum: input is not a whole number of G1Projective records")
     n = raw.size // G1_PROJECTIVE.itemsize
     out = np.zeros(1, dtype=G1_PROJECTIVE)
-    _lib.check(_lib.lib().snarkvm_hip_g1_sum(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(raw.ctypes.data), ctypes.c_size_t(n)))
+    _lib.check(_lib.lib().snarkvm_hip_g1_sum(out.ctypes.data, raw.ctypes.data, n))
     return out

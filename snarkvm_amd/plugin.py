@@ -14,7 +14,7 @@ __all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_
 
 
 def _ptr(a):
-    return ctypes.c_void_p(a.ctypes.data)
+    return a.ctypes.data
 
 
 def NTT(domain_size, inout, ntt_order, ntt_direction, ntt_type):
@@ -24,8 +24,7 @@ def NTT(domain_size, inout, ntt_order, ntt_direction, ntt_type):
     if not (isinstance(inout, np.ndarray) and inout.dtype == np.uint64 and inout.flags.c_contiguous and inout.size == 4 * domain_size):
         raise ValueError("inout must be a C-contiguous uint64 array of domain_size x 4 limbs")
     lg = domain_size.bit_length() - 1
-    err = _lib.lib().snarkvm_ntt(_ptr(inout), ctypes.c_uint32(lg), ctypes.c_int(ntt_order), ctypes.c_int(ntt_direction),
-                                 ctypes.c_int(ntt_type))
+    err = _lib.lib().snarkvm_ntt(_ptr(inout), lg, ntt_order, ntt_direction, ntt_type)
     _lib.check(err)
 
 
@@ -38,7 +37,7 @@ def NTT_device_batch(lg, device_ptrs, directions=None, types=None, ntt_order=0):
     ptrs = (ctypes.c_void_p * k)(*[int(p) for p in device_ptrs])
     dirs = (ctypes.c_int * k)(*[int(d) for d in directions]) if directions is not None else None
     tys = (ctypes.c_int * k)(*[int(t) for t in types]) if types is not None else None
-    _lib.check(_lib.lib().snarkvm_hip_ntt_device_batch(ptrs, ctypes.c_size_t(k), ctypes.c_uint32(lg), ctypes.c_int(ntt_order), dirs, tys))
+    _lib.check(_lib.lib().snarkvm_hip_ntt_device_batch(ptrs, k, lg, ntt_order, dirs, tys))
 
 
 def polymul(domain, polynomials, evaluations, zero=None):
@@ -54,8 +53,7 @@ def polymul(domain, polynomials, evaluations, zero=None):
     pl = (ctypes.c_size_t * max(1, len(polys)))(*[p.shape[0] for p in polys])
     ep = (ctypes.c_void_p * max(1, len(evals)))(*[e.ctypes.data for e in evals])
     el = (ctypes.c_size_t * max(1, len(evals)))(*[e.shape[0] for e in evals])
-    err = _lib.lib().snarkvm_polymul(_ptr(out), ctypes.c_size_t(len(polys)), pp, pl, ctypes.c_size_t(len(evals)), ep, el,
-                                     ctypes.c_uint32(lg))
+    err = _lib.lib().snarkvm_polymul(_ptr(out), len(polys), pp, pl, len(evals), ep, el, lg)
     _lib.check(err)
     return out
 
@@ -71,7 +69,7 @@ def polymul_device(lg, out_ptr, polys=(), evals=()):
     pl = (ctypes.c_size_t * max(1, len(polys)))(*[n for _, n in polys])
     ep = (ctypes.c_void_p * max(1, len(evals)))(*evals)
     el = (ctypes.c_size_t * max(1, len(evals)))(*([1 << lg] * len(evals)))
-    _lib.check(_lib.lib().snarkvm_hip_polymul_device(ctypes.c_void_p(int(out_ptr)), len(polys), pp, pl, len(evals), ep, el, lg))
+    _lib.check(_lib.lib().snarkvm_hip_polymul_device(int(out_ptr), len(polys), pp, pl, len(evals), ep, el, lg))
 
 
 FR_LINCOMB_CHUNK = 24  # operands per kernel launch of snarkvm_hip_fr_lincomb (include/snarkvm_hip.h; csrc/poly.hip.h FR_LINCOMB_CHUNK)
@@ -89,14 +87,14 @@ def fr_lincomb_device(d_out, n_out, d_polys, lens, coeffs):
         raise ValueError("length mismatch")
     pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
     pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
-    _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(ctypes.c_void_p(int(d_out) if d_out else None), int(n_out), k, pp, pl, _ptr(cs), 1))
+    _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(int(d_out) if d_out else None, int(n_out), k, pp, pl, _ptr(cs), 1))
 
 
 FR_REDUCE_SUM, FR_REDUCE_DOT = 0, 1  # include/snarkvm_hip.h: SNARKVM_HIP_FR_REDUCE_*
 
 
 def _dp(p):
-    return ctypes.c_void_p(int(p) if p else None)
+    return int(p) if p else None
 
 
 def fr_reduce_device(op, d_a, d_b, n):
@@ -150,8 +148,7 @@ def msm(points, scalars):
     if npoints > points.shape[0]:
         raise ValueError(f"length mismatch {points.shape[0]} points < {npoints} scalars")
     ret = np.zeros(1, dtype=G1_PROJECTIVE)
-    err = _lib.lib().snarkvm_msm(_ptr(ret), _ptr(points), ctypes.c_size_t(npoints), _ptr(scalars),
-                                 ctypes.c_size_t(G1_AFFINE.itemsize))
+    err = _lib.lib().snarkvm_msm(_ptr(ret), _ptr(points), npoints, _ptr(scalars), G1_AFFINE.itemsize)
     _lib.check(err)
     return ret
 
@@ -165,7 +162,7 @@ def set_base_cache(tables, verified=False):
     caller need not promise that its base vector never changes.  Overrides the environment; needs no device."""
     L = _lib.lib()
     fn = L.snarkvm_hip_set_base_cache_verified if verified else L.snarkvm_hip_set_base_cache
-    _lib.check(fn(ctypes.c_int(int(tables))))
+    _lib.check(fn(int(tables)))
 
 
 def base_cache_stats(reset=False):

@@ -28,7 +28,7 @@ def _v(x):
 
 
 def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else ctypes.c_void_p()
+    return a.ctypes.data if a is not None else None
 
 
 def trim(coeffs):
@@ -49,8 +49,7 @@ def vec_op(op, a, b=None, c=None, scalar=None):
             raise ValueError("length mismatch")  # the reference zips with zip_eq
     s = None if scalar is None else _v(scalar)
     out = np.empty_like(a)
-    _lib.check(_lib.lib().snarkvm_hip_fr_vec_op(ctypes.c_int(VEC_OPS[op]), _p(out), _p(a), _p(b), _p(c), _p(s), ctypes.c_size_t(n),
-                                               ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_vec_op(VEC_OPS[op], _p(out), _p(a), _p(b), _p(c), _p(s), n, 0))
     return out
 
 
@@ -105,8 +104,7 @@ def divide_by_linear(coeffs, point):
     n = coeffs.shape[0]
     q = np.zeros((max(n - 1, 0), 4), dtype=np.uint64)
     rem = np.zeros((1, 4), dtype=np.uint64)
-    _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_linear(_p(q) if n > 1 else ctypes.c_void_p(), _p(rem), _p(coeffs), ctypes.c_size_t(n),
-                                                         _p(_v(point)), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_linear(_p(q) if n > 1 else None, _p(rem), _p(coeffs), n, _p(_v(point)), 0))
     return trim(q), rem
 
 
@@ -114,22 +112,21 @@ def evaluate(coeffs, point):
     """DensePolynomial::evaluate (dense.rs:98-114)."""
     coeffs = trim(coeffs)
     rem = np.zeros((1, 4), dtype=np.uint64)
-    _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_linear(ctypes.c_void_p(), _p(rem), _p(coeffs), ctypes.c_size_t(coeffs.shape[0]),
-                                                         _p(_v(point)), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_linear(None, _p(rem), _p(coeffs), coeffs.shape[0], _p(_v(point)), 0))
     return rem
 
 
 def batch_inversion_and_mul(v, coeff):
     """fields/src/lib.rs:73-129: returns coeff / v_i (zeros stay zero)."""
     v = np.array(v, dtype=np.uint64, copy=True).reshape(-1, 4)
-    _lib.check(_lib.lib().snarkvm_hip_fr_batch_inversion_and_mul(_p(v), ctypes.c_size_t(v.shape[0]), _p(_v(coeff)), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_batch_inversion_and_mul(_p(v), v.shape[0], _p(_v(coeff)), 0))
     return v
 
 
 def distribute_powers_and_mul_by_const(v, g, c):
     """fft/domain.rs:229-254: v_i * c * g^i."""
     v = np.array(v, dtype=np.uint64, copy=True).reshape(-1, 4)
-    _lib.check(_lib.lib().snarkvm_hip_fr_distribute_powers(_p(v), ctypes.c_size_t(v.shape[0]), _p(_v(g)), _p(_v(c)), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_distribute_powers(_p(v), v.shape[0], _p(_v(g)), _p(_v(c)), 0))
     return v
 
 
@@ -139,7 +136,7 @@ def evaluate_all_lagrange_coefficients(domain_size, tau):
     if domain_size <= 0 or 1 << lg != domain_size:
         raise ValueError("domain_size is not power of 2")
     out = np.zeros((domain_size, 4), dtype=np.uint64)
-    _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(_p(out), ctypes.c_uint32(lg), _p(_v(tau)), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(_p(out), lg, _p(_v(tau)), 0))
     return out
 
 
@@ -151,8 +148,7 @@ def divide_by_vanishing_poly(coeffs, domain_size):
         return coeffs, coeffs
     q = np.zeros((max(n - domain_size, 0), 4), dtype=np.uint64)
     r = np.zeros((min(n, domain_size), 4), dtype=np.uint64)
-    _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_vanishing(_p(q) if q.shape[0] else ctypes.c_void_p(), _p(r), _p(coeffs), ctypes.c_size_t(n),
-                                                            ctypes.c_size_t(domain_size), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_vanishing(_p(q) if q.shape[0] else None, _p(r), _p(coeffs), n, domain_size, 0))
     return trim(q), trim(r)
 
 
@@ -160,6 +156,5 @@ def mul_by_vanishing_poly(coeffs, domain_size):
     """dense.rs:153-159: p * (X^domain_size - 1), trimmed."""
     coeffs = _v(coeffs)
     out = np.zeros((coeffs.shape[0] + domain_size, 4), dtype=np.uint64)
-    _lib.check(_lib.lib().snarkvm_hip_fr_mul_by_vanishing(_p(out), _p(coeffs) if coeffs.shape[0] else ctypes.c_void_p(),
-                                                         ctypes.c_size_t(coeffs.shape[0]), ctypes.c_size_t(domain_size), ctypes.c_int(0)))
+    _lib.check(_lib.lib().snarkvm_hip_fr_mul_by_vanishing(_p(out), _p(coeffs) if coeffs.shape[0] else None, coeffs.shape[0], domain_size, 0))
     return trim(out)

@@ -34,7 +34,7 @@ from .layout import G1_AFFINE, G1_PROJECTIVE, G2_AFFINE, G2_PROJECTIVE
 
 
 def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 class ProofShape:
@@ -76,9 +76,9 @@ class ProverKeys:
 
             buf = torch.empty(n * G1_AFFINE.itemsize, dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
-        _lib.check(L.snarkvm_hip_g1_generate_bases_device(_p(buf), ctypes.c_uint64(1), ctypes.c_size_t(n)))
+        _lib.check(L.snarkvm_hip_g1_generate_bases_device(_p(buf), 1, n))
         self.h = ctypes.c_void_p()
-        _lib.check(L.snarkvm_hip_register_bases_windowed(ctypes.byref(self.h), _p(buf), ctypes.c_size_t(n), ctypes.c_size_t(G1_AFFINE.itemsize), 1, tables, window_bits))
+        _lib.check(L.snarkvm_hip_register_bases_windowed(ctypes.byref(self.h), _p(buf), n, G1_AFFINE.itemsize, 1, tables, window_bits))
         self.g1_host = (buf.download() if mem == "hip" else buf.cpu().numpy()).view(G1_AFFINE)
         if mem == "hip":
             buf.free()
@@ -89,8 +89,7 @@ class ProverKeys:
         self.g2_host = None
         if shape.lg_g2:
             self.g2_host = synthetic.g2_points(1 << shape.lg_g2)
-            _lib.check(L.snarkvm_hip_register_bases_g2(ctypes.byref(self.hg2), ctypes.c_void_p(self.g2_host.ctypes.data), ctypes.c_size_t(self.g2_host.shape[0]),
-                                                       ctypes.c_size_t(G2_AFFINE.itemsize), tables, window_bits))
+            _lib.check(L.snarkvm_hip_register_bases_g2(ctypes.byref(self.hg2), self.g2_host.ctypes.data, self.g2_host.shape[0], G2_AFFINE.itemsize, tables, window_bits))
         assert scalars in ("uniform", "witness")
         self.scalars = scalars
         if scalars == "witness":
@@ -148,13 +147,13 @@ def replay(ws, salt=0, collect=None):
         t[kind] += time.perf_counter() - t0
 
     def ntt(v, lg, direction, kind=0):
-        timed("ntt", lambda: _lib.check(L.snarkvm_hip_ntt_device(_p(v), ctypes.c_uint32(lg), 0, direction, kind)))
+        timed("ntt", lambda: _lib.check(L.snarkvm_hip_ntt_device(_p(v), lg, 0, direction, kind)))
 
     def ntt_batch(vs, lg, directions):  # independent transforms of one round: one enqueue, one synchronisation
         k = len(vs)
         ptrs = (ctypes.c_void_p * k)(*[v.data_ptr() for v in vs])
         dirs = (ctypes.c_int * k)(*directions)
-        timed("ntt", lambda: _lib.check(L.snarkvm_hip_ntt_device_batch(ptrs, ctypes.c_size_t(k), ctypes.c_uint32(lg), 0, dirs, None)))
+        timed("ntt", lambda: _lib.check(L.snarkvm_hip_ntt_device_batch(ptrs, k, lg, 0, dirs, None)))
 
     def load(v, n, shift):  # a fresh "polynomial" of n coefficients (device copy on torch's stream: not part of the hot path)
         s = 4 * (shift + salt)
@@ -166,7 +165,7 @@ def replay(ws, salt=0, collect=None):
 
     def product(x, y, lg):  # PolyMultiplier::multiply of two coefficient vectors on the 2^lg domain, result in x
         ntt_batch((x, y), lg, (0, 0))
-        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_mul_device(_p(x), _p(x), _p(y), ctypes.c_size_t(1 << lg))))
+        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_mul_device(_p(x), _p(x), _p(y), 1 << lg)))
         ntt(x, lg, 1)
 
     def commit_round(polys):
@@ -179,7 +178,7 @@ def replay(ws, salt=0, collect=None):
         off1 = (ctypes.c_size_t * k)(*([sh.nmax] * k))
         n1 = (ctypes.c_size_t * k)(*[h for _, _, h in polys])
         outs = np.zeros(k, dtype=G1_PROJECTIVE)
-        timed("msm", lambda: _lib.check(L.snarkvm_hip_msm_registered_batch_ex(ctypes.c_void_p(outs.ctypes.data), keys.h, k, off0, n0, off1, n1, ptrs, 1, 1, 0)))
+        timed("msm", lambda: _lib.check(L.snarkvm_hip_msm_registered_batch_ex(outs.ctypes.data, keys.h, k, off0, n0, off1, n1, ptrs, 1, 1, 0)))
         if collect is not None:
             collect.extend(outs[i : i + 1].tobytes() for i in range(k))
 
@@ -191,8 +190,8 @@ def replay(ws, salt=0, collect=None):
         d.copy_(c)
         torch.cuda.current_stream().synchronize()
     product(a, b, sh.lg_r + 1)
-    timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_vec_op(1, _p(a), _p(a), _p(d), None, None, ctypes.c_size_t(2 * nR), 1)))
-    timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(_p(b), _p(c), _p(a), ctypes.c_size_t(2 * nR), ctypes.c_size_t(nR), 1)))
+    timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_vec_op(1, _p(a), _p(a), _p(d), None, None, 2 * nR, 1)))
+    timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(_p(b), _p(c), _p(a), 2 * nR, nR, 1)))
     commit_round([(b, nR, 0)])
     for m in range(3):                                                                                            # round 3
         load(a, nR, 20 + m); ntt(a, sh.lg_r, 1); load(b, nR, 30 + m); product(a, b, sh.lg_r + 1)
@@ -209,14 +208,12 @@ def replay(ws, salt=0, collect=None):
     opens = []                                                                                                    # openings
     for (s, n), q in zip(((13, nK), (17, nR), (19, nK)), (b, c, d)):
         load(a, n, s)
-        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_linear(_p(q), ctypes.c_void_p(ws.rem.ctypes.data), _p(a), ctypes.c_size_t(n),
-                                                                            ctypes.c_void_p(keys.point.ctypes.data), 1)))
+        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_linear(_p(q), ws.rem.ctypes.data, _p(a), n, keys.point.ctypes.data, 1)))
         opens.append((q, n - 1, 0))
     commit_round(opens)                                                                                           # batch_open: the three witness commitments
     if keys.hg2:                                                                                                 # G2 leg
         n2 = 1 << sh.lg_g2
-        timed("g2", lambda: _lib.check(L.snarkvm_hip_msm_g2_registered(ctypes.c_void_p(ws.out_g2.ctypes.data), keys.hg2, 0, n2,
-                                                                        ctypes.c_void_p(pool.data_ptr() + 32 * (23 + salt)), 1, 0)))
+        timed("g2", lambda: _lib.check(L.snarkvm_hip_msm_g2_registered(ws.out_g2.ctypes.data, keys.hg2, 0, n2, pool.data_ptr() + 32 * (23 + salt), 1, 0)))
         if collect is not None:
             collect.append(ws.out_g2.tobytes())
 
@@ -346,17 +343,14 @@ def replay_single(ws, salt=0, collect=None, async_msm=True, marks=None, await_ro
     nR, nK = 1 << sh.lg_r, 1 << sh.lg_k
     pool = ws.pool
     stride_b = ws.row_bytes
-    estride = ctypes.c_size_t(ws.row_bytes // 32)
+    estride = ws.row_bytes // 32
     t0 = time.perf_counter()
 
     def row(r):
         return ws.work_ptr + r * stride_b
 
-    def rp(r):
-        return ctypes.c_void_p(row(r))
-
     # every committed vector keeps its row until the proof is done (SNARKVM_HIP_SCOPE_STABLE_INPUTS: the transform stream never waits for an MSM)
-    _lib.check(L.snarkvm_hip_scope_begin_ex(ctypes.c_void_p(pool.data_ptr()), 3 if async_msm else 0))
+    _lib.check(L.snarkvm_hip_scope_begin_ex(pool.data_ptr(), 3 if async_msm else 0))
     try:
         ws.bind_stream(L.snarkvm_hip_scope_stream())
 
@@ -368,10 +362,10 @@ def replay_single(ws, salt=0, collect=None, async_msm=True, marks=None, await_ro
             ptrs = (ctypes.c_void_p * k)(*[row(r) for r in rows])
             dirs = (ctypes.c_int * k)(*([direction] * k))
             kinds = (ctypes.c_int * k)(*([kind] * k))
-            _lib.check(L.snarkvm_hip_ntt_device_batch(ptrs, ctypes.c_size_t(k), ctypes.c_uint32(lg), 0, dirs, kinds))
+            _lib.check(L.snarkvm_hip_ntt_device_batch(ptrs, k, lg, 0, dirs, kinds))
 
         def mul(x, y, lg, count=1):  # rows x .. x + count - 1 *= rows y .. y + count - 1
-            _lib.check(L.snarkvm_hip_fr_vec_op_strided(2, rp(x), rp(x), rp(y), None, None, ctypes.c_size_t(1 << lg), ctypes.c_size_t(count), estride))
+            _lib.check(L.snarkvm_hip_fr_vec_op_strided(2, row(x), row(x), row(y), None, None, 1 << lg, count, estride))
 
         slot = [0]
 
@@ -383,7 +377,7 @@ def replay_single(ws, salt=0, collect=None, async_msm=True, marks=None, await_ro
             n0 = (ctypes.c_size_t * k)(*[n for _, n, _ in polys])
             off1 = (ctypes.c_size_t * k)(*([sh.nmax] * k))
             n1 = (ctypes.c_size_t * k)(*[h for _, _, h in polys])
-            out = ctypes.c_void_p(ws.outs.ctypes.data + G1_PROJECTIVE.itemsize * slot[0])
+            out = ws.outs.ctypes.data + G1_PROJECTIVE.itemsize * slot[0]
             _lib.check(L.snarkvm_hip_msm_registered_batch_ex(out, keys.h, k, off0, n0, off1, n1, ptrs, 1, 1, 0))
             slot[0] += k
             if await_rounds and async_msm:
@@ -398,8 +392,7 @@ def replay_single(ws, salt=0, collect=None, async_msm=True, marks=None, await_ro
             if keys.hg2:
                 if in_stream:
                     _lib.check(L.snarkvm_hip_scope_set_flags(3))
-                _lib.check(L.snarkvm_hip_msm_g2_registered(ctypes.c_void_p(ws.out_g2.ctypes.data), keys.hg2, 0, 1 << sh.lg_g2,
-                                                            ctypes.c_void_p(pool.data_ptr() + 32 * (23 + salt)), 1, 0))
+                _lib.check(L.snarkvm_hip_msm_g2_registered(ws.out_g2.ctypes.data, keys.hg2, 0, 1 << sh.lg_g2, pool.data_ptr() + 32 * (23 + salt), 1, 0))
             mark("g2 msm issued")
             if in_stream:
                 _lib.check(L.snarkvm_hip_scope_set_flags(3 | 4))
@@ -417,8 +410,8 @@ def replay_single(ws, salt=0, collect=None, async_msm=True, marks=None, await_ro
         load(0, nR, 10, count=3, zero_to=2 * nR)                                             # round 2: z_a, z_b, z_c in rows 0, 1, 2
         ntt([0, 1, 2], sh.lg_r, 1)
         ntt([0, 1], sh.lg_r + 1, 0); mul(0, 1, sh.lg_r + 1); ntt([0], sh.lg_r + 1, 1)
-        _lib.check(L.snarkvm_hip_fr_vec_op(1, rp(0), rp(0), rp(2), None, None, ctypes.c_size_t(2 * nR), 1))
-        _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(rp(1), rp(3), rp(0), ctypes.c_size_t(2 * nR), ctypes.c_size_t(nR), 1))
+        _lib.check(L.snarkvm_hip_fr_vec_op(1, row(0), row(0), row(2), None, None, 2 * nR, 1))
+        _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(row(1), row(3), row(0), 2 * nR, nR, 1))
         mark("round 2 transforms + passes issued")
         commit_round([(row(1), nR, 0)])
         mark("round 2 commit issued")
@@ -441,8 +434,7 @@ def replay_single(ws, salt=0, collect=None, async_msm=True, marks=None, await_ro
         opens = []                                                                           # openings
         for i, (s, n) in enumerate(((13, nK), (17, nR), (19, nK))):
             load(20 + i, n, s)
-            _lib.check(L.snarkvm_hip_fr_divide_by_linear(rp(23 + i), ctypes.c_void_p(ws.rem[i : i + 1].ctypes.data), rp(20 + i), ctypes.c_size_t(n),
-                                                          ctypes.c_void_p(keys.point.ctypes.data), 1))
+            _lib.check(L.snarkvm_hip_fr_divide_by_linear(row(23 + i), ws.rem[i : i + 1].ctypes.data, row(20 + i), n, keys.point.ctypes.data, 1))
             opens.append((row(23 + i), n - 1, 0))
         mark("opening divisions issued")
         commit_round(opens)
@@ -509,13 +501,13 @@ def replay_lockstep(ws, salts, collect=False, async_scope=False, await_rounds=Fa
     stream = None
     deferred = []  # (proof-major outputs array, instances per proof) of the commitment calls, read after scope_end
     if async_scope:
-        _lib.check(L.snarkvm_hip_scope_begin_ex(ctypes.c_void_p(pool.data_ptr()), 1))
+        _lib.check(L.snarkvm_hip_scope_begin_ex(pool.data_ptr(), 1))
         stream = torch.cuda.ExternalStream(L.snarkvm_hip_scope_stream(), device=ws.device)
 
     class scope:  # device-resident calls between loads: enqueued on one stream, one wait at the end (async_scope: the group's one scope is open already)
         def __enter__(self):
             if not async_scope:
-                _lib.check(L.snarkvm_hip_scope_begin(ctypes.c_void_p(pool.data_ptr())))
+                _lib.check(L.snarkvm_hip_scope_begin(pool.data_ptr()))
 
         def __exit__(self, *exc):
             if not async_scope:
@@ -549,16 +541,16 @@ def replay_lockstep(ws, salts, collect=False, async_scope=False, await_rounds=Fa
         ptrs = (ctypes.c_void_p * k)(*ptr_list)
         dirs = (ctypes.c_int * k)(*([direction] * k))
         kinds = (ctypes.c_int * k)(*([kind] * k))
-        timed("ntt", lambda: _lib.check(L.snarkvm_hip_ntt_device_batch(ptrs, ctypes.c_size_t(k), ctypes.c_uint32(lg), 0, dirs, kinds)))
+        timed("ntt", lambda: _lib.check(L.snarkvm_hip_ntt_device_batch(ptrs, k, lg, 0, dirs, kinds)))
 
-    estride = ctypes.c_size_t(stride // 32)  # elements between the vectors of consecutive proofs
+    estride = stride // 32  # elements between the vectors of consecutive proofs
 
     def vp(v):
-        return ctypes.c_void_p(vec(v, 0))
+        return vec(v, 0)
 
     def product(x, y, lg):  # PolyMultiplier::multiply per proof, result in x
         ntt_all((x, y), lg, 0)
-        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_vec_op_strided(2, vp(x), vp(x), vp(y), None, None, ctypes.c_size_t(1 << lg), ctypes.c_size_t(P), estride)))
+        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_vec_op_strided(2, vp(x), vp(x), vp(y), None, None, 1 << lg, P, estride)))
         ntt_all((x,), lg, 1)
 
     def commit_round(polys):
@@ -571,9 +563,9 @@ def replay_lockstep(ws, salts, collect=False, async_scope=False, await_rounds=Fa
         off1 = (ctypes.c_size_t * k)(*([sh.nmax] * k))
         n1 = (ctypes.c_size_t * k)(*[h for _ in range(P) for _, _, h in polys])
         outs = np.zeros(k, dtype=G1_PROJECTIVE)
-        timed("msm", lambda: _lib.check(L.snarkvm_hip_msm_registered_batch_ex(ctypes.c_void_p(outs.ctypes.data), keys.h, k, off0, n0, off1, n1, ptrs, 1, 1, 0)))
+        timed("msm", lambda: _lib.check(L.snarkvm_hip_msm_registered_batch_ex(outs.ctypes.data, keys.h, k, off0, n0, off1, n1, ptrs, 1, 1, 0)))
         if async_scope and await_rounds:  # this round's commitments now (the transcript order); the G2 batch and the scope's stream keep running
-            timed("msm", lambda: _lib.check(L.snarkvm_hip_scope_collect(ctypes.c_void_p(outs.ctypes.data))))
+            timed("msm", lambda: _lib.check(L.snarkvm_hip_scope_collect(outs.ctypes.data)))
         deferred.append((outs, m))  # (asynchronous scope: written by scope_end / scope_collect)
 
     def work_ptr(v):
@@ -593,8 +585,8 @@ def replay_lockstep(ws, salts, collect=False, async_scope=False, await_rounds=Fa
             torch.cuda.current_stream().synchronize()
     with scope():
         product(A, B, sh.lg_r + 1)
-        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_vec_op_strided(1, vp(A), vp(A), vp(D), None, None, ctypes.c_size_t(2 * nR), ctypes.c_size_t(P), estride)))
-        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_vanishing_strided(vp(B), vp(C), vp(A), ctypes.c_size_t(2 * nR), ctypes.c_size_t(nR), ctypes.c_size_t(P), estride)))
+        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_vec_op_strided(1, vp(A), vp(A), vp(D), None, None, 2 * nR, P, estride)))
+        timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_vanishing_strided(vp(B), vp(C), vp(A), 2 * nR, nR, P, estride)))
     commit_round([(work_ptr(B), nR, 0)])
     for m in range(3):                                                                                            # round 3
         load(A, nR, 20 + m); load(B, nR, 30 + m)
@@ -622,8 +614,7 @@ def replay_lockstep(ws, salts, collect=False, async_scope=False, await_rounds=Fa
     for i, ((s, n), q) in enumerate(zip(((13, nK), (17, nR), (19, nK)), (B, C, D))):
         load(A, n, s)
         with scope():
-            timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_linear_strided(vp(q), ctypes.c_void_p(ws.rem[i].ctypes.data), vp(A), ctypes.c_size_t(n),
-                                                                                        ctypes.c_void_p(keys.point.ctypes.data), ctypes.c_size_t(P), estride)))
+            timed("poly", lambda: _lib.check(L.snarkvm_hip_fr_divide_by_linear_strided(vp(q), ws.rem[i].ctypes.data, vp(A), n, keys.point.ctypes.data, P, estride)))
         opens.append((work_ptr(q), n - 1, 0))
     commit_round(opens)                                                                                           # batch_open: the three witness commitments
     if keys.hg2:                                                                                                 # G2 leg: one batched call
@@ -632,7 +623,7 @@ def replay_lockstep(ws, salts, collect=False, async_scope=False, await_rounds=Fa
         offs = (ctypes.c_size_t * P)(*([0] * P))
         ns = (ctypes.c_size_t * P)(*([n2] * P))
         outs2 = np.zeros(P, dtype=G2_PROJECTIVE)
-        timed("g2", lambda: _lib.check(L.snarkvm_hip_msm_g2_registered_batch(ctypes.c_void_p(outs2.ctypes.data), keys.hg2, P, offs, ns, ptrs, 1, 0)))
+        timed("g2", lambda: _lib.check(L.snarkvm_hip_msm_g2_registered_batch(outs2.ctypes.data, keys.hg2, P, offs, ns, ptrs, 1, 0)))
     else:
         outs2 = None
     if async_scope:
@@ -768,7 +759,7 @@ class FfiProofHost:
                 self._conv.free()
             self._conv = HipMem(max(v.nbytes, 32 << 18))
         self._conv.upload(v)
-        _lib.check(_lib.lib().snarkvm_hip_fr_convert_device(ctypes.c_void_p(self._conv.ptr), ctypes.c_void_p(self._conv.ptr), ctypes.c_size_t(v.shape[0]), 1))
+        _lib.check(_lib.lib().snarkvm_hip_fr_convert_device(self._conv.ptr, self._conv.ptr, v.shape[0], 1))
         return self._conv.download(v.nbytes, 0, np.uint64).reshape(-1, 4)
 
 
@@ -793,7 +784,7 @@ def replay_ffi(host, salt=0, collect=None, times=None, g2=True):
         t.setdefault(k, 0.0)
     for k in ("ntt_calls", "polymul_calls", "msm_calls"):
         t.setdefault(k, 0)
-    P = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    P = lambda a: a.ctypes.data  # noqa: E731
 
     def load(n, shift, size=None):
         v = np.zeros((size or n, 4), dtype=np.uint64)
@@ -803,19 +794,19 @@ def replay_ffi(host, salt=0, collect=None, times=None, g2=True):
     def ntt(v, direction, kind=0):  # in place, the whole array is the domain
         lg = v.shape[0].bit_length() - 1
         assert v.shape[0] == 1 << lg
-        _lib.check(L.snarkvm_ntt(P(v), ctypes.c_uint32(lg), 0, direction, kind))
+        _lib.check(L.snarkvm_ntt(P(v), lg, 0, direction, kind))
         return v
 
     def polymul(x, y, lg):  # PolyMultiplier::multiply of two coefficient vectors -> a new vector of the whole 2^lg domain
         out = np.zeros((1 << lg, 4), dtype=np.uint64)
         ptrs = (ctypes.c_void_p * 2)(x.ctypes.data, y.ctypes.data)
         lens = (ctypes.c_size_t * 2)(x.shape[0], y.shape[0])
-        _lib.check(L.snarkvm_polymul(P(out), ctypes.c_size_t(2), ptrs, lens, ctypes.c_size_t(0), None, None, ctypes.c_uint32(lg)))
+        _lib.check(L.snarkvm_polymul(P(out), 2, ptrs, lens, 0, None, None, lg))
         return out
 
     def msm(off, n, scalars):  # one commitment's plaintext MSM: a slice of the long-lived base vector + canonical scalars
         out = np.zeros(1, dtype=G1_PROJECTIVE)
-        _lib.check(L.snarkvm_msm(P(out), ctypes.c_void_p(bases.ctypes.data + off * G1_AFFINE.itemsize), ctypes.c_size_t(n), P(scalars), ctypes.c_size_t(G1_AFFINE.itemsize)))
+        _lib.check(L.snarkvm_msm(P(out), bases.ctypes.data + off * G1_AFFINE.itemsize, n, P(scalars), G1_AFFINE.itemsize))
         return out
 
     def step(kind, jobs, ncalls):
@@ -857,9 +848,9 @@ def replay_ffi(host, salt=0, collect=None, times=None, g2=True):
         zc = np.zeros_like(prod)
         zc[:nR] = z[2]
         row = np.empty_like(prod)
-        _lib.check(L.snarkvm_hip_fr_vec_op(1, P(row), P(prod), P(zc), None, None, ctypes.c_size_t(2 * nR), 0))
+        _lib.check(L.snarkvm_hip_fr_vec_op(1, P(row), P(prod), P(zc), None, None, 2 * nR, 0))
         q, rem = np.zeros((nR, 4), dtype=np.uint64), np.zeros((nR, 4), dtype=np.uint64)
-        _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(P(q), P(rem), P(row), ctypes.c_size_t(2 * nR), ctypes.c_size_t(nR), 0))
+        _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(P(q), P(rem), P(row), 2 * nR, nR, 0))
         return q
 
     q = glue(rowcheck)
@@ -896,7 +887,7 @@ def replay_ffi(host, salt=0, collect=None, times=None, g2=True):
     def witness(s, n):
         p = load(n, s)
         qq, rem = np.zeros((n - 1, 4), dtype=np.uint64), np.zeros((1, 4), dtype=np.uint64)
-        _lib.check(L.snarkvm_hip_fr_divide_by_linear(P(qq), P(rem), P(p), ctypes.c_size_t(n), P(keys.point), 0))
+        _lib.check(L.snarkvm_hip_fr_divide_by_linear(P(qq), P(rem), P(p), n, P(keys.point), 0))
         return qq
 
     ws_ = glue(lambda: [witness(s, n) for s, n in ((13, nK), (17, nR), (19, nK))])
@@ -907,7 +898,7 @@ def replay_ffi(host, salt=0, collect=None, times=None, g2=True):
         sc2 = np.ascontiguousarray(pool[23 + salt : 23 + salt + n2])
         out_g2 = np.zeros(1, dtype=G2_PROJECTIVE)
         t0 = time.perf_counter()
-        _lib.check(L.snarkvm_hip_msm_g2(P(out_g2), P(keys.g2_host), ctypes.c_size_t(n2), P(sc2), ctypes.c_size_t(G2_AFFINE.itemsize)))
+        _lib.check(L.snarkvm_hip_msm_g2(P(out_g2), P(keys.g2_host), n2, P(sc2), G2_AFFINE.itemsize))
         t["g2"] += time.perf_counter() - t0
     if collect is not None:
         def finish():  # the hiding term (<= 3 points: the reference's CPU path) and the closing addition
@@ -919,7 +910,7 @@ def replay_ffi(host, salt=0, collect=None, times=None, g2=True):
                 both[0] = plain[0]
                 both[1] = msm(nmax, hid.shape[0], hid)[0]
                 tot = np.zeros(1, dtype=G1_PROJECTIVE)
-                _lib.check(L.snarkvm_hip_g1_sum(P(tot), P(both), ctypes.c_size_t(2)))
+                _lib.check(L.snarkvm_hip_g1_sum(P(tot), P(both), 2))
                 collect.append(tot.tobytes())
             if out_g2 is not None:
                 collect.append(out_g2.tobytes())

@@ -37,8 +37,7 @@ def g1_deserialize(data, compressed=False, validate=False):
         raise SerializationError("truncated input")
     n = buf.shape[0] // psz
     out = np.zeros(n, dtype=G1_AFFINE)
-    _check(_lib.lib().snarkvm_hip_g1_deserialize(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(buf.ctypes.data), ctypes.c_size_t(n),
-                                                ctypes.c_int(int(compressed)), ctypes.c_int(int(validate))))
+    _check(_lib.lib().snarkvm_hip_g1_deserialize(out.ctypes.data, buf.ctypes.data, n, int(compressed), int(validate)))
     return out
 
 
@@ -47,8 +46,7 @@ def g1_serialize(points, compressed=False):
     points = np.ascontiguousarray(points, dtype=G1_AFFINE).reshape(-1)
     psz = COMPRESSED_SIZE if compressed else UNCOMPRESSED_SIZE
     out = np.zeros(points.shape[0] * psz, dtype=np.uint8)
-    _check(_lib.lib().snarkvm_hip_g1_serialize(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(points.ctypes.data), ctypes.c_size_t(points.shape[0]),
-                                              ctypes.c_size_t(G1_AFFINE.itemsize), ctypes.c_int(int(compressed))))
+    _check(_lib.lib().snarkvm_hip_g1_serialize(out.ctypes.data, points.ctypes.data, points.shape[0], G1_AFFINE.itemsize, int(compressed)))
     return out.tobytes()
 
 
@@ -65,8 +63,7 @@ def register_bases_serialized(data, npoints, compressed=False, validate=False, t
     """bytes -> opaque registered-bases handle (snarkvm_hip_register_bases_serialized)."""
     buf = np.frombuffer(bytes(data), dtype=np.uint8)
     h = ctypes.c_void_p()
-    _check(_lib.lib().snarkvm_hip_register_bases_serialized(ctypes.byref(h), ctypes.c_void_p(buf.ctypes.data), ctypes.c_size_t(npoints),
-                                                           ctypes.c_int(int(compressed)), ctypes.c_int(int(validate)), ctypes.c_int(int(tables))))
+    _check(_lib.lib().snarkvm_hip_register_bases_serialized(ctypes.byref(h), buf.ctypes.data, npoints, int(compressed), int(validate), int(tables)))
     return h
 
 
@@ -86,7 +83,7 @@ def g2_deserialize(data, validate=False, compressed=False):
     n = buf.shape[0] // psz
     out = np.zeros(n, dtype=G2_AFFINE)
     fn = _lib.lib().snarkvm_hip_g2_deserialize_compressed if compressed else _lib.lib().snarkvm_hip_g2_deserialize
-    _check(fn(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(buf.ctypes.data), ctypes.c_size_t(n), ctypes.c_int(int(validate))))
+    _check(fn(out.ctypes.data, buf.ctypes.data, n, int(validate)))
     return out
 
 
@@ -96,5 +93,5 @@ def g2_serialize(points, compressed=False):
     points = np.ascontiguousarray(points, dtype=G2_AFFINE).reshape(-1)
     out = np.zeros(points.shape[0] * (G2_COMPRESSED_SIZE if compressed else G2_UNCOMPRESSED_SIZE), dtype=np.uint8)
     fn = _lib.lib().snarkvm_hip_g2_serialize_compressed if compressed else _lib.lib().snarkvm_hip_g2_serialize
-    _check(fn(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(points.ctypes.data), ctypes.c_size_t(points.shape[0]), ctypes.c_size_t(G2_AFFINE.itemsize)))
+    _check(fn(out.ctypes.data, points.ctypes.data, points.shape[0], G2_AFFINE.itemsize))
     return out.tobytes()

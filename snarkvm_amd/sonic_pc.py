@@ -100,8 +100,7 @@ class CommitterUnionKey:
             place(("lagrange", s), v)
         allpts = np.concatenate(parts)
         self._h = ctypes.c_void_p()
-        _lib.check(_lib.lib().snarkvm_hip_register_bases_tables(ctypes.byref(self._h), ctypes.c_void_p(allpts.ctypes.data), ctypes.c_size_t(allpts.shape[0]),
-                                                               ctypes.c_size_t(G1_AFFINE.itemsize), ctypes.c_int(0), ctypes.c_int(int(tables))))
+        _lib.check(_lib.lib().snarkvm_hip_register_bases_tables(ctypes.byref(self._h), allpts.ctypes.data, allpts.shape[0], G1_AFFINE.itemsize, 0, int(tables)))
 
     # ---- the views the reference hands to KZG10 (host arrays + their place in the registered vector)
     def powers(self):  # data_structures.rs:302-307
@@ -207,8 +206,7 @@ class SonicKZG10:
         if k:
             arr = lambda v: (ctypes.c_size_t * k)(*v)  # noqa: E731
             ptrs = (ctypes.c_void_p * k)(*[s.ctypes.data for s in scal])
-            _lib.check(_lib.lib().snarkvm_hip_msm_registered_batch_ex(ctypes.c_void_p(outs.ctypes.data), ck._h, ctypes.c_size_t(k), arr(off0), arr(n0), arr(off1),
-                                                                     arr(n1), ptrs, ctypes.c_int(0), ctypes.c_int(1), ctypes.c_int(0)))
+            _lib.check(_lib.lib().snarkvm_hip_msm_registered_batch_ex(outs.ctypes.data, ck._h, k, arr(off0), arr(n0), arr(off1), arr(n1), ptrs, 0, 1, 0))
         affine = kzg10.to_affine(outs) if k else np.zeros(0, dtype=G1_AFFINE)
         return [LabeledCommitment(p.label, affine[i], p.degree_bound) for i, p in enumerate(items)], rands
 

@@ -77,6 +77,132 @@ def test_rust_sys_matches_the_header():
     assert sys_rs == gen.generate(), "sys.rs is stale: run python tools/gen_bindings.py"
 
 
+def _gen():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("gen_bindings", os.path.join(util.ROOT, "tools", "gen_bindings.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+def test_python_abi_table_matches_the_header():
+    """snarkvm_amd/_abi.py is exactly what tools/gen_bindings.py yields today, and lists the header's functions in the header's order."""
+    from snarkvm_amd import _abi
+
+    gen = _gen()
+    text = open(os.path.join(util.ROOT, "snarkvm_amd", "_abi.py")).read()
+    assert text.startswith("# @generated") and "DO NOT EDIT" in text.splitlines()[0]
+    assert text == gen.generate_py(), "_abi.py is stale: run python tools/gen_bindings.py"
+    names = [f["name"] for f in gen.parse_header()[0]]
+    assert [name for name, _, _ in _abi.FUNCTIONS] == names and _lib.SYMBOLS == names
+
+
+def _ctypes_class(t):
+    """Width class of a ctypes restype / argtypes entry, in the vocabulary of tools/gen_bindings.py::width_class (pointers without a depth)."""
+    if t is None:
+        return ("void",)
+    if t is _lib.RustError:
+        return ("err",)
+    if t in (ctypes.c_void_p, ctypes.c_char_p):
+        return ("ptr",)
+    if t is ctypes.c_double:
+        return ("f64",)
+    assert t in (ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_long, ctypes.c_ulong), t
+    return ("int", ctypes.sizeof(t))
+
+
+def test_every_function_is_bound_as_the_header_declares():
+    """The loaded library's functions against include/snarkvm_hip.h (the expectation is computed from the header, not read from _abi.py): argtypes
+    of the declared length, every argument and the result in the declared width class; pointer arguments are exactly c_void_p."""
+    gen = _gen()
+    L = _lib.lib()
+    funcs, _ = gen.parse_header()
+    assert len(funcs) == len(_lib.SYMBOLS)
+    for f in funcs:
+        fn = getattr(L, f["name"])
+        assert fn.argtypes is not None and len(fn.argtypes) == len(f["args"]), f["name"]
+        for t, (an, ct) in zip(fn.argtypes, f["args"]):
+            want = gen.width_class(ct)
+            if want[0] == "ptr":
+                assert t is ctypes.c_void_p, (f["name"], an, t)
+            else:
+                assert _ctypes_class(t) == want, (f["name"], an, t, want)
+        want = gen.width_class(f["ret"])
+        assert _ctypes_class(fn.restype) == (("ptr",) if want[0] == "ptr" else want), (f["name"], fn.restype, want)
+
+
+def test_bare_ints_travel_at_the_declared_width():
+    """A bare Python int given to a size_t parameter arrives whole (without argtypes ctypes passes it as a 32-bit C int), and bare ints and
+    addresses give what the explicitly wrapped calls of the other tests give."""
+    L = _lib.lib()
+    big = (1 << 32) + 1
+    assert L.snarkvm_hip_batch_lanes(big) == L.snarkvm_hip_batch_lanes(ctypes.c_size_t(big))
+    if "SNARKVM_HIP_TUNING" not in os.environ:  # 8 lanes below 2^20 points, 3 from there on: cut to 32 bits, 2^32 + 1 would count as 1
+        assert L.snarkvm_hip_batch_lanes(big) == L.snarkvm_hip_batch_lanes(1 << 20) != L.snarkvm_hip_batch_lanes(1)
+    for n, wb, tables, tb in ((1 << 16, 0, 1, 0), (1 << 22, 0, 16, 0), (1 << 24, 22, 12, 22), (5000, 15, 17, 15)):
+        bare, wrapped = (ctypes.c_uint32 * 10)(), (ctypes.c_uint32 * 10)()
+        rc_bare = L.snarkvm_hip_selftest_msm_plan(n, wb, tables, tb, bare)
+        rc_wrapped = L.snarkvm_hip_selftest_msm_plan(ctypes.c_size_t(n), ctypes.c_int(wb), ctypes.c_int(tables), ctypes.c_int(tb), wrapped)
+        assert rc_bare == rc_wrapped and list(bare) == list(wrapped) and any(bare), (n, wb, tables, tb)
+    # the single-polynomial copy of snarkvm_polymul (test_polymul_single_polynomial_longer_than_domain), addresses and counts as bare ints
+    p = np.arange(9 * 4, dtype=np.uint64).reshape(9, 4) + 1
+    out = np.full((16, 4), 7, dtype=np.uint64)
+    pp = (ctypes.c_void_p * 1)(p.ctypes.data)
+    for lg, plen in ((3, 9), (0, 2)):
+        with pytest.raises(_lib.HipError) as e:
+            _lib.check(L.snarkvm_polymul(out.ctypes.data, 1, pp, (ctypes.c_size_t * 1)(plen), 0, None, None, lg))
+        assert e.value.code == 1 and (out == 7).all(), lg
+    _lib.check(L.snarkvm_polymul(out.ctypes.data, 1, pp, (ctypes.c_size_t * 1)(8), 0, None, None, 3))
+    assert np.array_equal(out[:8], p[:8]) and (out[8:] == 7).all()
+
+
+def test_a_scalar_of_the_wrong_ctypes_class_is_refused():
+    """A c_int where size_t is declared raises instead of travelling on (held in a variable: written in the call it would be a finding of
+    test_call_sites_match_the_header)."""
+    wrong = ctypes.c_int(5)
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.lib().snarkvm_hip_batch_lanes(wrong)
+
+
+def test_call_sites_match_the_header():
+    """Every `.snarkvm_*(...)` call written in a .py file of the repository (read as text, nothing imported) passes the declared number of
+    positional arguments, and every argument written as ctypes.c_X(...) has the class of its parameter: pointer parameters take c_void_p or
+    c_char_p, c_size_t / c_uint64 are one class, c_int / c_int32 are one class."""
+    import ast
+
+    gen = _gen()
+    decl = {f["name"]: [gen.width_class(ct) for _, ct in f["args"]] for f in gen.parse_header()[0]}
+    wrappers = {"c_void_p": ("ptr",), "c_char_p": ("ptr",), "c_size_t": ("u", 8), "c_uint64": ("u", 8), "c_int": ("i", 4), "c_int32": ("i", 4),
+                "c_uint32": ("u", 4), "c_double": ("f64",)}
+    params = {"size_t": ("u", 8), "uint64_t": ("u", 8), "uint32_t": ("u", 4), "int": ("i", 4), "int32_t": ("i", 4), "double": ("f64",)}
+    header_args = {f["name"]: f["args"] for f in gen.parse_header()[0]}
+    seen, bad = 0, []
+    for dirpath, dirnames, files in os.walk(util.ROOT):
+        dirnames[:] = [d for d in dirnames if not d.startswith(".") and d not in ("__pycache__", "build")]
+        for fname in files:
+            if not fname.endswith(".py"):
+                continue
+            path = os.path.join(dirpath, fname)
+            for node in ast.walk(ast.parse(open(path).read(), filename=path)):
+                if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in decl):
+                    continue
+                if any(isinstance(a, ast.Starred) for a in node.args):
+                    continue
+                seen += 1
+                where = (os.path.relpath(path, util.ROOT), node.lineno, node.func.attr)
+                if len(node.args) != len(decl[node.func.attr]) or node.keywords:
+                    bad.append(where + ("argument count",))
+                    continue
+                for a, (pname, (base, levels)) in zip(node.args, header_args[node.func.attr]):
+                    if isinstance(a, ast.Call) and isinstance(a.func, ast.Attribute) and isinstance(a.func.value, ast.Name) and a.func.value.id == "ctypes" and a.func.attr.startswith("c_"):
+                        want = ("ptr",) if levels else ("i", 4) if base in gen.ENUMS else params[base]
+                        if wrappers.get(a.func.attr) != want:
+                            bad.append(where + (pname, a.func.attr))
+    assert not bad, bad
+    assert seen >= 500, seen
+
+
 def test_rust_error_layout():
     # sppark cuda::Error {code: i32, message: *mut c_char}: 16 bytes on x86-64
     assert ctypes.sizeof(_lib.RustError) == 16

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Generates rust/snarkvm-algorithms-hip/src/sys.rs from include/snarkvm_hip.h: every `snarkvm_*` declaration of the header becomes one item
-of an `extern "C"` block (the reference's crate binds everything its library exports by hand, algorithms/cuda/src/lib.rs:42-69; its build.rs
-compiles the device code, algorithms/cuda/build.rs:71-93 - here the library is prebuilt and the declarations are derived mechanically so that
-they cannot drift from the header).
+"""Generates the two bindings of include/snarkvm_hip.h: rust/snarkvm-algorithms-hip/src/sys.rs, where every `snarkvm_*` declaration of the header
+becomes one item of an `extern "C"` block (the reference's crate binds everything its library exports by hand, algorithms/cuda/src/lib.rs:42-69;
+its build.rs compiles the device code, algorithms/cuda/build.rs:71-93 - here the library is prebuilt and the declarations are derived mechanically
+so that they cannot drift from the header), and snarkvm_amd/_abi.py, the prototype table snarkvm_amd/_lib.py sets every ctypes restype / argtypes from.
 
-    python tools/gen_bindings.py            # rewrite sys.rs
-    python tools/gen_bindings.py --check    # exit 1 if the committed sys.rs differs from what the header yields
+    python tools/gen_bindings.py            # rewrite both
+    python tools/gen_bindings.py --check    # exit 1 if a committed file differs from what the header yields
 
-`parse_header` is also what tests/test_abi.py uses for the header side of its header-vs-Rust comparison (the Rust side is parsed from the text of
-sys.rs by the test itself).  Type map: size_t -> usize, int -> i32, uint32_t -> u32, int32_t -> i32, uint64_t -> u64, double -> f64, char -> c_char,
+`parse_header` is also what tests/test_abi.py uses for the header side of its comparisons (the Rust side is parsed from the text of sys.rs by the
+test itself; the Python side is read off the loaded library's functions).  Rust type map: size_t -> usize, int -> i32, uint32_t -> u32, int32_t -> i32, uint64_t -> u64, double -> f64, char -> c_char,
 void -> c_void, `enum X` -> the #[repr(C)] enum X of lib.rs, RustError -> Error, the opaque handle structs -> zero-sized #[repr(C)] structs;
-`const T *` -> *const T, `T *` -> *mut T, `T *const *` -> *const *mut T.
+`const T *` -> *const T, `T *` -> *mut T, `T *const *` -> *const *mut T.  Python tags (snarkvm_amd/_lib.py maps them to ctypes): a pointer argument of any
+depth, constness or pointee -> "ptr" (c_void_p: call sites pass addresses, byref(), arrays, handles and None alike), size_t -> "size", int and the
+three enums -> "int", int32_t -> "i32", uint32_t -> "u32", uint64_t -> "u64", double -> "f64"; results: RustError -> "err", void -> "void",
+`void *` -> "ptr", `const char *` -> "str".
 """
 import os
 import re
@@ -19,8 +22,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "snarkvm_hip.h")
 SYS_RS = os.path.join(ROOT, "rust", "snarkvm-algorithms-hip", "src", "sys.rs")
+ABI_PY = os.path.join(ROOT, "snarkvm_amd", "_abi.py")
 
 SCALARS = {"size_t": "usize", "int": "i32", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "double": "f64", "char": "c_char", "void": "c_void"}
+PY_TAGS = {"size_t": "size", "int": "int", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "double": "f64"}
 ENUMS = ("NTTInputOutputOrder", "NTTDirection", "NTTType")
 OPAQUE = ("snarkvm_hip_bases_t", "snarkvm_hip_bases_g2_t", "snarkvm_hip_fr_matrix_t")
 RUST_KEYWORDS = {"type", "in", "ref", "move", "fn", "box", "loop", "match", "mod", "use", "where", "impl", "self", "super", "trait", "yield"}
@@ -138,18 +143,46 @@ def generate():
     return "\n".join(out) + "\n"
 
 
+def py_tag(ct, result=False):
+    base, levels = ct
+    if levels:
+        return "str" if result and base == "char" else "ptr"
+    if base == "RustError":
+        return "err"
+    if base == "void":
+        return "void"
+    return "int" if base in ENUMS else PY_TAGS[base]
+
+
+def generate_py():
+    funcs, _ = parse_header()
+    out = ["# @generated by tools/gen_bindings.py from include/snarkvm_hip.h - DO NOT EDIT (tests/test_abi.py::test_python_abi_table_matches_the_header fails on drift).",
+           '"""The prototypes of libsnarkvm_hip.so as data: (name, result tag, argument tags) per function of include/snarkvm_hip.h, in header order.',
+           'snarkvm_amd/_lib.py maps the tags to ctypes; the header\'s comments are the documentation of every function."""',
+           "FUNCTIONS = ("]
+    for f in funcs:
+        args = "".join(f'"{py_tag(t)}", ' for _, t in f["args"]).rstrip()
+        if len(f["args"]) > 1:
+            args = args[:-1]
+        out.append(f'    ("{f["name"]}", "{py_tag(f["ret"], result=True)}", ({args})),')
+    out.append(")")
+    return "\n".join(out) + "\n"
+
+
 def main():
-    text = generate()
+    outputs = [(SYS_RS, generate()), (ABI_PY, generate_py())]
     if "--check" in sys.argv:
-        have = open(SYS_RS).read() if os.path.exists(SYS_RS) else ""
-        if have != text:
-            print(f"{SYS_RS} is stale: run python tools/gen_bindings.py", file=sys.stderr)
+        stale = [path for path, text in outputs if not os.path.exists(path) or open(path).read() != text]
+        for path in stale:
+            print(f"{path} is stale: run python tools/gen_bindings.py", file=sys.stderr)
+        if stale:
             sys.exit(1)
-        print("sys.rs is current")
+        print("sys.rs and _abi.py are current")
         return
-    with open(SYS_RS, "w") as fh:
-        fh.write(text)
-    print(f"wrote {SYS_RS}: {text.count('pub fn ')} functions")
+    for path, text in outputs:
+        with open(path, "w") as fh:
+            fh.write(text)
+        print(f"wrote {path}: {len(parse_header()[0])} functions")
 
 
 if __name__ == "__main__":
