@@ -449,6 +449,41 @@ void snarkvm_hip_fr_matrix_free(snarkvm_hip_fr_matrix_t *handle);
 RustError snarkvm_hip_fr_spmv(void *y, size_t n_out, const snarkvm_hip_fr_matrix_t *handle, const void *x, size_t count, size_t stride_x, size_t stride_y,
                               int on_device);
 
+/* Varuna round 4 over a REGISTERED arithmetization (csrc/poly.hip.h: fr_sumcheck_evals_kernel): the evaluations on K that
+ * calculate_matrix_sumcheck_witness (snark/varuna/ahp/prover/round_functions/fourth.rs:155-245) builds per matrix M in {A, B, C} from the circuit's
+ * row, col and row_col_val on K (ahp/matrices.rs:101-195) and the challenges alpha, beta.  With r, c, v the three at kappa and
+ * d = (alpha - r)(beta - c) (the reference forms it twice: as this product for f, expanded as alpha beta - beta r - alpha c + r c for b):
+ *     a[kappa] = a_scale * v        b[kappa] = b_scale * d        f[kappa] = f_scale * v / d, and 0 where d = 0
+ * (the zero rule of batch_inversion_and_mul, fields/src/lib.rs:66-129, followed by the product with v).  The caller passes the reference's
+ * a_scale = v_R(alpha) v_C(beta), b_scale = |R| |C|, f_scale = a_scale / (|R| |C|).  One fused pass - Montgomery's trick with one shared inversion per
+ * thread - where the existing entry points need a dozen launches per matrix.  The arithmetization is circuit data, fixed for the life of a proving
+ * key like the SRS and the R1CS matrices: register once, evaluate for every proof.
+ * fr_arith_register: row, col, row_col_val are HOST arrays of k elements (32 bytes, Montgomery form), not retained; k need not be a power of
+ * two; k == 0 is legal.  One replica per device of the current device set, like snarkvm_hip_fr_matrix_register.
+ *  - Refused with hipErrorInvalidValue BEFORE a device is needed and before anything is allocated (*handle, when given, is NULL afterwards): a NULL
+ *    handle; a NULL array with k > 0; k > 2^28.
+ * fr_arith_free: NULL is a no-op.  The replicas are released with hipFree, which returns only when every stream of their device is idle: freeing a
+ * handle while a scope of the calling thread still has an evaluation enqueued is safe, as for snarkvm_hip_fr_matrix_free.
+ * fr_matrix_sumcheck_evals: `count` members in ONE launch; member m writes k_m elements (the k of ariths[m]) to each of a_evals[m], b_evals[m],
+ * f_evals[m].  alpha, beta and the three scales (a_scale, b_scale, f_scale: 3 x 32 bytes) are HOST values shared by all members - they belong to one
+ * circuit (fourth.rs:94-121).  An output pointer, or a whole pointer array, may be NULL: that output is skipped (a call without any f skips the
+ * inversion too).
+ *  - on_device = 1: the outputs are device pointers on one device; inside a snarkvm_hip_scope the call is only enqueued.  on_device = 0: host
+ *    outputs, staged like the other passes, the results are there on return.
+ *  - Refused with hipErrorInvalidValue before anything is launched, every output untouched: count > 16; a NULL `ariths` with count > 0 or a NULL
+ *    handle in it; NULL alpha, beta or scales; outputs of one call that overlap each other; with on_device = 1 outputs on different devices;
+ *    a handle without a replica on the outputs' device.
+ *  - count == 0, or every k_m == 0: success, nothing is touched, no device is needed (the same when every output of every member is NULL).
+ *  - Workspace: none with on_device = 1 - the running products of the trick are parked in the f output itself before f overwrites them; with
+ *    on_device = 0 the staged outputs live in one buffer of the calling lane.  A repeated call grows nothing (snarkvm_hip_alloc_stats).
+ *  - No atomics; every thread owns its elements, field arithmetic is exact and results canonical: the 32 bytes of every output depend on neither
+ *    the thread count nor the grid. */
+typedef struct snarkvm_hip_fr_arith snarkvm_hip_fr_arith_t;
+RustError snarkvm_hip_fr_arith_register(snarkvm_hip_fr_arith_t **handle, size_t k, const void *row, const void *col, const void *row_col_val);
+void snarkvm_hip_fr_arith_free(snarkvm_hip_fr_arith_t *handle);
+RustError snarkvm_hip_fr_matrix_sumcheck_evals(const snarkvm_hip_fr_arith_t *const *ariths, size_t count, void *const *a_evals, void *const *b_evals,
+                                               void *const *f_evals, const void *alpha, const void *beta, const void *scales, int on_device);
+
 /* Strided batches of the passes above on device memory - the same pass over one vector of every proof of a batch proved in lock
  * step (VarunaSNARK::prove_batch, snark/varuna/varuna.rs:336): member y of the batch uses every vector pointer advanced by
  * y * stride elements (stride >= the vector length); ONE kernel launch sequence for the whole batch.  fr_vec_op_strided: `scalar`
@@ -562,6 +597,14 @@ int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t *out4);
 int snarkvm_hip_selftest_fr_spmv(void *y, size_t n_out, size_t rows, size_t cols, const uint64_t *row_ptr, const uint32_t *col_idx, const void *vals,
                                  const void *x, uint32_t seg, uint32_t width);
 int snarkvm_hip_selftest_fr_spmv_geometry(size_t rows, size_t nnz, uint32_t *out4);
+/* snarkvm_hip_fr_matrix_sumcheck_evals for one member over host memory with the CPU in the kernel's place, over a GIVEN geometry: blocks x threads
+ * threads in all (any counts >= 1; more threads than elements is allowed), thread t owning t, t + T, ... through the kernel's own per-thread routine
+ * and the same host-side constants (csrc/poly.hip.h: fr_sumcheck_thread, fr_sumcheck_consts).  a, b, f may be NULL (skipped).  0, or -1 when the
+ * arguments are refused.  fr_sumcheck_geometry: out4 = {threads T, threads per workgroup, workgroups, elements per thread (the share the thread
+ * count is derived from)} of what the device call launches for a member of k elements; 0, or -1 for a NULL out or k > 2^28. */
+int snarkvm_hip_selftest_fr_sumcheck(void *a, void *b, void *f, const void *row, const void *col, const void *rcv, size_t k, const void *alpha,
+                                     const void *beta, const void *scales, uint32_t blocks, uint32_t threads);
+int snarkvm_hip_selftest_fr_sumcheck_geometry(size_t k, uint32_t *out);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 /* Field arithmetic that the two operands of snarkvm_hip_selftest_field cannot express, one case per record, operands and results in memory

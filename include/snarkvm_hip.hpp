@@ -266,4 +266,27 @@ private:
     size_t rows_, cols_;
 };
 
+// A registered arithmetization (snarkvm_hip.h: snarkvm_hip_fr_arith_register): row, col and row_col_val of one matrix on K go to HBM once per
+// proving key; matrix_sumcheck_evals() below is the fused round-4 pass over up to 16 of them (round_functions/fourth.rs:155-245).
+class RegisteredArithmetization {
+public:
+    RegisteredArithmetization(size_t k, const void* row, const void* col, const void* row_col_val) : k_(k) {
+        check(snarkvm_hip_fr_arith_register(&h_, k, row, col, row_col_val));
+    }
+    RegisteredArithmetization(const RegisteredArithmetization&) = delete;
+    RegisteredArithmetization& operator=(const RegisteredArithmetization&) = delete;
+    ~RegisteredArithmetization() { snarkvm_hip_fr_arith_free(h_); }  // waits for the device: safe with an evaluation still enqueued in this thread's Scope
+    size_t size() const { return k_; }
+    const snarkvm_hip_fr_arith_t* handle() const { return h_; }
+
+private:
+    snarkvm_hip_fr_arith_t* h_ = nullptr;
+    size_t k_;
+};
+// a, b, f on K for `count` arithmetizations in one launch; an output pointer or a whole list may be null (skipped); scales = a_scale, b_scale, f_scale
+inline void matrix_sumcheck_evals(const snarkvm_hip_fr_arith_t* const* ariths, size_t count, void* const* a_evals, void* const* b_evals, void* const* f_evals,
+                                  const void* alpha, const void* beta, const void* scales, bool on_device) {
+    check(snarkvm_hip_fr_matrix_sumcheck_evals(ariths, count, a_evals, b_evals, f_evals, alpha, beta, scales, on_device ? 1 : 0));
+}
+
 }  // namespace snarkvm_hip

@@ -1054,6 +1054,161 @@ int snarkvm_hip_selftest_fr_spmv_geometry(size_t rows, size_t nnz, uint32_t* out
     return 0;
 }
 
+// ---- Varuna round 4: matrix-sumcheck evaluations over a registered arithmetization (poly.hip.h: fr_sumcheck_evals_kernel) -----------
+static constexpr size_t FR_ARITH_K_MAX = (size_t)1 << NTT_LG_MAX;
+}  // extern "C"
+// one replica per logical device, like a registered matrix: ONE block holding row | col | row_col_val, k elements each
+struct snarkvm_hip_fr_arith {
+    size_t k = 0;
+    std::vector<fr_mem_t*> d;  // [logical device]
+    void free_all() {
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        for (size_t i = 0; i < d.size(); i++)
+            if (d[i]) {
+                (void)hipSetDevice(g_rt.devs[i]->physical);
+                (void)hipFree(d[i]);  // waits for every stream of the device: nothing queued - an open scope's evaluation included - can still use the block
+                d[i] = nullptr;
+            }
+        (void)hipSetDevice(prev);
+    }
+};
+extern "C" {
+RustError snarkvm_hip_fr_arith_register(snarkvm_hip_fr_arith_t** handle, size_t k, const void* row, const void* col, const void* row_col_val) {
+    if (!handle) return fail((int)hipErrorInvalidValue, "snarkvm_hip: fr_arith_register: null handle");
+    *handle = nullptr;
+    if (k > FR_ARITH_K_MAX) return fail((int)hipErrorInvalidValue, "snarkvm_hip: fr_arith_register: more than 2^28 elements");
+    if (k && (!row || !col || !row_col_val)) return fail((int)hipErrorInvalidValue, "snarkvm_hip: fr_arith_register: null array of a non-empty arithmetization");
+    API_TRY
+    std::unique_ptr<snarkvm_hip_fr_arith> h(new snarkvm_hip_fr_arith());
+    h->k = k;
+    const int nd = g_rt.ndev();
+    h->d.assign(nd, nullptr);
+    try {
+        std::vector<int> all;
+        for (int d = 0; d < nd; d++) all.push_back(d);
+        for_each_device(all, [&](int dev) {  // every device uploads its own replica
+            lane_guard lg(dev);
+            lane_t& c = lg.c();
+            const size_t bytes = sizeof(fr_mem_t) * k;
+            HIP_TRY(hipMalloc((void**)&h->d[dev], k ? 3 * bytes : 32));
+            if (k) {
+                HIP_TRY(hipMemcpyAsync(h->d[dev], row, bytes, hipMemcpyHostToDevice, c.stream));
+                HIP_TRY(hipMemcpyAsync(h->d[dev] + k, col, bytes, hipMemcpyHostToDevice, c.stream));
+                HIP_TRY(hipMemcpyAsync(h->d[dev] + 2 * k, row_col_val, bytes, hipMemcpyHostToDevice, c.stream));
+                HIP_TRY(hipStreamSynchronize(c.stream));
+            }
+        });
+    } catch (...) {
+        h->free_all();
+        throw;
+    }
+    *handle = h.release();
+    API_CATCH
+}
+void snarkvm_hip_fr_arith_free(snarkvm_hip_fr_arith_t* h) {
+    if (!h) return;
+    h->free_all();
+    delete h;
+}
+// one wanted output of a call: member, which of a / b / f, the caller's pointer, elements
+struct fr_sumcheck_out_t {
+    size_t m;
+    int which;
+    uint8_t* p;
+    size_t k;
+};
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  outs: every non-NULL output of a member with k > 0.
+static const char* fr_sumcheck_check(const snarkvm_hip_fr_arith_t* const* ariths, size_t count, void* const* a, void* const* b, void* const* f, const void* alpha,
+                                     const void* beta, const void* scales, std::vector<fr_sumcheck_out_t>& outs) {
+    if (count > (size_t)FR_SUMCHECK_MEMBERS) return "more than 16 members";
+    if (!ariths) return "null list of handles";
+    for (size_t m = 0; m < count; m++)
+        if (!ariths[m]) return "null handle in the list";
+    if (!alpha || !beta || !scales) return "null alpha, beta or scales";
+    void* const* lists[3] = {a, b, f};
+    for (size_t m = 0; m < count; m++)
+        for (int w = 0; w < 3; w++)
+            if (ariths[m]->k && lists[w] && lists[w][m]) outs.push_back({m, w, (uint8_t*)lists[w][m], ariths[m]->k});
+    // sorted by address: any overlap shows between neighbours
+    std::vector<fr_sumcheck_out_t> by_addr(outs);
+    std::sort(by_addr.begin(), by_addr.end(), [](const fr_sumcheck_out_t& x, const fr_sumcheck_out_t& y) { return x.p < y.p; });
+    for (size_t i = 1; i < by_addr.size(); i++)
+        if (by_addr[i].p < by_addr[i - 1].p + sizeof(fr_mem_t) * by_addr[i - 1].k) return "two outputs overlap";
+    return nullptr;
+}
+RustError snarkvm_hip_fr_matrix_sumcheck_evals(const snarkvm_hip_fr_arith_t* const* ariths, size_t count, void* const* a_evals, void* const* b_evals, void* const* f_evals,
+                                               const void* alpha, const void* beta, const void* scales, int on_device) {
+    if (count == 0) return ok();
+    std::vector<fr_sumcheck_out_t> outs;
+    if (const char* why = fr_sumcheck_check(ariths, count, a_evals, b_evals, f_evals, alpha, beta, scales, outs))
+        return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_matrix_sumcheck_evals: ") + why);
+    if (outs.empty()) return ok();  // every k_m == 0, or nothing wanted
+    API_BEGIN_DEV(device_for(outs[0].p, on_device ? 1 : 0))
+    const int dev = c.dev->logical;
+    if (on_device)
+        for (const fr_sumcheck_out_t& o : outs) fr_same_device(c, o.p, "fr_matrix_sumcheck_evals: the outputs live on different devices");
+    fr_sumcheck_t tab{};
+    size_t threads = 0;
+    for (const fr_sumcheck_out_t& o : outs) {
+        const snarkvm_hip_fr_arith& h = *ariths[o.m];
+        if (dev >= (int)h.d.size() || !h.d[dev]) throw hip_failure{hipErrorInvalidValue, "fr_matrix_sumcheck_evals: a handle has no replica on this device", __LINE__};
+        fr_sumcheck_member_t& mb = tab.m[o.m];
+        mb.row = h.d[dev], mb.col = h.d[dev] + h.k, mb.rcv = h.d[dev] + 2 * h.k;
+        mb.k = h.k, mb.T = fr_sumcheck_threads(h.k);
+        if (mb.T > threads) threads = mb.T;
+    }
+    fr_mem_t* staged = nullptr;
+    if (!on_device) {  // host outputs: one lane buffer holds them one behind the other; one download each
+        size_t total = 0;
+        for (const fr_sumcheck_out_t& o : outs) total += o.k;
+        c.poly[0].ensure(sizeof(fr_mem_t) * total);
+        staged = c.poly[0].as<fr_mem_t>();
+    }
+    {
+        fr_mem_t* next = staged;
+        for (const fr_sumcheck_out_t& o : outs) {
+            fr_mem_t* d = on_device ? (fr_mem_t*)o.p : next;
+            fr_sumcheck_member_t& mb = tab.m[o.m];
+            (o.which == 0 ? mb.a : (o.which == 1 ? mb.b : mb.f)) = d;
+            if (!on_device) next += o.k;
+        }
+    }
+    const uint8_t* sc = (const uint8_t*)scales;
+    const fr_mem_t sc3[3] = {fr_mem_from_host(sc), fr_mem_from_host(sc + sizeof(fr_mem_t)), fr_mem_from_host(sc + 2 * sizeof(fr_mem_t))};
+    tab.cs = fr_sumcheck_consts(fr_mem_from_host(alpha), fr_mem_from_host(beta), sc3);
+    hipLaunchKernelGGL(fr_sumcheck_evals_kernel, dim3((unsigned)((threads + FR_SUMCHECK_B - 1) / FR_SUMCHECK_B), (unsigned)count), dim3(FR_SUMCHECK_B), 0, c.stream, tab);
+    HIP_TRY(hipGetLastError());
+    if (!on_device) {
+        fr_mem_t* next = staged;
+        for (const fr_sumcheck_out_t& o : outs) {
+            HIP_TRY(hipMemcpyAsync(o.p, next, sizeof(fr_mem_t) * o.k, hipMemcpyDeviceToHost, c.stream));
+            next += o.k;
+        }
+    }
+    fr_call_done(c, on_device);
+    API_END
+}
+// One member on host memory with the CPU in the kernel's place over blocks x threads threads: the same constants, every thread through
+// fr_sumcheck_thread.  0, or -1 when refused.
+int snarkvm_hip_selftest_fr_sumcheck(void* a, void* b, void* f, const void* row, const void* col, const void* rcv, size_t k, const void* alpha, const void* beta,
+                                     const void* scales, uint32_t blocks, uint32_t threads) {
+    if (k > FR_ARITH_K_MAX || (k && (!row || !col || !rcv)) || !alpha || !beta || !scales || blocks < 1 || threads < 1) return -1;
+    const uint8_t* sc = (const uint8_t*)scales;
+    const fr_mem_t sc3[3] = {fr_mem_from_host(sc), fr_mem_from_host(sc + sizeof(fr_mem_t)), fr_mem_from_host(sc + 2 * sizeof(fr_mem_t))};
+    const fr_sumcheck_consts_t cs = fr_sumcheck_consts(fr_mem_from_host(alpha), fr_mem_from_host(beta), sc3);
+    fr_sumcheck_member_t mb{(const fr_mem_t*)row, (const fr_mem_t*)col, (const fr_mem_t*)rcv, (fr_mem_t*)a, (fr_mem_t*)b, (fr_mem_t*)f, k, (size_t)blocks * threads};
+    for (size_t t = 0; t < mb.T && t < k; t++) fr_sumcheck_thread(mb, cs, t);
+    return 0;
+}
+// what snarkvm_hip_fr_matrix_sumcheck_evals launches for a member of k elements: out4 = {threads, threads per workgroup, workgroups, elements per thread}
+int snarkvm_hip_selftest_fr_sumcheck_geometry(size_t k, uint32_t* out4) {
+    if (!out4 || k > FR_ARITH_K_MAX) return -1;
+    const size_t T = fr_sumcheck_threads(k);
+    out4[0] = (uint32_t)T, out4[1] = FR_SUMCHECK_B, out4[2] = (uint32_t)((T + FR_SUMCHECK_B - 1) / FR_SUMCHECK_B), out4[3] = (uint32_t)fr_sumcheck_share(k);
+    return 0;
+}
+
 // ---- setup-time group operations (group.hip.h) -------------------------------------------------------
 RustError snarkvm_hip_g1_fixed_base_msm(void* out_projective, const void* g_affine, const void* scalars, size_t n) {
     API_BEGIN

@@ -13,6 +13,7 @@
 //   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
 //   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
 //   fr_spmv_seg_kernel          y = M x over a registered CSR matrix, segment by segment  round_functions/mod.rs:131-188 (z_M), third.rs:303-306 (M(alpha, .))
+//   fr_sumcheck_evals_kernel    a, b, f of the matrix sumcheck on K over a registered arithmetization  round_functions/fourth.rs:155-245
 //
 // Representation note (ff.hip.h): the raw memory limbs of a, read as an internal value, are the internal Montgomery form of
 // a * 2^-5 ("shifted").  Sums and differences of shifted values are shifted values; the product of a TRUE internal
@@ -638,6 +639,117 @@ static __global__ void __launch_bounds__(FR_SPMV_B) fr_spmv_fix_kernel(const fr_
         fr_spmv_finish(v).store(&y[(size_t)blockIdx.y * stride_y + f.row]);
     else if (g - nfix < n_out - rows)
         fr_t::zero().store(&y[(size_t)blockIdx.y * stride_y + rows + (g - nfix)]);
+}
+#endif
+
+// ---- Varuna round 4: the matrix-sumcheck evaluations on K over a registered arithmetization ---------------------------------
+// calculate_matrix_sumcheck_witness (round_functions/fourth.rs:155-245) per matrix M: with r, c, v = row, col, row_col_val at kappa in K
+// (ahp/matrices.rs:101-195) and d = (alpha - r)(beta - c) - the reference forms this element twice, as the product for f and expanded as
+// alpha beta - beta r - alpha c + r c for b -
+//   a = a_scale v,   b = b_scale d,   f = f_scale v / d   (f = 0 where d = 0: batch_inversion_and_mul leaves zeros, fields/src/lib.rs:66-129).
+// One fused pass instead of a dozen fr_vec_op / fr_batch_inversion_and_mul launches: Montgomery's trick per thread over the strided set
+// {t, t + T, ...} as in fr_batch_inverse_kernel, the forward sweep forming d from row and col and parking the running product, the backward
+// sweep emitting a, b and f.  The running products are parked IN THE f OUTPUT ITSELF: a thread owns its indices, reads slot i - T before it
+// writes f[i] and has read slot i one step earlier, so the pass needs no workspace at all; a call that wants no f skips the sweep and the inversion.
+// blockIdx.y is the batch member (the matrices A, B, C of one circuit: members of different lengths, the same alpha, beta and scales); the member
+// table and the constants travel BY KERNEL ARGUMENT like fr_lincomb_t (nothing staged, nothing to release after an enqueue-only call).
+// Forms (top of this file): alpha - r and beta - c are differences of raw ("shifted") values, their product p is the internal form of d 2^-10.
+// The chain of products, its Fermat inverse and the unwinding run on p as it is; the powers of two this leaves behind are folded into the three
+// constants ONCE, on the host (fr_sumcheck_consts): a = raw(v) * A, b = p * B, f = raw(v) * (inv_i * F-carried) are memory-form values, canonical
+// like every product.  7 products per element and one inversion (~300) per thread.
+// Geometry (fr_sumcheck_share): the Fermat inversion is a chain of ~300 DEPENDENT products that every thread pays, so the pass is bound by that
+// latency until the chip is full; a member gets FR_SUMCHECK_THREADS threads (three members: 768 waves over the 1024 SIMDs) and the share per thread
+// grows with k between FR_SUMCHECK_E_MIN and FR_SUMCHECK_E_MAX - 8 at |K| = 2^17, 32 from 2^19 on, where the work and not the latency decides.
+// Measured against the 32 per thread of fr_batch_inverse_run and against smaller shares: profiles/fr_sumcheck.md (tools/bench_fr_sumcheck.py).
+static constexpr int FR_SUMCHECK_B = 256;       // threads per workgroup
+static constexpr int FR_SUMCHECK_MEMBERS = 16;  // members per call: 16 x 64 B + 180 B of the 4 KB of kernel arguments
+#ifndef FR_SUMCHECK_THREADS
+#define FR_SUMCHECK_THREADS 16384  // threads per member the share is sized for; a -D override (with the two below) builds the variants tools/bench_fr_sumcheck.py compares
+#endif
+#ifndef FR_SUMCHECK_E_MIN
+#define FR_SUMCHECK_E_MIN 4
+#endif
+#ifndef FR_SUMCHECK_E_MAX
+#define FR_SUMCHECK_E_MAX 32
+#endif
+// elements per thread for a member of k elements; the member runs T = ceil(k / share) threads (no cap: 2^28 / 32 threads are 32 768 workgroups)
+SV_HD size_t fr_sumcheck_share(size_t k) {
+    const size_t e = (k + FR_SUMCHECK_THREADS - 1) / FR_SUMCHECK_THREADS;
+    return e < FR_SUMCHECK_E_MIN ? FR_SUMCHECK_E_MIN : (e > FR_SUMCHECK_E_MAX ? FR_SUMCHECK_E_MAX : e);
+}
+SV_HD size_t fr_sumcheck_threads(size_t k) {
+    const size_t e = fr_sumcheck_share(k);
+    return (k + e - 1) / e;
+}
+struct fr_sumcheck_consts_t {
+    uint32_t alpha[9], beta[9];  // raw limbs of the memory images
+    uint32_t a[9];               // a_scale, true internal form:      raw(v) * a = memory form of a_scale v
+    uint32_t b[9];               // b_scale 2^266:                    p * b      = memory form of b_scale d
+    uint32_t f[9];               // f_scale 2^251:                    carried by the inverse, raw(v) * (f / p) = memory form of f_scale v / d
+};
+// alpha, beta: memory images; scales: a_scale, b_scale, f_scale
+SV_HD fr_sumcheck_consts_t fr_sumcheck_consts(const fr_mem_t& alpha, const fr_mem_t& beta, const fr_mem_t* scales) {
+    fr_sumcheck_consts_t cs;
+    const fr_t al = fr_t::load(&alpha), be = fr_t::load(&beta);
+    const fr_t a = fr_t::load(&scales[0]).from_mem_mont();
+    const fr_t b = fr_t::load(&scales[1]).from_mem_mont().from_mem_mont();
+    const fr_t f = fr_t::load(&scales[2]) * fr_t::one().to_mem_mont();  // raw(x) * 2^256 2^-261 = x 2^251
+    for (int l = 0; l < 9; l++) cs.alpha[l] = al.v[l], cs.beta[l] = be.v[l], cs.a[l] = a.v[l], cs.b[l] = b.v[l], cs.f[l] = f.v[l];
+    return cs;
+}
+struct fr_sumcheck_member_t {
+    const fr_mem_t *row, *col, *rcv;  // the registered arithmetization, k elements each
+    fr_mem_t *a, *b, *f;              // outputs, k elements each; nullptr: skipped
+    size_t k, T;                      // thread t < T owns t, t + T, ... < k
+};
+struct fr_sumcheck_t {
+    fr_sumcheck_member_t m[FR_SUMCHECK_MEMBERS];
+    fr_sumcheck_consts_t cs;
+};
+// the whole work of thread t of a member: the kernel below and the host replay (snarkvm_hip_selftest_fr_sumcheck) both call it
+SV_HD void fr_sumcheck_thread(const fr_sumcheck_member_t& m, const fr_sumcheck_consts_t& cs, size_t t) {
+    const size_t k = m.k, T = m.T;
+    if (t >= T || t >= k) return;
+    const fr_t alpha = fr_t::from_table(cs.alpha), beta = fr_t::from_table(cs.beta);
+    fr_t inv = fr_t::zero();
+    if (m.f) {
+        fr_t run = fr_t::one();
+        bool any = false;
+#pragma unroll 1
+        for (size_t i = t; i < k; i += T) {
+            const fr_t p = (alpha - fr_t::load(&m.row[i])) * (beta - fr_t::load(&m.col[i]));
+            if (!p.is_zero()) {
+                run = run * p;
+                any = true;
+            }
+            run.store(&m.f[i]);
+        }
+        if (any) inv = run.inverse() * fr_t::from_table(cs.f);
+    }
+    const fr_t as = fr_t::from_table(cs.a), bs = fr_t::from_table(cs.b);
+    const size_t cnt = (k - t + T - 1) / T;
+#pragma unroll 1
+    for (size_t j = cnt; j-- > 0;) {
+        const size_t i = t + j * T;
+        const fr_t v = fr_t::load(&m.rcv[i]);
+        if (m.a) (v * as).store(&m.a[i]);
+        if (!m.b && !m.f) continue;
+        const fr_t p = (alpha - fr_t::load(&m.row[i])) * (beta - fr_t::load(&m.col[i]));
+        if (m.b) (p * bs).store(&m.b[i]);
+        if (!m.f) continue;
+        fr_t fv = fr_t::zero();
+        if (!p.is_zero()) {  // a zero neither entered the chain nor leaves it: its neighbours see the product of the others
+            const fr_t s = j ? fr_t::load(&m.f[i - T]) : fr_t::one();
+            fv = v * (inv * s);
+            inv = inv * p;
+        }
+        fv.store(&m.f[i]);
+    }
+}
+#if defined(__HIPCC__)
+// grid (ceil(max_m T_m / FR_SUMCHECK_B), members): a workgroup behind its member's last thread leaves at once
+static __global__ void __launch_bounds__(FR_SUMCHECK_B) fr_sumcheck_evals_kernel(fr_sumcheck_t tab) {
+    fr_sumcheck_thread(tab.m[blockIdx.y], tab.cs, blockIdx.x * (size_t)FR_SUMCHECK_B + threadIdx.x);
 }
 #endif
 

@@ -3,15 +3,20 @@ algorithms/src/snark/varuna/ahp/matrices.rs) registered once in device memory an
 
     z_M = M z for M in {A, B, C}            snark/varuna/ahp/prover/round_functions/mod.rs:131-188 (`inner_product` over every row)
     M(alpha, .) = M^T l_alpha               snark/varuna/ahp/prover/round_functions/third.rs:303-306, with the transpose of ahp/matrices.rs:250-264
+    a, b, f on K, sum, g_M, lhs_M           round_functions/fourth.rs:155-245 over the arithmetization of ahp/matrices.rs:138-195; h_2: fifth.rs:50-64
 
 The transpose is circuit data like the matrix itself: built once on the host (`transpose`) and registered; the product is
-`snarkvm_hip_fr_spmv` (include/snarkvm_hip.h).  Nothing here builds a circuit index or drives a prover round.
+`snarkvm_hip_fr_spmv` (include/snarkvm_hip.h).  The arithmetization (row, col, row_col_val on K) is circuit data too: built once on the host
+(`matrix_evals`), registered (`RegisteredArithmetization`), and turned into the round-4 witness of every proof by one fused kernel
+(`snarkvm_hip_fr_matrix_sumcheck_evals`) followed by entry points that already exist (`matrix_sumcheck_witness`).  Nothing here builds a
+circuit index or drives a prover round.
 """
 import ctypes
 
 import numpy as np
 
 from . import _lib, plugin
+from .devmem import HipMem
 
 R_MOD = 8444461749428370424248824938781546531375899335154063827935233455917409239041
 _MONT_R = (1 << 256) % R_MOD
@@ -154,3 +159,162 @@ def m_at_alpha_evals_device(reg_transposed, lg_constraint_domain, alpha, d_out, 
     tau = np.ascontiguousarray(alpha, dtype=np.uint64).reshape(1, 4)
     _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(_dev_ptr(d_lagrange), lg_constraint_domain, tau.ctypes.data, 1))
     reg_transposed.mul_device(d_out, reg_transposed.rows, d_lagrange)
+
+
+# ---- round 4: the matrix sumcheck ------------------------------------------------------------------------------------------------------------
+_TWO_ADICITY = 47
+_TWO_ADIC_ROOT = 8065159656716812877374967518403273466521432693661810619979959746626482506078  # curves/src/bls12_377/fr.rs:109-120
+
+
+def _lg(size, what):
+    size = int(size)
+    if size < 1 or size & (size - 1):
+        raise ValueError(f"{what} is not a power of two")
+    return size.bit_length() - 1
+
+
+def _domain_elements(size):
+    """the elements 1, w, w^2, ... of the multiplicative subgroup of `size` elements (EvaluationDomain::elements), Python ints"""
+    w = pow(_TWO_ADIC_ROOT, 1 << (_TWO_ADICITY - _lg(size, "a domain size")), R_MOD)
+    out, x = [], 1
+    for _ in range(size):
+        out.append(x)
+        x = x * w % R_MOD
+    return out
+
+
+def _mont_limbs(values):
+    return np.array([_fr_mont(v) for v in values], dtype=np.uint64).reshape(-1, 4)
+
+
+def _from_mont(limbs):
+    inv = pow(_MONT_R, -1, R_MOD)
+    return [(int(a) | int(b) << 64 | int(c) << 128 | int(d) << 192) * inv % R_MOD for a, b, c, d in np.asarray(limbs, dtype=np.uint64).reshape(-1, 4).tolist()]
+
+
+def matrix_evals(matrix, non_zero_domain_size, variable_domain_size, input_domain_size, constraint_domain_size=None):
+    """`matrix_evals` of ahp/matrices.rs:138-195: the arithmetization of a SparseMatrix on the non-zero domain K -> (row, col, row_col_val), each a
+    (|K|, 4) array in Montgomery memory form.  Entry (val, j) of row i gives row = the i-th element of the constraint domain (the smallest power of
+    two >= the number of rows unless constraint_domain_size says otherwise), col = element reindex_by_subdomain(j) of the variable domain and
+    row_col_val = val * row * col; the places behind the entries are padded with (1, 1, 0).  Host-side big-int work, done once per circuit."""
+    k = int(non_zero_domain_size)
+    _lg(k, "non_zero_domain_size")
+    if matrix.nnz > k:
+        raise ValueError("matrix_evals: the matrix has more entries than the non-zero domain has elements")
+    if constraint_domain_size is None:
+        constraint_domain_size = 1 << max(0, (matrix.rows - 1).bit_length())
+    if matrix.rows > constraint_domain_size:
+        raise ValueError("matrix_evals: the matrix has more rows than the constraint domain has elements")
+    r_elems, c_elems = _domain_elements(constraint_domain_size), _domain_elements(variable_domain_size)
+    at = _reindex_all(variable_domain_size, input_domain_size, matrix.col_idx).tolist() if matrix.nnz else []
+    if at and max(at) >= variable_domain_size:
+        raise ValueError("matrix_evals: a variable does not fit the variable domain")
+    src_row = np.repeat(np.arange(matrix.rows, dtype=np.int64), matrix.row_lengths()).tolist()
+    vals = _from_mont(matrix.vals)
+    row = [r_elems[i] for i in src_row] + [1] * (k - matrix.nnz)
+    col = [c_elems[j] for j in at] + [1] * (k - matrix.nnz)
+    rcv = [v * r % R_MOD * c % R_MOD for v, r, c in zip(vals, row, col)] + [0] * (k - matrix.nnz)
+    return _mont_limbs(row), _mont_limbs(col), _mont_limbs(rcv)
+
+
+class RegisteredArithmetization:
+    """row, col and row_col_val of one matrix on K resident in device memory (`snarkvm_hip_fr_arith_register`: on every device in use), for as many
+    proofs as the proving key lives - the twin of RegisteredMatrix.  close() - also run when the object dies - releases it; that is safe while a
+    scope of the calling thread still has an evaluation enqueued (the release waits for the device)."""
+
+    def __init__(self, row, col, row_col_val):
+        row, col, rcv = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (row, col, row_col_val))
+        if not row.shape[0] == col.shape[0] == rcv.shape[0]:
+            raise ValueError("RegisteredArithmetization: row, col and row_col_val differ in length")
+        self.k = row.shape[0]
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().snarkvm_hip_fr_arith_register(ctypes.byref(h), self.k, *(x.ctypes.data if self.k else None for x in (row, col, rcv))))
+        self.handle = h.value or 0
+
+    @classmethod
+    def from_matrix(cls, matrix, non_zero_domain_size, variable_domain_size, input_domain_size, constraint_domain_size=None):
+        return cls(*matrix_evals(matrix, non_zero_domain_size, variable_domain_size, input_domain_size, constraint_domain_size))
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _lib.lib().snarkvm_hip_fr_arith_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown / a dead device: nothing left to do
+            pass
+
+
+def sumcheck_scales(lg_r, lg_c, alpha, beta):
+    """a_scale = v_R(alpha) v_C(beta), b_scale = |R| |C|, f_scale = a_scale / (|R| |C|) (fourth.rs:95-97, 171-172, 208) as a (3, 4) array; alpha, beta:
+    Montgomery limbs"""
+    al, be = _from_mont(alpha)[0], _from_mont(beta)[0]
+    a_scale = (pow(al, 1 << lg_r, R_MOD) - 1) * (pow(be, 1 << lg_c, R_MOD) - 1) % R_MOD
+    b_scale = (1 << (lg_r + lg_c)) % R_MOD
+    return _mont_limbs([a_scale, b_scale, a_scale * pow(b_scale, -1, R_MOD) % R_MOD])
+
+
+class DevicePoly:
+    """`n` coefficients at device address `ptr`; `owner` keeps the block they live in alive"""
+
+    def __init__(self, ptr, n, owner):
+        self.ptr, self.n, self.owner = int(ptr), int(n), owner
+
+    def download(self):
+        out = np.empty((self.n, 4), dtype=np.uint64)
+        if self.n:
+            _lib.check(_lib.lib().snarkvm_hip_memcpy_d2h(out.ctypes.data, self.ptr, 32 * self.n))
+        return out
+
+
+def matrix_sumcheck_witness(regs, lg_r, lg_c, alpha, beta, max_non_zero_domain_size, scales=None, device=-1):
+    """`calculate_matrix_sumcheck_witness` (fourth.rs:155-245) for the registered arithmetizations `regs` of ONE circuit (constraint domain 2^lg_r,
+    variable domain 2^lg_c; every |K_M| a power of two), on device memory: the fused evaluations of a, b, f for all members, one inverse
+    transform batch per domain size, then per member `polymul_device(b, f)`, a - b f in one `fr_lincomb`, the division by v_K
+    (`fr_divide_by_vanishing`), the zero test of the remainder (`fr_support`; a non-zero remainder raises ValueError like the `ensure!` of
+    selectors.rs:92-93) and the |K_M| / |K_max| multiplier (selectors.rs:95-96).
+    -> one (sum, lhs, g, a_poly, b_poly) per member: sum = f[0] as a (1, 4) host array, the others DevicePoly - lhs |K_M| coefficients, g = f from
+    coefficient 1 on (|K_M| - 1 coefficients, a pointer offset into f: ready for a resident commitment), a_poly and b_poly |K_M| coefficients.
+    Lengths are untrimmed.  scales: (3, 4) a_scale, b_scale, f_scale when the caller has them already (default: sumcheck_scales).  Call it outside a
+    scope: it reads the sums and the remainder tests back."""
+    L = _lib.lib()
+    lgs = [_lg(r.k, "the size of a registered arithmetization") for r in regs]
+    k_max = int(max_non_zero_domain_size)
+    _lg(k_max, "max_non_zero_domain_size")
+    scales = sumcheck_scales(lg_r, lg_c, alpha, beta) if scales is None else scales
+    # per member: a | b | f | b f and then a - b f (2 |K|) | quotient | remainder
+    mems = [HipMem(32 * 7 * r.k, device) for r in regs]
+    at = lambda m, off: mems[m].ptr + 32 * off * regs[m].k
+    n = len(regs)
+    plugin.fr_sumcheck_evals_device([r.handle for r in regs], [at(m, 0) for m in range(n)], [at(m, 1) for m in range(n)], [at(m, 2) for m in range(n)],
+                                    alpha, beta, scales)
+    for lg in sorted(set(lgs)):
+        ptrs = [at(m, j) for m in range(n) if lgs[m] == lg for j in range(3)]
+        plugin.NTT_device_batch(lg, ptrs, directions=[1] * len(ptrs), types=[0] * len(ptrs))
+    minus_one = _mont_limbs([1, R_MOD - 1])
+    out = []
+    for m, reg in enumerate(regs):
+        k = reg.k
+        d_a, d_b, d_f, d_h, d_q, d_r = (at(m, j) for j in (0, 1, 2, 3, 5, 6))
+        total = mems[m].download(32, 32 * 2 * k, dtype=np.uint64).reshape(1, 4)
+        plugin.polymul_device(lgs[m] + 1, d_h, polys=[(d_b, k), (d_f, k)])
+        plugin.fr_lincomb_device(d_h, 2 * k, [d_a, d_h], [k, 2 * k], minus_one)
+        _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(d_q, d_r, d_h, 2 * k, k, 1))
+        if int(plugin.fr_support_device(d_r, k)[0]) != 0:
+            raise ValueError("Failed to divide by vanishing polynomial - non-zero remainder")
+        if k != k_max:
+            mult = _mont_limbs([k * pow(k_max, -1, R_MOD) % R_MOD])
+            _lib.check(L.snarkvm_hip_fr_vec_op(4, d_q, d_q, None, None, mult.ctypes.data, k, 1))
+        out.append((total, DevicePoly(d_q, k, mems[m]), DevicePoly(d_f + 32, k - 1, mems[m]), DevicePoly(d_a, k, mems[m]), DevicePoly(d_b, k, mems[m])))
+    return out
+
+
+def h_2(lhs_list, deltas, device=-1):
+    """fifth.rs:50-64: sum_M delta_M lhs_M over the DevicePoly `lhs_list` as ONE `fr_lincomb` -> DevicePoly of max |K_M| coefficients.  deltas:
+    (len(lhs_list), 4) Montgomery limbs on the host."""
+    n = max((p.n for p in lhs_list), default=0)
+    mem = HipMem(32 * max(n, 1), device)
+    plugin.fr_lincomb_device(mem.ptr, n, [p.ptr for p in lhs_list], [p.n for p in lhs_list], deltas)
+    return DevicePoly(mem.ptr, n, mem)

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -137,6 +137,47 @@ def fr_spmv_device(handle, d_y, n_out, d_x, count=1, stride_x=0, stride_y=0):
     written, the tail as zeros.  Member m of a batch reads d_x + m * stride_x elements (stride_x = 0: the one shared x) and writes
     d_y + m * stride_y.  y must not overlap x.  Inside a scope the call is only enqueued."""
     _lib.check(_lib.lib().snarkvm_hip_fr_spmv(_dp(d_y), int(n_out), _dp(handle), _dp(d_x), int(count), int(stride_x), int(stride_y), 1))
+
+
+def _fr_scalar(x, n=1):
+    v = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4)
+    if v.shape[0] != n:
+        raise ValueError("length mismatch")
+    return v
+
+
+def _ptr_list(ptrs, count):
+    if ptrs is None:
+        return None
+    if len(ptrs) != count:
+        raise ValueError("length mismatch")
+    return (ctypes.c_void_p * max(1, count))(*[_dp(p) for p in ptrs])
+
+
+def fr_sumcheck_evals_device(handles, d_a, d_b, d_f, alpha, beta, scales):
+    """Extension (no reference counterpart): the evaluations on K of a, b and f of the Varuna matrix sumcheck (round_functions/fourth.rs:155-245)
+    for `len(handles)` <= 16 arithmetizations registered with `snarkvm_hip_fr_arith_register` (`handles`: their addresses, see
+    matrices.RegisteredArithmetization) into device vectors, in one launch (`snarkvm_hip_fr_matrix_sumcheck_evals`, on_device = 1).  d_a, d_b, d_f:
+    one device pointer per member (k_m elements are written), a None entry or a None list skips that output.  alpha, beta: (4,) Montgomery limbs on
+    the host; scales: (3, 4) = a_scale, b_scale, f_scale.  Inside a scope the call is only enqueued."""
+    k = len(handles)
+    hs = (ctypes.c_void_p * max(1, k))(*[_dp(h) for h in handles])
+    al, be, sc = _fr_scalar(alpha), _fr_scalar(beta), _fr_scalar(scales, 3)
+    _lib.check(_lib.lib().snarkvm_hip_fr_matrix_sumcheck_evals(hs, k, _ptr_list(d_a, k), _ptr_list(d_b, k), _ptr_list(d_f, k), _ptr(al), _ptr(be), _ptr(sc), 1))
+
+
+def fr_sumcheck_evals(handles, sizes, alpha, beta, scales, want="abf"):
+    """The same on host arrays (on_device = 0): -> three lists (a, b, f) of (sizes[m], 4) arrays, None for the outputs not in `want`.  sizes[m]: the k
+    the m-th handle was registered with."""
+    k = len(handles)
+    if len(sizes) != k:
+        raise ValueError("length mismatch")
+    hs = (ctypes.c_void_p * max(1, k))(*[_dp(h) for h in handles])
+    al, be, sc = _fr_scalar(alpha), _fr_scalar(beta), _fr_scalar(scales, 3)
+    outs = {w: [np.zeros((int(n), 4), dtype=np.uint64) for n in sizes] if w in want else None for w in "abf"}
+    lists = [(ctypes.c_void_p * max(1, k))(*[o.ctypes.data if o.size else None for o in outs[w]]) if outs[w] is not None else None for w in "abf"]
+    _lib.check(_lib.lib().snarkvm_hip_fr_matrix_sumcheck_evals(hs, k, lists[0], lists[1], lists[2], _ptr(al), _ptr(be), _ptr(sc), 0))
+    return outs["a"], outs["b"], outs["f"]
 
 
 def msm(points, scalars):

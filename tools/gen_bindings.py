@@ -27,7 +27,7 @@ ABI_PY = os.path.join(ROOT, "snarkvm_amd", "_abi.py")
 SCALARS = {"size_t": "usize", "int": "i32", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "double": "f64", "char": "c_char", "void": "c_void"}
 PY_TAGS = {"size_t": "size", "int": "int", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "double": "f64"}
 ENUMS = ("NTTInputOutputOrder", "NTTDirection", "NTTType")
-OPAQUE = ("snarkvm_hip_bases_t", "snarkvm_hip_bases_g2_t", "snarkvm_hip_fr_matrix_t")
+OPAQUE = ("snarkvm_hip_bases_t", "snarkvm_hip_bases_g2_t", "snarkvm_hip_fr_matrix_t", "snarkvm_hip_fr_arith_t")
 RUST_KEYWORDS = {"type", "in", "ref", "move", "fn", "box", "loop", "match", "mod", "use", "where", "impl", "self", "super", "trait", "yield"}
 
 
