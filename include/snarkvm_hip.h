@@ -629,6 +629,28 @@ RustError snarkvm_hip_devtest_field_ext(int op, const void *in, void *out, size_
  * multi).  digits_bytes must be digit rows * columns * bytes per digit exactly (the planner is snarkvm_hip_selftest_msm_plan), n >= 1. */
 RustError snarkvm_hip_devtest_msm_digits(const void *scalars, size_t n, int window_bits, int tables, int table_bits, int montgomery, int multi,
                                          void *digits, size_t digits_bytes, uint32_t *info);
+/* The tail kernels of a variable-base MSM (csrc/msm.hip.h 6.-7b), unmodified, launched ONCE over caller-chosen partial-sum lists; every output comes
+ * back as an exact projective point (the reference's Projective image: 144 B for G1, 288 B for G2).
+ * arith: 0 = G1 on the exact arithmetic, 1 = G1 on the lazy tail arithmetic, 2 = G2 (hipErrorNotSupported in a build without G2).
+ * stage: 0 = reduce round, 1 = bucket merge, 2 = fold, fold fix, dense bit planes, plane fix, 3 = the bit planes of unfolded windows.
+ * geom[12] = {m, hb, W, nb, S2, L, slot, fold threads, plane threads, hex, quads (bit 0: planes, bit 1: fold), run_fix (G2: launch the fix kernels)};
+ * a stage reads its own members only.  Buckets nbt: stage 0, 1: any (<= 2^17); stage 2: W * 2^(m + hb); stage 3: W * nb.
+ * points: npoints affine points in the Rust layout (G1 104 B, G2 200 B stride), none at infinity.  Entry e is the exact sum of +- points[|t| - 1] over
+ * its terms t = terms[3 e .. 3 e + 2] (0 = none; no term = the point at infinity, an all-zero image), formed with the mixed addition; seeds[e] != 0
+ * replaces it by another representative (l^2 X, l^3 Y, l^2 ZZ, l^3 ZZZ), l derived from the seed.  Entries [0, nentries) are the lists' partial sums,
+ * bucket k owning entries start[k] .. start[k] + cnt[k] - 1 (start holds nbt + 1 values); stage 1: entries [nentries, nentries + nbt * L) are the
+ * initial content of the accumulator.
+ * Every output buffer is filled with 0xff bytes before the launch (the accumulator of stage 1 excepted).  out holds nout points, status and flags
+ * nout words each: status 0 = written, 1 = the device image is still the fill pattern (the point is then meaningless), 2 = (stage 1) the device
+ * image is bit for bit what was put in; flags: the word the fast G2 kernel left for that output (0xffffffff: none written; G1: 0).
+ *   stage 0: nout >= the number T of partial sums the round leaves (the grid covers nout, as the launcher's covers its bound); aux[nbt + 1] receives
+ *            start_out.           stage 1: nout = nbt * L.
+ *   stage 2: nout = W * 2^(m + 1) fold slots, then 2 W (m + 1) planes.      stage 3: nout = W * nbits planes, nbits = log2(nb) + 1.
+ * hipErrorInvalidValue: a null pointer, hb > m, hb > 11, nb > 1024 or not a power of two, threads other than 64 / 128 / 256, quads with 64 threads,
+ * hex or run_fix outside G2, lists that overrun the entries or are not laid out bucket after bucket where a kernel relies on that, a wrong nout. */
+RustError snarkvm_hip_devtest_msm_tail(int arith, int stage, const int32_t *geom, const void *points, size_t npoints, const int32_t *terms,
+                                       const uint64_t *seeds, size_t nentries, const uint32_t *start, const uint32_t *cnt, size_t nbt, void *out,
+                                       uint32_t *status, uint32_t *flags, size_t nout, uint32_t *aux);
 
 #ifdef __cplusplus
 }
