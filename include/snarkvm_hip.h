@@ -383,6 +383,36 @@ RustError snarkvm_hip_fr_mul_by_vanishing(void *out, const void *poly, size_t le
 RustError snarkvm_hip_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs,
                                  int on_device);
 
+/* Selector fold: the sums of Varuna's round 3 (calculate_lineval_sumcheck_witness, snark/varuna/ahp/prover/round_functions/third.rs:126-327) in
+ * one pass.  Member k is a polynomial polys[k] of L_k = lens[k] coefficients, a source domain of n_k = src_sizes[k] elements and a multiplier
+ * mu_k = multipliers[k] (combiner * n_k / N).  apply_randomized_selector (ahp/selectors.rs:100-121) scales the member, divides it by X^n_k - 1,
+ * multiplies the remainder by X^N - 1 and divides by X^n_k - 1 again; the last two steps tile the remainder over N = target_size coefficients
+ * (their own remainder is identically zero when n_k divides N), so summed over the members:
+ *    h_out[i]  = sum_k mu_k sum_{j >= 1, i + j n_k < L_k} polys[k][i + j n_k]     for i < h_len      (h_1)
+ *    xg_out[i] = sum_k mu_k sum_{j >= 0} polys[k][(i mod n_k) + j n_k]            for i < target_size (x g_1; g_1 is xg_out from coefficient 1 on)
+ *    sums[k]   = n_k sum_j polys[k][j n_k]   - NOT scaled by mu_k: the sum of the member over its source domain (third.rs:317), no transform needed.
+ * `polys`, `lens`, `src_sizes` and `multipliers` (count x 32 bytes, Montgomery form) are HOST arrays, read during the call and not retained;
+ * on_device governs h_out, xg_out, sums (count x 32 bytes) and every polys[k].  A member pointer may be NULL iff its length is 0; a member of
+ * length 0 contributes nothing and its sum is 0.  Members may overlap each other and repeat; they are never written.
+ *  - Each of the three outputs may be NULL, which skips it (h_len is ignored when h_out is NULL, target_size when xg_out is NULL); with all three
+ *    NULL a call whose other arguments are valid succeeds and touches nothing.  Of a given output every element is written: all h_len elements of
+ *    h_out (zeros past the longest quotient), all target_size of xg_out, all count of sums.  count == 0 zero-fills h_out and xg_out.
+ *  - Nothing to write (no output given, or only an h_out with h_len == 0): success, no device is needed.
+ *  - Refused with hipErrorInvalidValue before anything is launched and before a device is needed, every output untouched: NULL host arrays with
+ *    count > 0; a NULL member of non-zero length; any n_k == 0; xg_out given and target_size == 0, target_size > 2^28 or an n_k that does not divide
+ *    target_size; h_out given and h_len < max_k (L_k - n_k); h_len or any L_k above 2^29; count > 65535; any overlap of an output with a member or
+ *    with another output; with on_device = 1, pointers on different devices.
+ *  - With on_device = 1 inside a snarkvm_hip_scope the call is only enqueued (sums is device memory like the other outputs: nothing is delivered
+ *    at snarkvm_hip_scope_end).
+ *  - With on_device = 0 outputs and members are staged in one lane buffer: one upload per member, one download per output.
+ *  - Members travel 24 per kernel launch (FR_SELECTOR_CHUNK); a longer list takes further launches that add to the outputs.
+ *  - No atomics and a fixed order of additions per output element; field addition is exact and results canonical, so the bytes depend on neither
+ *    the grid, the split into launches nor the way the members are grouped.
+ *  - Workspace: none with on_device = 1; a repeated call grows nothing (snarkvm_hip_alloc_stats). */
+RustError snarkvm_hip_fr_selector_fold(void *h_out, size_t h_len, void *xg_out, size_t target_size, void *sums, size_t count,
+                                       const void *const *polys, const size_t *lens, const size_t *src_sizes, const void *multipliers,
+                                       int on_device);
+
 /* Reductions: a vector -> a value, in one streaming read (csrc/poly.hip.h: fr_reduce_kernel, fr_support_kernel; a second launch folds the
  * per-workgroup partials - no atomics, and since field addition is exact the 32 bytes do not depend on the shape of the tree).
  * fr_reduce: op SNARKVM_HIP_FR_REDUCE_SUM: *result = sum_i a[i] (`b` is ignored; the sum of a polynomial's evaluations over a domain,
@@ -581,6 +611,11 @@ int snarkvm_hip_selftest_ntt_host(void *inout, uint32_t lg, const int32_t *plan,
  * every launch a loop over i through the kernel's own per-element routine (csrc/poly.hip.h: fr_lincomb_at, Fp::sum_of_products).  0, or -1
  * when the arguments are refused. */
 int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs);
+/* snarkvm_hip_fr_selector_fold over host memory with the CPU in the kernels' place: the same validation, member tables and split into launches,
+ * every launch a loop over i through the kernel's own per-index routine (csrc/poly.hip.h: fr_selector_at), then the tiling of xg_out.  0, or
+ * -1 when the arguments are refused. */
+int snarkvm_hip_selftest_fr_selector_fold(void *h_out, size_t h_len, void *xg_out, size_t target_size, void *sums, size_t count,
+                                          const void *const *polys, const size_t *lens, const size_t *src_sizes, const void *multipliers);
 /* snarkvm_hip_fr_reduce / snarkvm_hip_fr_support over host memory with the CPU in the kernels' place, over a GIVEN launch geometry (blocks >= 1
  * workgroups of threads = 64, 128 or 256): every thread's private accumulation and every combine step through the kernels' own routines
  * (csrc/poly.hip.h: fr_reduce_thread, fr_support_thread, fr_support_combine), the trees level by level over the lanes they exchange between, the

@@ -201,6 +201,24 @@ inline void fr_lincomb(void* out, size_t n_out, const std::vector<DevicePoly>& p
     check(snarkvm_hip_fr_lincomb(out, n_out, pptrs.size(), pptrs.data(), plens.data(), coeffs, on_device ? 1 : 0));
 }
 
+// The sums of Varuna's round 3 in one device pass (snarkvm_hip.h: snarkvm_hip_fr_selector_fold): member k = members[k] with source domain
+// src_sizes[k] and multiplier multipliers[k] (members.size() x 32 bytes of HOST memory, Montgomery form).  h_out (h_len coefficients): the sum of
+// the scaled quotients by X^n_k - 1; xg_out (target_size coefficients): the sum of the scaled remainders, tiled; sums (members.size() elements):
+// the sum of every unscaled member over its source domain.  Each output may be nullptr (skipped); on_device governs the outputs and every
+// members[k].data.  No member is written.  With on_device inside a Scope the call is only enqueued.
+inline void fr_selector_fold(void* h_out, size_t h_len, void* xg_out, size_t target_size, void* sums, const std::vector<DevicePoly>& members,
+                             const std::vector<size_t>& src_sizes, const void* multipliers, bool on_device) {
+    if (src_sizes.size() != members.size()) throw std::invalid_argument("fr_selector_fold: one source domain per member");
+    std::vector<const void*> pptrs;
+    std::vector<size_t> plens;
+    for (auto& p : members) {
+        pptrs.push_back(p.data);
+        plens.push_back(p.len);
+    }
+    check(snarkvm_hip_fr_selector_fold(h_out, h_len, xg_out, target_size, sums, pptrs.size(), pptrs.data(), plens.data(), src_sizes.data(), multipliers,
+                                       on_device ? 1 : 0));
+}
+
 // Reductions in one device pass (snarkvm_hip.h: snarkvm_hip_fr_reduce, snarkvm_hip_fr_support): the sum of a vector, the inner product of two
 // (Evaluations::evaluate_with_coeffs with the Lagrange coefficients left in device memory), and the support of a coefficient vector.  `result`
 // is 32 bytes of HOST memory; with on_device inside a Scope the call is only enqueued and the value arrives when the Scope ends.

@@ -691,6 +691,163 @@ int snarkvm_hip_selftest_fr_lincomb(void* out, size_t n_out, size_t count, const
     return 0;
 }
 
+// ---- selector fold: Varuna round 3 (poly.hip.h: fr_selector_fold_kernel) ---------------------------------------------------
+// What the device call and its host replay share: validation, the member tables and the split into launches.  src[m]: the caller's index
+// of table entry m (its pointers are bound later: to the caller's memory, or to the staged copies).
+static void fr_same_device(lane_t& c, const void* p, const char* what);
+static constexpr size_t FR_SELECTOR_LEN_MAX =(size_t)1 << 29, FR_SELECTOR_TARGET_MAX = (size_t)1 << 28;
+struct fr_selector_launch_t {
+    fr_selector_t t;
+    size_t src[FR_SELECTOR_CHUNK];
+};
+struct fr_selector_plan_t {
+    std::vector<fr_selector_launch_t> launches;
+    bool want_h = false, want_xg = false, want_sums = false;
+    uint32_t h_len = 0, N = 0, span = 0, threads = 0;  // span: the indices of xg the fold itself writes (the tile kernel the rest)
+};
+static fr_t fr_from_u64(uint64_t x) {
+    const fr_t two32 = fr_t::from_u32(65536).sqr();
+    return fr_t::from_u32((uint32_t)(x >> 32)) * two32 + fr_t::from_u32((uint32_t)x);
+}
+static size_t fr_gcd(size_t a, size_t b) {
+    while (b) {
+        const size_t r = a % b;
+        a = b, b = r;
+    }
+    return a;
+}
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  Nothing has been touched either way.  A plan without
+// launches: nothing is wanted.
+static const char* fr_selector_plan(const void* h_out, size_t h_len, const void* xg_out, size_t target_size, const void* sums, size_t count, const void* const* polys,
+                                    const size_t* lens, const size_t* src_sizes, const void* multipliers, fr_selector_plan_t& plan) {
+    if (count > 65535) return "more than 65535 members";
+    if (count && (!polys || !lens || !src_sizes || !multipliers)) return "missing argument";
+    if (h_out && h_len > FR_SELECTOR_LEN_MAX) return "h_len above 2^29";
+    if (xg_out && (target_size == 0 || target_size > FR_SELECTOR_TARGET_MAX)) return "target_size is 0 or above 2^28";
+    size_t need = 0, period = 1;
+    for (size_t k = 0; k < count; k++) {
+        const size_t n = src_sizes[k], L = lens[k];
+        if (!n) return "an empty source domain";
+        if (L > FR_SELECTOR_LEN_MAX) return "a member longer than 2^29";
+        if (L && !polys[k]) return "null member of non-zero length";
+        if (xg_out && target_size % n) return "a source domain does not divide target_size";
+        if (L > n && L - n > need) need = L - n;
+        if (xg_out && L) period = period / fr_gcd(period, n) * n;  // every n_k divides target_size: so does the period
+    }
+    if (h_out && h_len < need) return "h_len is shorter than the longest quotient";
+    {  // no output may overlap an operand or another output; sorted by address, an overlap shows against the furthest end seen so far
+        struct range_t {
+            const uint8_t* p;
+            size_t bytes;
+            bool out;
+        };
+        std::vector<range_t> rs;
+        if (h_out && h_len) rs.push_back({(const uint8_t*)h_out, sizeof(fr_mem_t) * h_len, true});
+        if (xg_out) rs.push_back({(const uint8_t*)xg_out, sizeof(fr_mem_t) * target_size, true});
+        if (sums && count) rs.push_back({(const uint8_t*)sums, sizeof(fr_mem_t) * count, true});
+        for (size_t k = 0; k < count; k++)
+            if (lens[k]) rs.push_back({(const uint8_t*)polys[k], sizeof(fr_mem_t) * lens[k], false});
+        std::sort(rs.begin(), rs.end(), [](const range_t& x, const range_t& y) { return x.p < y.p; });
+        const uint8_t *end_any = nullptr, *end_out = nullptr;
+        for (const range_t& r : rs) {
+            if (r.p < (r.out ? end_any : end_out)) return "an output overlaps an operand or another output";
+            if (r.p + r.bytes > end_any) end_any = r.p + r.bytes;
+            if (r.out && r.p + r.bytes > end_out) end_out = r.p + r.bytes;
+        }
+    }
+    plan.want_h = h_out && h_len, plan.want_xg = xg_out != nullptr, plan.want_sums = sums && count;
+    if (!plan.want_h && !plan.want_xg && !plan.want_sums) return nullptr;
+    plan.h_len = plan.want_h ? (uint32_t)h_len : 0;
+    plan.N = plan.want_xg ? (uint32_t)target_size : 0;
+    plan.span = plan.want_xg ? (FR_SELECTOR_TILE ? (uint32_t)period : plan.N) : 0;
+    plan.threads = plan.h_len > plan.span ? plan.h_len : plan.span;
+    if (!plan.threads) plan.threads = 1;
+    std::vector<size_t> live;  // an empty member contributes nothing: it stays only where its sum (zero) is to be written
+    for (size_t k = 0; k < count; k++)
+        if (lens[k] || plan.want_sums) live.push_back(k);
+    size_t at = 0;
+    do {  // no member at all: one launch that writes the zeros
+        fr_selector_launch_t L{};
+        int m = 0;
+        L.t.accumulate = at != 0;
+        for (; m < FR_SELECTOR_CHUNK && at < live.size(); m++, at++) {
+            const size_t k = live[at];
+            const fr_mem_t mu_mem = fr_mem_from_host((const uint8_t*)multipliers + sizeof(fr_mem_t) * k);
+            const fr_t mu = fr_t::load(&mu_mem).from_mem_mont(), ns = fr_from_u64((uint64_t)src_sizes[k]);
+            L.src[m] = k;
+            L.t.len[m] = (uint32_t)lens[k];
+            L.t.n[m] = src_sizes[k] > ((size_t)1 << 30) ? (1u << 30) : (uint32_t)src_sizes[k];
+            for (int l = 0; l < 9; l++) L.t.mu[m][l] = mu.v[l], L.t.ns[m][l] = ns.v[l];
+        }
+        L.t.count = m;
+        plan.launches.push_back(L);
+    } while (at < live.size());
+    return nullptr;
+}
+// pointers of the tables: member k at polys[k], its sum at sums + k (nullptr: no sums)
+static void fr_selector_bind(fr_selector_plan_t& plan, const fr_mem_t* const* polys, fr_mem_t* sums) {
+    for (fr_selector_launch_t& L : plan.launches)
+        for (int m = 0; m < L.t.count; m++) L.t.p[m] = polys[L.src[m]], L.t.sum[m] = sums ? sums + L.src[m] : nullptr;
+}
+RustError snarkvm_hip_fr_selector_fold(void* h_out, size_t h_len, void* xg_out, size_t target_size, void* sums, size_t count, const void* const* polys,
+                                       const size_t* lens, const size_t* src_sizes, const void* multipliers, int on_device) {
+    fr_selector_plan_t plan;
+    if (const char* why = fr_selector_plan(h_out, h_len, xg_out, target_size, sums, count, polys, lens, src_sizes, multipliers, plan))
+        return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_selector_fold: ") + why);
+    if (plan.launches.empty()) return ok();
+    const void* first = plan.want_h ? h_out : (plan.want_xg ? xg_out : sums);
+    API_BEGIN_DEV(device_for(first, on_device ? 1 : 0))
+    fr_mem_t *dh = plan.want_h ? (fr_mem_t*)h_out : nullptr, *dxg = plan.want_xg ? (fr_mem_t*)xg_out : nullptr, *dsums = plan.want_sums ? (fr_mem_t*)sums : nullptr;
+    std::vector<const fr_mem_t*> members(count, nullptr);
+    if (on_device) {
+        const char* why = "fr_selector_fold: the outputs and members live on different devices";
+        fr_same_device(c, dh, why), fr_same_device(c, dxg, why), fr_same_device(c, dsums, why);
+        for (size_t k = 0; k < count; k++) {
+            if (lens[k]) fr_same_device(c, polys[k], why);
+            members[k] = (const fr_mem_t*)polys[k];
+        }
+    } else {
+        // host operands: one lane buffer holds the outputs and, behind them, every member; one upload each, one download per output
+        size_t total = (size_t)plan.h_len + plan.N + (plan.want_sums ? count : 0);
+        for (size_t k = 0; k < count; k++) total += lens[k];
+        c.poly[0].ensure(sizeof(fr_mem_t) * total);
+        fr_mem_t* next = c.poly[0].as<fr_mem_t>();
+        if (plan.want_h) dh = next, next += plan.h_len;
+        if (plan.want_xg) dxg = next, next += plan.N;
+        if (plan.want_sums) dsums = next, next += count;
+        for (size_t k = 0; k < count; k++) {
+            if (!lens[k]) continue;
+            HIP_TRY(hipMemcpyAsync(next, polys[k], sizeof(fr_mem_t) * lens[k], hipMemcpyHostToDevice, c.stream));
+            members[k] = next;
+            next += lens[k];
+        }
+    }
+    fr_selector_bind(plan, members.data(), dsums);
+    for (const fr_selector_launch_t& L : plan.launches)
+        hipLaunchKernelGGL(fr_selector_fold_kernel, dim3(fr_grid(plan.threads)), dim3(256), 0, c.stream, dh, plan.h_len, dxg, plan.span, plan.threads, L.t);
+    if (plan.span < plan.N) hipLaunchKernelGGL(fr_tile_kernel, dim3(fr_grid(plan.N - plan.span)), dim3(256), 0, c.stream, dxg, plan.span, plan.N);
+    HIP_TRY(hipGetLastError());
+    if (plan.want_h) fr_finish_out(c, dh, h_out, plan.h_len, on_device);
+    if (plan.want_xg) fr_finish_out(c, dxg, xg_out, plan.N, on_device);
+    if (plan.want_sums) fr_finish_out(c, dsums, sums, count, on_device);
+    fr_call_done(c, on_device);
+    API_END
+}
+// The same call on host memory with the CPU in the kernels' place: the same plan, every launch a loop over i through the kernel's own
+// per-index routine, then the tiling.  0, or -1 when the plan refuses the arguments.
+int snarkvm_hip_selftest_fr_selector_fold(void* h_out, size_t h_len, void* xg_out, size_t target_size, void* sums, size_t count, const void* const* polys,
+                                          const size_t* lens, const size_t* src_sizes, const void* multipliers) {
+    fr_selector_plan_t plan;
+    if (fr_selector_plan(h_out, h_len, xg_out, target_size, sums, count, polys, lens, src_sizes, multipliers, plan)) return -1;
+    if (plan.launches.empty()) return 0;
+    fr_mem_t *h = plan.want_h ? (fr_mem_t*)h_out : nullptr, *xg = plan.want_xg ? (fr_mem_t*)xg_out : nullptr;
+    fr_selector_bind(plan, (const fr_mem_t* const*)polys, plan.want_sums ? (fr_mem_t*)sums : nullptr);
+    for (const fr_selector_launch_t& L : plan.launches)
+        for (uint32_t i = 0; i < plan.threads; i++) fr_selector_at(L.t, h, plan.h_len, xg, plan.span, i);
+    for (uint32_t i = plan.span; i < plan.N; i++) fr_tile_at(xg, plan.span, i);
+    return 0;
+}
+
 // ---- reductions (poly.hip.h: fr_reduce_kernel, fr_support_kernel) ---------------------------------------------------------------
 // nullptr, or why the call is refused (hipErrorInvalidValue); needs no device
 static const char* fr_reduce_check(int op, const void* result, const void* a, const void* b, size_t n) {

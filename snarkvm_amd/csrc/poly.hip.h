@@ -9,6 +9,8 @@
 //   fr_distribute_powers_kernel v_i <- v_i * c * g^i                             fft/domain.rs:224-254
 //   fr_fold_vanishing_kernel    quotient / remainder by X^D - 1                  dense.rs:161-169 (divide_by_vanishing_poly)
 //   fr_mul_vanishing_kernel     p * (X^D - 1)                                    dense.rs:153-159
+//   fr_selector_fold_kernel     sum_k mu_k (quotient, tiled remainder) of p_k by X^n_k - 1, and the sums over the n_k-th roots
+//                                                                                 third.rs:126-327, selectors.rs:100-121 (round 3)
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
 //   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
 //   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
@@ -352,6 +354,124 @@ static __global__ void fr_mul_vanishing_kernel(const fr_mem_t* __restrict__ a, s
     const fr_t hi = (i >= D) ? fr_t::load(&a[i - D]) : fr_t::zero();
     const fr_t lo = (i < len) ? fr_t::load(&a[i]) : fr_t::zero();
     (hi - lo).store(&out[i]);
+}
+
+// ---- selector fold: Varuna round 3 -----------------------------------------------------------------------------------
+// apply_randomized_selector (ahp/selectors.rs:100-121) per (instance, matrix) member k of the lineval sumcheck (third.rs:280-327): scale the
+// product p_k by mu_k = combiner * n_k / N, divide by X^n_k - 1 (quotient -> h_1, remainder = x g), multiply x g by X^N - 1 and divide by
+// X^n_k - 1 again.  The last two steps are a TILING - the quotient of xg (X^N - 1) by X^n - 1 is q[i] = xg[i mod n] for i < N and the
+// remainder is identically zero when n | N - and the scaling commutes with the class sums, so the whole sequence, summed over the members, is
+//   h[i]  = sum_k mu_k sum_{j >= 1, i + j n_k < L_k} p_k[i + j n_k]        i < h_len
+//   xg[i] = sum_k mu_k sum_{j >= 0} p_k[(i mod n_k) + j n_k]               i < N
+//   sums[k] = n_k sum_j p_k[j n_k]    (= sum of p_k over the n_k-th roots of unity, third.rs:317: no transform needed)
+// ONE streaming pass where the reference's sequence is seven launches per member.  One thread per output index walks each member's residue
+// class from the top, as fr_fold_vanishing_kernel does: the running sum when the walk passes i is the h term, at the bottom the class sum;
+// the thread that owns index 0 has walked class 0 of every member and writes sums.  The member table travels BY KERNEL ARGUMENT like
+// fr_lincomb_t (nothing staged, nothing retained: an enqueue-only call has no later moment to release a table); multipliers and the n_k
+// arrive in the TRUE internal form, the vectors are streamed raw, so every product is a raw memory-form value.  Members go FR_SELECTOR_G at
+// a time through Fp::sum_of_products (class sums are canonical, the multipliers are the first factor).  A list longer than
+// FR_SELECTOR_CHUNK takes further launches with `accumulate` set: those add to what the outputs hold.
+// Class sums and N > n: xg has the period P = lcm_k n_k, which divides N.  With FR_SELECTOR_TILE the fold runs over i < P only and
+// fr_tile_kernel copies xg[i mod P] to the rest - every class sum is formed once; without, every i < N recomputes its class sum (reads that
+// hit L2, redundant by N / n_k).  Both, and the group sizes, give the same bytes: field addition is exact and results canonical, there are
+// no atomics, and a thread's order of additions depends on neither the grid nor the split.  tools/bench_fr_selector.py times the variants
+// (-DFR_SELECTOR_G=1|2|3|6, -DFR_SELECTOR_TILE=0|1); what has been measured is in profiles/fr_selector.md.
+// Indices are 32-bit: lengths <= 2^29, N <= 2^28, and an n_k above 2^30 behaves like 2^30 for every index that exists (the host clamps it;
+// ns keeps the true value).  Registers (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): fr_selector_fold_kernel 159 VGPRs, 106 SGPRs, no
+// scratch, 3 waves per SIMD at G = 6 (G = 3: 104 VGPRs, 100 SGPRs, no scratch, 4 waves; G = 1: 68 VGPRs); fr_tile_kernel 20 VGPRs, 25 SGPRs, no
+// scratch.  No call (tools/device_calls.sh).
+#ifndef FR_SELECTOR_G
+#define FR_SELECTOR_G 6  // members per Montgomery reduction: measured against 1 and 3 (profiles/fr_selector.md)
+#endif
+#ifndef FR_SELECTOR_TILE
+#define FR_SELECTOR_TILE 1  // 1: class sums once, then tiled; 0: every index recomputes its class sum (about 3x slower at N = 4 n with 24 members of 2^21)
+#endif
+static_assert(FR_SELECTOR_G >= 1 && FR_SELECTOR_G <= 6, "Fp::sum_of_products takes at most 6 terms");
+static constexpr int FR_SELECTOR_CHUNK = 24;  // members per launch: 24 x (8 + 8 + 4 + 4 + 36 + 36) B + 8 = 2312 B of the 4 KB of kernel arguments
+struct fr_selector_t {
+    const fr_mem_t* p[FR_SELECTOR_CHUNK];
+    fr_mem_t* sum[FR_SELECTOR_CHUNK];     // where sums[k] goes; nullptr: not wanted
+    uint32_t len[FR_SELECTOR_CHUNK];      // L_k
+    uint32_t n[FR_SELECTOR_CHUNK];        // min(n_k, 2^30)
+    uint32_t mu[FR_SELECTOR_CHUNK][9];    // limbs of mu_k, true internal form
+    uint32_t ns[FR_SELECTOR_CHUNK][9];    // limbs of n_k as a field element, true internal form
+    int count;
+    int accumulate;  // the outputs already hold the sum over earlier members
+};
+SV_HD uint32_t fr_selector_mod(uint32_t x, uint32_t n) { return (n & (n - 1)) ? x % n : x & (n - 1); }
+// member (p, L, n) at index i: hs = sum_{j >= 1, i + j n < L} p[i + j n]; with want_class also cs = sum_{j >= 0} p[(i mod n) + j n]
+SV_HD void fr_selector_walk(const fr_mem_t* p, uint32_t L, uint32_t n, uint32_t i, bool want_class, fr_t& hs, fr_t& cs) {
+    hs = fr_t::zero(), cs = fr_t::zero();
+    const uint32_t lo = want_class ? fr_selector_mod(i, n) : i;
+    if (lo >= L) return;
+    fr_t acc = fr_t::zero();
+    uint32_t j = (L - 1) - fr_selector_mod(L - 1 - lo, n);  // the top of the class: j = lo mod n, so j > x >= lo implies j - n >= x
+    for (; j > i; j -= n) acc = acc + fr_t::load(&p[j]);
+    hs = acc;
+    if (!want_class) return;
+    for (; j > lo; j -= n) acc = acc + fr_t::load(&p[j]);
+    cs = acc + fr_t::load(&p[lo]);
+}
+// members k0 + g .. k0 + G - 1 of a group, by recursion: a loop that holds the walks is not always unrolled, and an array indexed by a
+// loop counter that survives lives in scratch
+template <int G, int g>
+SV_HD void fr_selector_members(const fr_selector_t& t, int k0, uint32_t i, bool want_xg, fr_t* mu, fr_t* hs, fr_t* cs) {
+    if constexpr (g < G) {
+        const int k = k0 + g;
+        mu[g] = fr_t::from_table(t.mu[k]);
+        const bool want_sum = i == 0 && t.sum[k];
+        fr_selector_walk(t.p[k], t.len[k], t.n[k], i, want_xg || want_sum, hs[g], cs[g]);
+        if (want_sum) (fr_t::from_table(t.ns[k]) * cs[g]).store(t.sum[k]);
+        fr_selector_members<G, g + 1>(t, k0, i, want_xg, mu, hs, cs);
+    }
+}
+template <int G>
+SV_HD void fr_selector_group(const fr_selector_t& t, int k0, uint32_t i, bool want_h, bool want_xg, fr_t& h, fr_t& xg) {
+    fr_t mu[G], hs[G], cs[G];
+    fr_selector_members<G, 0>(t, k0, i, want_xg, mu, hs, cs);
+    if (want_h) h = h + fr_t::sum_of_products<G>(mu, hs);
+    if (want_xg) xg = xg + fr_t::sum_of_products<G>(mu, cs);
+}
+// the per-index routine: the kernel below and the host replay (snarkvm_hip_selftest_fr_selector_fold) both call it.  h_out / xg_out may be
+// nullptr (skipped); xg is written for i < span.
+SV_HD void fr_selector_at(const fr_selector_t& t, fr_mem_t* h_out, uint32_t h_len, fr_mem_t* xg_out, uint32_t span, uint32_t i) {
+    const bool want_h = h_out && i < h_len, want_xg = xg_out && i < span;
+    fr_t h = fr_t::zero(), xg = fr_t::zero();
+    if (t.accumulate) {
+        if (want_h) h = fr_t::load(&h_out[i]);
+        if (want_xg) xg = fr_t::load(&xg_out[i]);
+    }
+    // Whole groups, then what is left in groups of 3, 2 or 1: four instantiations at most.  Every use of the table in an instantiation counts
+    // towards the limit up to which the compiler reads a by-value kernel argument in place (more, and it copies the table to scratch).
+    constexpr int S = FR_SELECTOR_G > 3 ? 3 : FR_SELECTOR_G;
+    int step;
+#pragma unroll 1
+    for (int k0 = 0; k0 < t.count; k0 += step) {
+        const int left = t.count - k0;
+        if (left >= FR_SELECTOR_G)
+            fr_selector_group<FR_SELECTOR_G>(t, k0, i, want_h, want_xg, h, xg), step = FR_SELECTOR_G;
+        else if (left >= 3)
+            fr_selector_group<S>(t, k0, i, want_h, want_xg, h, xg), step = S;
+        else if (left == 2)
+            fr_selector_group<(S >= 2 ? 2 : 1)>(t, k0, i, want_h, want_xg, h, xg), step = S >= 2 ? 2 : 1;
+        else
+            fr_selector_group<1>(t, k0, i, want_h, want_xg, h, xg), step = 1;
+    }
+    if (want_h) h.store(&h_out[i]);
+    if (want_xg) xg.store(&xg_out[i]);
+}
+// threads = max(h_len if h_out, span if xg_out, 1): index 0 always has an owner (the sums)
+static __global__ void __launch_bounds__(256) fr_selector_fold_kernel(fr_mem_t* h_out, uint32_t h_len, fr_mem_t* xg_out, uint32_t span, uint32_t threads, fr_selector_t t) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < threads; i += st) fr_selector_at(t, h_out, h_len, xg_out, span, (uint32_t)i);
+}
+// v[i] = v[i mod period] for period <= i < n: reads [0, period), writes the rest
+SV_HD void fr_tile_at(fr_mem_t* v, uint32_t period, uint32_t i) { v[i] = v[fr_selector_mod(i, period)]; }
+static __global__ void fr_tile_kernel(fr_mem_t* v, uint32_t period, uint32_t n) {
+    size_t i = period + blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < n; i += st) fr_tile_at(v, period, (uint32_t)i);
 }
 
 // ---- reductions: a vector -> a value ----------------------------------------------------------------------------------------

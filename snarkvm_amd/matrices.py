@@ -8,9 +8,17 @@ algorithms/src/snark/varuna/ahp/matrices.rs) registered once in device memory an
 The transpose is circuit data like the matrix itself: built once on the host (`transpose`) and registered; the product is
 `snarkvm_hip_fr_spmv` (include/snarkvm_hip.h).  The arithmetization (row, col, row_col_val on K) is circuit data too: built once on the host
 (`matrix_evals`), registered (`RegisteredArithmetization`), and turned into the round-4 witness of every proof by one fused kernel
-(`snarkvm_hip_fr_matrix_sumcheck_evals`) followed by entry points that already exist (`matrix_sumcheck_witness`).  Nothing here builds a
-circuit index or drives a prover round.
+(`snarkvm_hip_fr_matrix_sumcheck_evals`) followed by entry points that already exist (`matrix_sumcheck_witness`).
+
+    z = w (X^|X| - 1) + x                   round_functions/third.rs:220-249 (`assignment_device`)
+    h_1, x g_1, g_1 and the MatrixSums      third.rs:126-218, 280-327 with ahp/selectors.rs:100-121 (`lineval_sumcheck_witness`)
+
+Round 3 is driven here from the registered transposes to its two oracles: the sparse products, the transforms and the per-member products
+are entry points that already exist, and the selector of every (instance, matrix) member, the running h_1 / x g_1 sums, the mask polynomial
+and the sums over the variable domain are ONE pass (`snarkvm_hip_fr_selector_fold`).  Nothing here builds a circuit index; rounds 1 and 2
+have no driver function.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -318,3 +326,91 @@ def h_2(lhs_list, deltas, device=-1):
     mem = HipMem(32 * max(n, 1), device)
     plugin.fr_lincomb_device(mem.ptr, n, [p.ptr for p in lhs_list], [p.n for p in lhs_list], deltas)
     return DevicePoly(mem.ptr, n, mem)
+
+
+# ---- round 3: the lineval sumcheck -------------------------------------------------------------------------------------------------------------
+def assignment_device(d_w, w_len, d_x, input_size, d_out):
+    """`calculate_assignments` (third.rs:236-239) for one instance on device memory: d_out (w_len + input_size coefficients, the caller's) =
+    w (X^input_size - 1) + x, with w of w_len coefficients at d_w and x of input_size coefficients at d_x - `fr_mul_by_vanishing`, then x added
+    in place by one `fr_lincomb`.  d_out must overlap neither operand.  -> the number of coefficients written.  Inside a scope both calls are
+    only enqueued."""
+    n = int(w_len) + int(input_size)
+    out = _dev_ptr(d_out)
+    _lib.check(_lib.lib().snarkvm_hip_fr_mul_by_vanishing(out, _dev_ptr(d_w) or None, int(w_len), int(input_size), 1))
+    plugin.fr_lincomb_device(out, n, [out, _dev_ptr(d_x)], [n, int(input_size)], _mont_limbs([1, 1]))
+    return n
+
+
+LinevalCircuit = collections.namedtuple("LinevalCircuit", "transposes lg_r lg_c circuit_combiner instance_combiners assignments")
+LinevalCircuit.__doc__ = """One circuit of round 3: `transposes` = the RegisteredMatrix of the transposes of A, B, C (`transpose`, 2^lg_c rows each), the
+constraint domain 2^lg_r and the variable domain 2^lg_c, `circuit_combiner` ((4,) Montgomery limbs), `instance_combiners` ((instances, 4)) and
+`assignments`: one DevicePoly z per instance (`assignment_device`)."""
+
+
+def lineval_sumcheck_witness(circuits, alpha, eta_b, eta_c, lg_max_variable_domain, mask=None, device=-1):
+    """`calculate_lineval_sumcheck_witness` (third.rs:126-218) over the LinevalCircuit list `circuits`, on device memory.  Per circuit, once (the
+    reference repeats it per instance, but it does not depend on the instance): l_alpha and M(alpha, .) = M^T l_alpha for the three registered
+    transposes, one inverse transform batch at |C|.  Then the M(alpha, X) and every assignment go zero-padded to the product domain (the
+    smallest power of two >= |C| + len(z) - 1) through ONE forward transform batch - an assignment is transformed once, not once per matrix -
+    and every (instance, matrix) product is one `polymul_device` over two evaluation vectors.  All 3 I members, and the mask polynomial
+    (third.rs:207-213: a further member with n = N and multiplier one), end in ONE `snarkvm_hip_fr_selector_fold`.
+    alpha, eta_b, eta_c: (4,) Montgomery limbs; mask: a DevicePoly or None (non-hiding mode).
+    -> (h_1, xg_1, g_1, sums): DevicePoly h_1 (untrimmed: the longest quotient, at least one coefficient), xg_1 (N = 2^lg_max_variable_domain
+    coefficients) and g_1 = xg_1 from coefficient 1 on (a pointer offset: ready for a resident commitment); sums: per circuit an
+    (instances, 3, 4) host array in the MatrixSums order sum_a, sum_b, sum_c.  Call it outside a scope: it reads the sums back."""
+    L = _lib.lib()
+    N = 1 << int(lg_max_variable_domain)
+    n_inv = pow(N, -1, R_MOD)
+    matrix_combiners = [1, _from_mont(eta_b)[0], _from_mont(eta_c)[0]]
+    tau = np.ascontiguousarray(alpha, dtype=np.uint64).reshape(1, 4)
+    keep, ptrs, lens, srcs, mus = [], [], [], [], []
+    for c in circuits:
+        size_c = 1 << c.lg_c
+        if size_c > N or any(t.rows != size_c for t in c.transposes) or len(c.transposes) != 3:
+            raise ValueError("lineval_sumcheck_witness: three transposes of |C| rows each, |C| <= the maximal variable domain")
+        inst = _from_mont(c.instance_combiners)
+        if len(inst) != len(c.assignments):
+            raise ValueError("lineval_sumcheck_witness: one instance combiner per assignment")
+        z_max = max((z.n for z in c.assignments), default=0)
+        if not c.assignments or z_max == 0:
+            continue
+        lg_p = max(size_c + z_max - 2, 0).bit_length()
+        P = 1 << lg_p
+        # m_A | m_B | m_C | one padded copy per assignment | one product per (instance, matrix); l_alpha apart
+        mem = HipMem(32 * P * (3 + 4 * len(c.assignments)), device)
+        lag = HipMem(32 << c.lg_r, device)
+        at = lambda j: mem.ptr + 32 * P * j
+        mem.fill(0, 0, 32 * P * (3 + len(c.assignments)))
+        _lib.check(L.snarkvm_hip_fr_lagrange_coefficients(lag.ptr, c.lg_r, tau.ctypes.data, 1))
+        for m, t in enumerate(c.transposes):
+            if t.cols > (1 << c.lg_r):
+                raise ValueError("lineval_sumcheck_witness: a matrix has more constraints than the constraint domain has elements")
+            t.mul_device(at(m), size_c, lag.ptr)
+        plugin.NTT_device_batch(c.lg_c, [at(m) for m in range(3)], directions=[1] * 3, types=[0] * 3)
+        for i, z in enumerate(c.assignments):
+            mem.copy_from(32 * P * (3 + i), z.ptr, 32 * z.n)
+        nv = 3 + len(c.assignments)
+        plugin.NTT_device_batch(lg_p, [at(j) for j in range(nv)], directions=[0] * nv, types=[0] * nv)
+        cc = _from_mont(c.circuit_combiner)[0]
+        for i, z in enumerate(c.assignments):
+            for m in range(3):
+                d_prod = at(nv + 3 * i + m)
+                plugin.polymul_device(lg_p, d_prod, evals=[at(m), at(3 + i)])
+                ptrs.append(d_prod), lens.append(size_c + z.n - 1), srcs.append(size_c)
+                mus.append(cc * inst[i] % R_MOD * matrix_combiners[m] % R_MOD * size_c % R_MOD * n_inv % R_MOD)
+        keep += [mem, lag]
+    members = len(ptrs)
+    if mask is not None and mask.n:
+        ptrs.append(mask.ptr), lens.append(mask.n), srcs.append(N), mus.append(1)
+    h_len = max([max(l - s, 0) for l, s in zip(lens, srcs)] + [1])
+    out = HipMem(32 * (h_len + N + max(len(ptrs), 1)), device)
+    d_h, d_xg, d_sums = out.ptr, out.ptr + 32 * h_len, out.ptr + 32 * (h_len + N)
+    plugin.fr_selector_fold_device(d_h, h_len, d_xg, N, d_sums if ptrs else None, ptrs, lens, srcs, _mont_limbs(mus))
+    flat = out.download(32 * members, 32 * (h_len + N), dtype=np.uint64).reshape(-1, 3, 4)
+    sums, first = [], 0
+    for c in circuits:
+        count = len(c.assignments) if any(z.n for z in c.assignments) else 0
+        sums.append(flat[first : first + count].copy() if count else np.zeros((len(c.assignments), 3, 4), dtype=np.uint64))
+        first += count
+    del keep
+    return DevicePoly(d_h, h_len, out), DevicePoly(d_xg, N, out), DevicePoly(d_xg + 32, N - 1, out), sums

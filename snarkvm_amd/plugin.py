@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -88,6 +88,30 @@ def fr_lincomb_device(d_out, n_out, d_polys, lens, coeffs):
     pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
     pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
     _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(int(d_out) if d_out else None, int(n_out), k, pp, pl, _ptr(cs), 1))
+
+
+FR_SELECTOR_CHUNK = 24  # members per kernel launch of snarkvm_hip_fr_selector_fold (include/snarkvm_hip.h; csrc/poly.hip.h FR_SELECTOR_CHUNK)
+
+
+def fr_selector_fold_device(d_h, h_len, d_xg, target_size, d_sums, d_polys, lens, src_sizes, multipliers):
+    """Extension (no reference counterpart): the sums of Varuna's round 3 over members that live in device memory (`snarkvm_hip_fr_selector_fold`,
+    on_device = 1; third.rs:280-327 with apply_randomized_selector, selectors.rs:100-121).  Member k = d_polys[k] (lens[k] coefficients) with source
+    domain src_sizes[k] and multiplier multipliers[k] ((k, 4) Montgomery limbs on the host):
+        d_h[i]  = sum_k mu_k sum_{j >= 1} p_k[i + j n_k]            i < h_len
+        d_xg[i] = sum_k mu_k sum_{j >= 0} p_k[(i mod n_k) + j n_k]  i < target_size
+        d_sums[k] = n_k sum_j p_k[j n_k]                             (len(d_polys) elements of device memory, not scaled by mu_k)
+    Each of d_h, d_xg and d_sums may be None (skipped).  No member is written.  Inside a scope the call is only enqueued."""
+    k = len(d_polys)
+    if len(lens) != k or len(src_sizes) != k:
+        raise ValueError("length mismatch")
+    mu = np.ascontiguousarray(multipliers, dtype=np.uint64).reshape(-1, 4) if k else np.zeros((0, 4), dtype=np.uint64)
+    if mu.shape[0] != k:
+        raise ValueError("length mismatch")
+    pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
+    pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
+    ps = (ctypes.c_size_t * max(1, k))(*[int(n) for n in src_sizes])
+    _lib.check(_lib.lib().snarkvm_hip_fr_selector_fold(int(d_h) if d_h else None, int(h_len), int(d_xg) if d_xg else None, int(target_size),
+                                                       int(d_sums) if d_sums else None, k, pp, pl, ps, _ptr(mu), 1))
 
 
 FR_REDUCE_SUM, FR_REDUCE_DOT = 0, 1  # include/snarkvm_hip.h: SNARKVM_HIP_FR_REDUCE_*

@@ -5,6 +5,7 @@ Host mirror of the reference functions the Varuna prover runs between its NTTs a
     DensePolynomial::{evaluate, mul_by_vanishing_poly, divide_by_vanishing_poly}   fft/polynomial/dense.rs:98-114, 153-169
     `polynomial / (X - point)` (Polynomial::divide_with_q_and_r)                    fft/polynomial/mod.rs:222-256
     `poly += (coeff, cur_poly)` over the terms of a linear combination              polycommit/sonic_pc/mod.rs:413-473, 548-564
+    apply_randomized_selector summed over the members of round 3 (`selector_fold`)  ahp/selectors.rs:100-121, round_functions/third.rs:179-213
     Evaluations::evaluate_with_coeffs (an inner product), sums over a domain        fft/evaluations.rs:90-92, round_functions/first.rs:119
     DensePolynomial::{degree, is_zero}, skip_leading_zeros_and_convert_to_bigints   fft/polynomial/dense.rs:66-96, kzg10/mod.rs:455-467
     batch_inversion / batch_inversion_and_mul                                       fields/src/lib.rs:66-129
@@ -67,6 +68,30 @@ def lincomb(coeffs, polys):
     lens = (ctypes.c_size_t * max(1, k))(*[p.shape[0] for p in polys])
     _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(_p(out), n, k, ptrs, lens, _p(cs), 0))
     return trim(out)
+
+
+def selector_fold(polys, src_sizes, multipliers, target_size, h_len=None, want="hxs"):
+    """The sums of Varuna's round 3 over host arrays in ONE device pass (`snarkvm_hip_fr_selector_fold`): per member k the reference scales
+    polys[k] by multipliers[k], divides by X^n_k - 1 (n_k = src_sizes[k]), multiplies the remainder by X^target_size - 1 and divides by X^n_k - 1
+    again (apply_randomized_selector, selectors.rs:100-121), adds the quotients into h_1 and the tiled remainders into x g_1 (third.rs:179-213) and
+    takes the sum of the unscaled member over its source domain (third.rs:317).  -> (h, xg, sums): h of h_len coefficients (default: the longest
+    quotient), xg of target_size, sums (len(polys), 4); None for the outputs whose letter is not in `want` ("h", "x", "s").  Untrimmed."""
+    polys = [_v(p) for p in polys]
+    k = len(polys)
+    mu = _v(multipliers) if k else np.zeros((0, 4), dtype=np.uint64)
+    if mu.shape[0] != k or len(src_sizes) != k:
+        raise ValueError("length mismatch")
+    if h_len is None:
+        h_len = max([max(p.shape[0] - int(n), 0) for p, n in zip(polys, src_sizes)] + [0])
+    h = np.empty((int(h_len), 4), dtype=np.uint64) if "h" in want else None
+    xg = np.empty((int(target_size), 4), dtype=np.uint64) if "x" in want else None
+    sums = np.empty((k, 4), dtype=np.uint64) if "s" in want else None
+    ptrs = (ctypes.c_void_p * max(1, k))(*[p.ctypes.data if p.shape[0] else None for p in polys])
+    lens = (ctypes.c_size_t * max(1, k))(*[p.shape[0] for p in polys])
+    srcs = (ctypes.c_size_t * max(1, k))(*[int(n) for n in src_sizes])
+    nz = lambda a: a.ctypes.data if a is not None and a.size else None
+    _lib.check(_lib.lib().snarkvm_hip_fr_selector_fold(nz(h), int(h_len), nz(xg), int(target_size), nz(sums), k, ptrs, lens, srcs, _p(mu), 0))
+    return h, xg, sums
 
 
 def inner_product(a, b):
