@@ -172,7 +172,7 @@ RustError snarkvm_hip_polymul_device(void *d_out, size_t pcount, const void *con
  * - snarkvm_hip_ntt_device, _ntt_device_batch, _polymul_device, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
  * kernels (snarkvm_hip_fr_lincomb and snarkvm_hip_fr_spmv among them) with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
  * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end, and so are the host results of
- * snarkvm_hip_fr_reduce[_strided] and snarkvm_hip_fr_support[_strided] over device operands (the same mechanism: parked in pinned memory, copied
+ * snarkvm_hip_fr_reduce[_strided], snarkvm_hip_fr_support[_strided] and the counts of snarkvm_hip_fr_rowcheck_fold over device operands (the same mechanism: parked in pinned memory, copied
  * to the caller's buffer when the scope is flushed - the buffer must stay valid until then).  Every other call (MSMs,
  * host buffers, a pointer on another GPU) first waits for the scope's queued work, so results are the same as without a scope - and
  * then runs on the scope's own stream: a thread inside a scope never waits for a free stream.  Scopes do not nest; a scope must be
@@ -413,6 +413,51 @@ RustError snarkvm_hip_fr_selector_fold(void *h_out, size_t h_len, void *xg_out, 
                                        const void *const *polys, const size_t *lens, const size_t *src_sizes, const void *multipliers,
                                        int on_device);
 
+/* Witness evaluations: the gather of Varuna's round 1 (calculate_w, snark/varuna/ahp/prover/round_functions/first.rs:127-161) between the forward
+ * transform of x_poly and the inverse transform that yields w (X^|X| - 1).  With ratio = n / input_size, for k < n:
+ *    out[k] = 0                                      when ratio divides k (the input subgroup)
+ *    out[k] = w[k - k / ratio - 1] - x_evals[k]      otherwise; w counts as zero from w_len on.
+ * on_device governs out, w and x_evals.  All n elements of out are written.  out may coincide EXACTLY with x_evals (in place on the transform of
+ * x_poly: a thread reads x_evals[k] before it writes out[k]); w is never written.
+ *  - n == 0 (with a valid input_size): success, nothing is touched and no device is needed.
+ *  - Refused with hipErrorInvalidValue before anything is launched and before a device is needed, out untouched: input_size == 0; input_size does
+ *    not divide n; n > 2^28; w_len > n - input_size; out or x_evals NULL with n > 0; w NULL with w_len > 0; out overlapping x_evals other than
+ *    exactly, or overlapping w; with on_device = 1, operands on different devices.
+ *  - With on_device = 1 inside a snarkvm_hip_scope the call is only enqueued.
+ *  - With on_device = 0 w, x_evals and out are staged in lane buffers: two uploads, one download.
+ *  - Workspace: none with on_device = 1. */
+RustError snarkvm_hip_fr_witness_evals(void *out, size_t n, const void *w, size_t w_len, const void *x_evals, size_t input_size, int on_device);
+
+/* Rowcheck fold: the sums of Varuna's round 2 (calculate_rowcheck_witness, round_functions/second.rs:76-142, with apply_randomized_selector
+ * without a remainder witness, ahp/selectors.rs:88-99) over `count` members (one per instance of every circuit of one domain size) of three
+ * n-element vectors a[k], b[k], c[k] and a multiplier mu_k = multipliers[k]:
+ *    out[i]        = sum_k mu_k (a[k][i] b[k][i] - c[k][i])           for i < n
+ *    violations[k] = #{ i < n : a[k][i] b[k][i] != c[k][i] }           for k < count
+ * Over the evaluations on R the counts are the divisibility test of the round (the remainder by v_R is zero iff every count is); over the
+ * evaluations on a coset g R, with mu_k = combiner * |R| / |R_max| / (g^|R| - 1), out holds the coset evaluations of h_0's share of this domain
+ * size: one inverse coset transform yields the coefficients.
+ * `a`, `b`, `c` (count pointers each), `multipliers` (count x 32 bytes, Montgomery form) and `violations` (count values) are HOST arrays; the
+ * first four are read during the call and not retained.  on_device governs out and every a[k], b[k], c[k].  Members may overlap each other and
+ * repeat; they are never written.
+ *  - Either output may be NULL, which skips it: out NULL is the check alone (multipliers is then ignored and may be NULL), violations NULL the fold
+ *    alone; with both NULL a call whose other arguments are valid succeeds and touches nothing.  Of a given output every element is written: all n
+ *    of out, all count of violations.  count == 0 zero-fills out.
+ *  - n == 0: success, violations is zero-filled, no device is needed.
+ *  - Refused with hipErrorInvalidValue before anything is launched and before a device is needed, both outputs untouched: n > 2^28; count > 65535;
+ *    a, b or c NULL with count > 0; multipliers NULL with count > 0 and out given; a NULL member pointer with n > 0; any overlap of out with a
+ *    member; with on_device = 1, pointers on different devices.
+ *  - With on_device = 1 inside a snarkvm_hip_scope the call is only enqueued: out is device memory, violations is delivered by
+ *    snarkvm_hip_scope_end (keep it alive until then), like the result of snarkvm_hip_fr_support.
+ *  - With on_device = 0 out and the members are staged in one lane buffer: one upload per member vector, one download.
+ *  - Members travel 24 per kernel launch (FR_ROWCHECK_CHUNK); a longer list takes further launches: the first writes out, the later ones add to it.
+ *  - The Fr output uses no atomics and a fixed order of additions per element; field addition is exact and results canonical, so the bytes depend
+ *    on neither the grid, the split into launches nor the way the members are grouped.  The counts are integer sums (one 64-bit integer atomic per
+ *    wave that saw a violation): exact whatever the order.
+ *  - Workspace: with violations given, count x 8 bytes of the lane's scratch, kept for the next call; a repeated call grows nothing
+ *    (snarkvm_hip_alloc_stats). */
+RustError snarkvm_hip_fr_rowcheck_fold(void *out, uint64_t *violations, size_t n, size_t count, const void *const *a, const void *const *b,
+                                       const void *const *c, const void *multipliers, int on_device);
+
 /* Reductions: a vector -> a value, in one streaming read (csrc/poly.hip.h: fr_reduce_kernel, fr_support_kernel; a second launch folds the
  * per-workgroup partials - no atomics, and since field addition is exact the 32 bytes do not depend on the shape of the tree).
  * fr_reduce: op SNARKVM_HIP_FR_REDUCE_SUM: *result = sum_i a[i] (`b` is ignored; the sum of a polynomial's evaluations over a domain,
@@ -616,6 +661,16 @@ int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const
  * -1 when the arguments are refused. */
 int snarkvm_hip_selftest_fr_selector_fold(void *h_out, size_t h_len, void *xg_out, size_t target_size, void *sums, size_t count,
                                           const void *const *polys, const size_t *lens, const size_t *src_sizes, const void *multipliers);
+/* snarkvm_hip_fr_witness_evals over host memory with the CPU in the kernel's place: the same validation, then a loop over k through the kernel's
+ * own per-index routine (csrc/poly.hip.h: fr_witness_at).  0, or -1 when the arguments are refused. */
+int snarkvm_hip_selftest_fr_witness_evals(void *out, size_t n, const void *w, size_t w_len, const void *x_evals, size_t input_size);
+/* snarkvm_hip_fr_rowcheck_fold over host memory with the CPU in the kernel's place: the same validation, member tables and split into launches,
+ * every launch a loop over i through the kernel's own per-index routine (csrc/poly.hip.h: fr_rowcheck_at), the violation bits it returns counted
+ * per member.  0, or -1 when the arguments are refused. */
+int snarkvm_hip_selftest_fr_rowcheck_fold(void *out, uint64_t *violations, size_t n, size_t count, const void *const *a, const void *const *b,
+                                          const void *const *c, const void *multipliers);
+/* what snarkvm_hip_fr_rowcheck_fold was built with: out2 = {members per launch (FR_ROWCHECK_CHUNK), members per Montgomery reduction} */
+int snarkvm_hip_selftest_fr_rowcheck_geometry(uint32_t *out2);
 /* snarkvm_hip_fr_reduce / snarkvm_hip_fr_support over host memory with the CPU in the kernels' place, over a GIVEN launch geometry (blocks >= 1
  * workgroups of threads = 64, 128 or 256): every thread's private accumulation and every combine step through the kernels' own routines
  * (csrc/poly.hip.h: fr_reduce_thread, fr_support_thread, fr_support_combine), the trees level by level over the lanes they exchange between, the

@@ -219,6 +219,22 @@ inline void fr_selector_fold(void* h_out, size_t h_len, void* xg_out, size_t tar
                                        on_device ? 1 : 0));
 }
 
+// The gather of Varuna's round 1 (snarkvm_hip.h: snarkvm_hip_fr_witness_evals): out[k] = 0 on the input subgroup, w[k - k / ratio - 1] - x_evals[k]
+// elsewhere, ratio = n / input_size; out may be x_evals.  With on_device inside a Scope the call is only enqueued.
+inline void fr_witness_evals(void* out, size_t n, const DevicePoly& w, const void* x_evals, size_t input_size, bool on_device) {
+    check(snarkvm_hip_fr_witness_evals(out, n, w.data, w.len, x_evals, input_size, on_device ? 1 : 0));
+}
+
+// The sums of Varuna's round 2 in one device pass (snarkvm_hip.h: snarkvm_hip_fr_rowcheck_fold): out[i] = sum_k mu_k (a[k][i] b[k][i] - c[k][i]) and
+// violations[k] = the number of i with a[k][i] b[k][i] != c[k][i], over members of n elements each.  multipliers: a.size() x 32 bytes of HOST memory,
+// Montgomery form; violations: a.size() values of HOST memory, delivered when the Scope ends for a call inside one.  Either output may be nullptr
+// (skipped); on_device governs out and every member vector.
+inline void fr_rowcheck_fold(void* out, uint64_t* violations, size_t n, const std::vector<const void*>& a, const std::vector<const void*>& b,
+                             const std::vector<const void*>& c, const void* multipliers, bool on_device) {
+    if (b.size() != a.size() || c.size() != a.size()) throw std::invalid_argument("fr_rowcheck_fold: three vectors per member");
+    check(snarkvm_hip_fr_rowcheck_fold(out, violations, n, a.size(), a.data(), b.data(), c.data(), multipliers, on_device ? 1 : 0));
+}
+
 // Reductions in one device pass (snarkvm_hip.h: snarkvm_hip_fr_reduce, snarkvm_hip_fr_support): the sum of a vector, the inner product of two
 // (Evaluations::evaluate_with_coeffs with the Lagrange coefficients left in device memory), and the support of a coefficient vector.  `result`
 // is 32 bytes of HOST memory; with on_device inside a Scope the call is only enqueued and the value arrives when the Scope ends.

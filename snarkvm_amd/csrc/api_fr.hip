@@ -848,6 +848,176 @@ int snarkvm_hip_selftest_fr_selector_fold(void* h_out, size_t h_len, void* xg_ou
     return 0;
 }
 
+// ---- round 1: the evaluations of w on the variable domain (poly.hip.h: fr_witness_evals_kernel) ------------------------------------------
+static constexpr size_t FR_ROUND12_N_MAX = (size_t)1 << 28;
+static bool fr_ranges_overlap(const void* p, size_t np, const void* q, size_t nq) {
+    const uint8_t *x = (const uint8_t*)p, *y = (const uint8_t*)q;
+    return p && q && np && nq && x < y + sizeof(fr_mem_t) * nq && y < x + sizeof(fr_mem_t) * np;
+}
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  Nothing has been touched either way.
+static const char* fr_witness_check(const void* out, size_t n, const void* w, size_t w_len, const void* x_evals, size_t input_size) {
+    if (input_size == 0) return "input_size is 0";
+    if (n % input_size) return "input_size does not divide n";
+    if (n > FR_ROUND12_N_MAX) return "n above 2^28";
+    if (w_len > n - input_size) return "w is longer than n - input_size";
+    if (n && (!out || !x_evals)) return "null vector of non-zero length";
+    if (w_len && !w) return "null witness of non-zero length";
+    if ((out != x_evals && fr_ranges_overlap(out, n, x_evals, n)) || fr_ranges_overlap(out, n, w, w_len)) return "out overlaps an operand (only out == x_evals is allowed)";
+    return nullptr;
+}
+RustError snarkvm_hip_fr_witness_evals(void* out, size_t n, const void* w, size_t w_len, const void* x_evals, size_t input_size, int on_device) {
+    if (const char* why = fr_witness_check(out, n, w, w_len, x_evals, input_size)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_witness_evals: ") + why);
+    if (n == 0) return ok();
+    API_BEGIN_DEV(device_for(out, on_device ? 1 : 0))
+    if (on_device) {
+        const char* why = "fr_witness_evals: the operands live on different devices";
+        fr_same_device(c, x_evals, why);
+        if (w_len) fr_same_device(c, w, why);
+    }
+    const fr_mem_t* dw = fr_stage_in(c, 0, w_len ? w : nullptr, w_len, on_device);
+    const fr_mem_t* dx = fr_stage_in(c, 1, x_evals, n, on_device);
+    fr_mem_t* dout = fr_stage_out(c, 3, out, n, on_device);
+    hipLaunchKernelGGL(fr_witness_evals_kernel, dim3(fr_grid(n)), dim3(256), 0, c.stream, dout, (uint32_t)n, dw, (uint32_t)w_len, dx, (uint32_t)(n / input_size));
+    HIP_TRY(hipGetLastError());
+    fr_finish_out(c, dout, out, n, on_device);
+    fr_call_done(c, on_device);
+    API_END
+}
+// The same call on host memory with the CPU in the kernel's place, through the kernel's own per-index routine.  0, or -1 when refused.
+int snarkvm_hip_selftest_fr_witness_evals(void* out, size_t n, const void* w, size_t w_len, const void* x_evals, size_t input_size) {
+    if (fr_witness_check(out, n, w, w_len, x_evals, input_size)) return -1;
+    for (size_t k = 0; k < n; k++) fr_witness_at((fr_mem_t*)out, (const fr_mem_t*)w, (uint32_t)w_len, (const fr_mem_t*)x_evals, (uint32_t)(n / input_size), (uint32_t)k);
+    return 0;
+}
+
+// ---- round 2: the rowcheck fold (poly.hip.h: fr_rowcheck_fold_kernel) ------------------------------------------------------------------------
+// What the device call and its host replay share: validation, the member tables and the split into launches.  Launch j holds the members
+// first .. first + t.count - 1 of the caller's order (its pointers are bound later: to the caller's memory, or to the staged copies).
+struct fr_rowcheck_launch_t {
+    fr_rowcheck_t t;
+    size_t first;
+};
+struct fr_rowcheck_plan_t {
+    std::vector<fr_rowcheck_launch_t> launches;
+    int mode = 0;  // FR_ROWCHECK_FOLD | FR_ROWCHECK_CHECK: what is wanted
+};
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  Nothing has been touched either way.  A plan without launches:
+// no kernel is needed (n == 0, or nothing is wanted).
+static const char* fr_rowcheck_plan(const void* out, const uint64_t* violations, size_t n, size_t count, const void* const* a, const void* const* b, const void* const* c,
+                                    const void* multipliers, fr_rowcheck_plan_t& plan) {
+    if (n > FR_ROUND12_N_MAX) return "n above 2^28";
+    if (count > 65535) return "more than 65535 members";
+    if (count && (!a || !b || !c || (out && !multipliers))) return "missing argument";
+    if (n)
+        for (size_t k = 0; k < count; k++) {
+            if (!a[k] || !b[k] || !c[k]) return "null member";
+            if (fr_ranges_overlap(out, n, a[k], n) || fr_ranges_overlap(out, n, b[k], n) || fr_ranges_overlap(out, n, c[k], n)) return "out overlaps a member";
+        }
+    plan.mode = (out ? FR_ROWCHECK_FOLD : 0) | (violations && count ? FR_ROWCHECK_CHECK : 0);
+    if (!n || !plan.mode) return nullptr;
+    size_t at = 0;
+    do {  // no member at all: one launch that writes the zeros
+        fr_rowcheck_launch_t L{};
+        L.first = at, L.t.accumulate = at != 0;
+        int m = 0;
+        for (; m < FR_ROWCHECK_CHUNK && at < count; m++, at++) {
+            if (!out) continue;
+            const fr_mem_t mu_mem = fr_mem_from_host((const uint8_t*)multipliers + sizeof(fr_mem_t) * at);
+            const fr_t mu = fr_t::load(&mu_mem).from_mem_mont(), mu_fix = mu.from_mem_mont(), neg = mu.neg();
+            for (int l = 0; l < 9; l++) L.t.mu[m][l] = mu_fix.v[l], L.t.nmu[m][l] = neg.v[l];
+        }
+        L.t.count = m;
+        plan.launches.push_back(L);
+    } while (at < count);
+    return nullptr;
+}
+// pointers of the tables: member k's vectors at a[k], b[k], c[k]
+static void fr_rowcheck_bind(fr_rowcheck_plan_t& plan, const fr_mem_t* const* a, const fr_mem_t* const* b, const fr_mem_t* const* c) {
+    for (fr_rowcheck_launch_t& L : plan.launches)
+        for (int m = 0; m < L.t.count; m++) L.t.a[m] = a[L.first + m], L.t.b[m] = b[L.first + m], L.t.c[m] = c[L.first + m];
+}
+RustError snarkvm_hip_fr_rowcheck_fold(void* out, uint64_t* violations, size_t n, size_t count, const void* const* a, const void* const* b, const void* const* c3,
+                                       const void* multipliers, int on_device) {
+    fr_rowcheck_plan_t plan;
+    if (const char* why = fr_rowcheck_plan(out, violations, n, count, a, b, c3, multipliers, plan)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_rowcheck_fold: ") + why);
+    if (plan.launches.empty()) {
+        if (violations && count) memset(violations, 0, sizeof(uint64_t) * count);  // n == 0: nothing is violated
+        return ok();
+    }
+    API_BEGIN_DEV(device_for(out ? out : a[0], on_device ? 1 : 0))
+    fr_mem_t* dout = (fr_mem_t*)out;
+    std::vector<const fr_mem_t*> members[3];
+    const void* const* given[3] = {a, b, c3};
+    for (auto& v : members) v.assign(count, nullptr);
+    if (on_device) {
+        const char* why = "fr_rowcheck_fold: out and the members live on different devices";
+        for (int j = 0; j < 3; j++)
+            for (size_t k = 0; k < count; k++) fr_same_device(c, given[j][k], why), members[j][k] = (const fr_mem_t*)given[j][k];
+    } else {
+        // host operands: one lane buffer holds out and, behind it, every member vector; one upload each, one download
+        c.poly[0].ensure(sizeof(fr_mem_t) * n * ((out ? 1 : 0) + 3 * count));
+        fr_mem_t* next = c.poly[0].as<fr_mem_t>();
+        if (out) dout = next, next += n;
+        for (int j = 0; j < 3; j++)
+            for (size_t k = 0; k < count; k++) {
+                HIP_TRY(hipMemcpyAsync(next, given[j][k], sizeof(fr_mem_t) * n, hipMemcpyHostToDevice, c.stream));
+                members[j][k] = next, next += n;
+            }
+    }
+    fr_rowcheck_bind(plan, members[0].data(), members[1].data(), members[2].data());
+    unsigned long long* dviol = nullptr;
+    if (plan.mode & FR_ROWCHECK_CHECK) {  // workspace: one 64-bit counter per member
+        c.poly[4].ensure(sizeof(unsigned long long) * count);
+        dviol = c.poly[4].as<unsigned long long>();
+        HIP_TRY(hipMemsetAsync(dviol, 0, sizeof(unsigned long long) * count, c.stream));
+    }
+    const dim3 grid(fr_grid(n)), block(256);
+    for (const fr_rowcheck_launch_t& L : plan.launches) {
+        unsigned long long* v = dviol ? dviol + L.first : nullptr;
+        if (plan.mode == FR_ROWCHECK_FOLD)
+            hipLaunchKernelGGL(fr_rowcheck_fold_kernel<FR_ROWCHECK_FOLD>, grid, block, 0, c.stream, dout, v, (uint32_t)n, L.t);
+        else if (plan.mode == FR_ROWCHECK_CHECK)
+            hipLaunchKernelGGL(fr_rowcheck_fold_kernel<FR_ROWCHECK_CHECK>, grid, block, 0, c.stream, dout, v, (uint32_t)n, L.t);
+        else
+            hipLaunchKernelGGL(fr_rowcheck_fold_kernel<FR_ROWCHECK_FOLD | FR_ROWCHECK_CHECK>, grid, block, 0, c.stream, dout, v, (uint32_t)n, L.t);
+    }
+    HIP_TRY(hipGetLastError());
+    if (out) fr_finish_out(c, dout, out, n, on_device);
+    // device operands inside a scope: delivered by snarkvm_hip_scope_end; host operands: the call waits below, the counts are there on return
+    if (dviol) c.host_result(violations, dviol, sizeof(uint64_t) * count, on_device != 0);
+    fr_call_done(c, on_device);
+    API_END
+}
+// The same call on host memory with the CPU in the kernel's place: the same plan, every launch a loop over i through the kernel's own
+// per-index routine, the bits it returns counted per member.  0, or -1 when the plan refuses the arguments.
+int snarkvm_hip_selftest_fr_rowcheck_fold(void* out, uint64_t* violations, size_t n, size_t count, const void* const* a, const void* const* b, const void* const* c3,
+                                          const void* multipliers) {
+    fr_rowcheck_plan_t plan;
+    if (fr_rowcheck_plan(out, violations, n, count, a, b, c3, multipliers, plan)) return -1;
+    const bool check = violations && count;
+    if (check) memset(violations, 0, sizeof(uint64_t) * count);
+    if (plan.launches.empty()) return 0;
+    fr_rowcheck_bind(plan, (const fr_mem_t* const*)a, (const fr_mem_t* const*)b, (const fr_mem_t* const*)c3);
+    for (const fr_rowcheck_launch_t& L : plan.launches)
+        for (size_t i = 0; i < n; i++) {
+            uint32_t bad;
+            if (plan.mode == FR_ROWCHECK_FOLD)
+                bad = fr_rowcheck_at<FR_ROWCHECK_FOLD>(L.t, (fr_mem_t*)out, (uint32_t)i);
+            else if (plan.mode == FR_ROWCHECK_CHECK)
+                bad = fr_rowcheck_at<FR_ROWCHECK_CHECK>(L.t, (fr_mem_t*)out, (uint32_t)i);
+            else
+                bad = fr_rowcheck_at<FR_ROWCHECK_FOLD | FR_ROWCHECK_CHECK>(L.t, (fr_mem_t*)out, (uint32_t)i);
+            for (int m = 0; bad; m++, bad >>= 1) violations[L.first + m] += bad & 1;
+        }
+    return 0;
+}
+// the members per launch and per Montgomery reduction the library was built with
+int snarkvm_hip_selftest_fr_rowcheck_geometry(uint32_t* out2) {
+    if (!out2) return -1;
+    out2[0] = FR_ROWCHECK_CHUNK, out2[1] = FR_ROWCHECK_G;
+    return 0;
+}
+
 // ---- reductions (poly.hip.h: fr_reduce_kernel, fr_support_kernel) ---------------------------------------------------------------
 // nullptr, or why the call is refused (hipErrorInvalidValue); needs no device
 static const char* fr_reduce_check(int op, const void* result, const void* a, const void* b, size_t n) {

@@ -11,6 +11,8 @@
 //   fr_mul_vanishing_kernel     p * (X^D - 1)                                    dense.rs:153-159
 //   fr_selector_fold_kernel     sum_k mu_k (quotient, tiled remainder) of p_k by X^n_k - 1, and the sums over the n_k-th roots
 //                                                                                 third.rs:126-327, selectors.rs:100-121 (round 3)
+//   fr_witness_evals_kernel     w's evaluations on the variable domain: the interleaving gather minus x     first.rs:127-161 (round 1)
+//   fr_rowcheck_fold_kernel     sum_k mu_k (a_k b_k - c_k) and the per-member counts of a_k b_k != c_k      second.rs:76-142, selectors.rs:88-99 (round 2)
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
 //   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
 //   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
@@ -473,6 +475,122 @@ static __global__ void fr_tile_kernel(fr_mem_t* v, uint32_t period, uint32_t n) 
     const size_t st = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += st) fr_tile_at(v, period, (uint32_t)i);
 }
+
+// ---- rounds 1 and 2: the witness gather and the rowcheck fold ---------------------------------------------------------------------
+// Round 1 (calculate_w, first.rs:127-161): between the forward and the inverse transform at |V| the reference interleaves the private
+// variables with the input subgroup - position k of the variable domain is an input position when ratio = |V| / |X| divides k (there w is
+// zero), otherwise it holds private variable k - k / ratio - 1 (zero past the end of the witness) minus x_poly's evaluation at k.  A map:
+// one thread per element, which reads x[k] before it writes out[k], so out may BE x.
+SV_HD void fr_witness_at(fr_mem_t* out, const fr_mem_t* w, uint32_t w_len, const fr_mem_t* x, uint32_t ratio, uint32_t k) {
+    const uint32_t q = k / ratio;
+    if (k == q * ratio) {
+        fr_t::zero().store(&out[k]);
+        return;
+    }
+    const uint32_t j = k - q - 1;
+    const fr_t wv = j < w_len ? fr_t::load(&w[j]) : fr_t::zero();
+    (wv - fr_t::load(&x[k])).store(&out[k]);
+}
+static __global__ void __launch_bounds__(256) fr_witness_evals_kernel(fr_mem_t* out, uint32_t n, const fr_mem_t* w, uint32_t w_len, const fr_mem_t* x, uint32_t ratio) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < n; i += st) fr_witness_at(out, w, w_len, x, ratio, (uint32_t)i);
+}
+// Round 2 (calculate_rowcheck_witness, second.rs:76-142, with apply_randomized_selector without a remainder witness, selectors.rs:88-99):
+// h_0 = sum over every instance k of every circuit of mu_k (z_a z_b - z_c) / v_R.  z_a z_b - z_c has degree <= 2 |R| - 2, its quotient by v_R
+// degree <= |R| - 2, so the quotient is fixed by its values on ONE coset g R, where v_R is the constant g^|R| - 1: no doubled domain.  Folded
+// into mu_k, the constant leaves
+//   out[i] = sum_k mu_k (a_k[i] b_k[i] - c_k[i])                                         (FR_ROWCHECK_FOLD; over coset evaluations)
+//   violations[k] = #{i < n : a_k[i] b_k[i] != c_k[i]}                                     (FR_ROWCHECK_CHECK; over evaluations on R itself:
+//                                                                                            the remainder by v_R is zero iff every count is)
+// and, the inverse transform being linear, ONE inverse coset transform of `out` where the reference runs one per instance.
+// The member table travels BY KERNEL ARGUMENT like fr_selector_t.  Vectors are streamed raw: raw(a) * raw(b) is the internal form of
+// a b 2^-10, so the host passes mu_k * MEM2INT beside -mu_k (both true internal form) and the member's term is the sum of TWO wide products,
+// (mu_k MEM2INT) (a b) + (-mu_k) c, a raw memory-form value: FR_ROWCHECK_G members = 2 G wide products go through one
+// Fp::sum_of_products (its conditions hold: the multipliers are canonical, a b is a canonical product and c a memory image).  The check
+// compares (a b).from_mem_mont() with c limb for limb: both canonical.  A list longer than FR_ROWCHECK_CHUNK takes further launches with
+// `accumulate` set, which add to `out`.  Counts: a wave's violating lanes of member m are counted by one ballot and added to the member's
+// 64-bit counter by one integer atomic of the lowest such lane - integer sums, so the counts do not depend on the order; a wave without a
+// violation (every wave of a valid proof) issues none.  The Fr output has no atomics and a fixed order of additions.
+// Indices are 32-bit: n <= 2^28.  Registers (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): fr_rowcheck_fold_kernel<FOLD> 131 VGPRs, 102 SGPRs,
+// 3 waves per SIMD at G = 3; <CHECK> 52 VGPRs, 8 waves; <FOLD | CHECK> 144 VGPRs and 10 SGPRs spilled to VGPR lanes; fr_witness_evals_kernel 28 VGPRs;
+// no scratch in any of them.  tools/bench_fr_rowcheck.py times G = 3 against G = 1 (-DFR_ROWCHECK_G=1); what has been measured is in
+// profiles/fr_rowcheck.md.
+enum { FR_ROWCHECK_FOLD = 1, FR_ROWCHECK_CHECK = 2 };
+#ifndef FR_ROWCHECK_G
+#define FR_ROWCHECK_G 3  // members per Montgomery reduction (two wide products each): measured against 1 (profiles/fr_rowcheck.md)
+#endif
+static_assert(FR_ROWCHECK_G >= 1 && FR_ROWCHECK_G <= 3, "Fp::sum_of_products takes at most 6 terms: two per member");
+static constexpr int FR_ROWCHECK_CHUNK = 24;  // members per launch: 24 x (3 x 8 + 36 + 36) B + 8 = 2312 B of the 4 KB of kernel arguments
+static_assert(FR_ROWCHECK_CHUNK <= 32, "fr_rowcheck_at returns one bit per member of a launch");
+struct fr_rowcheck_t {
+    const fr_mem_t* a[FR_ROWCHECK_CHUNK];
+    const fr_mem_t* b[FR_ROWCHECK_CHUNK];
+    const fr_mem_t* c[FR_ROWCHECK_CHUNK];
+    uint32_t mu[FR_ROWCHECK_CHUNK][9];   // limbs of mu_k * MEM2INT, true internal form
+    uint32_t nmu[FR_ROWCHECK_CHUNK][9];  // limbs of -mu_k, true internal form
+    int count;
+    int accumulate;  // out already holds the sum over earlier members
+};
+// members k0 + g .. k0 + G - 1 of a group, by recursion (see fr_selector_members)
+template <int MODE, int G, int g>
+SV_HD void fr_rowcheck_members(const fr_rowcheck_t& t, int k0, uint32_t i, fr_t* f, fr_t* x, uint32_t& bad) {
+    if constexpr (g < G) {
+        const int k = k0 + g;
+        const fr_t ab = fr_t::load(&t.a[k][i]) * fr_t::load(&t.b[k][i]);
+        const fr_t c = fr_t::load(&t.c[k][i]);
+        if (MODE & FR_ROWCHECK_CHECK) bad |= (ab.from_mem_mont() != c ? 1u : 0u) << k;
+        if (MODE & FR_ROWCHECK_FOLD) {
+            f[2 * g] = fr_t::from_table(t.mu[k]), x[2 * g] = ab;
+            f[2 * g + 1] = fr_t::from_table(t.nmu[k]), x[2 * g + 1] = c;
+        }
+        fr_rowcheck_members<MODE, G, g + 1>(t, k0, i, f, x, bad);
+    }
+}
+template <int MODE, int G>
+SV_HD void fr_rowcheck_group(const fr_rowcheck_t& t, int k0, uint32_t i, fr_t& acc, uint32_t& bad) {
+    fr_t f[2 * G], x[2 * G];
+    fr_rowcheck_members<MODE, G, 0>(t, k0, i, f, x, bad);
+    if (MODE & FR_ROWCHECK_FOLD) acc = acc + fr_t::sum_of_products<2 * G>(f, x);
+}
+// the per-index routine: the kernel below and the host replay (snarkvm_hip_selftest_fr_rowcheck_fold) both call it.  -> bit m set: member m
+// of this launch is violated at i (MODE without CHECK: 0).  out is written only with FOLD.
+template <int MODE>
+SV_HD uint32_t fr_rowcheck_at(const fr_rowcheck_t& t, fr_mem_t* out, uint32_t i) {
+    fr_t acc = fr_t::zero();
+    uint32_t bad = 0;
+    if ((MODE & FR_ROWCHECK_FOLD) && t.accumulate) acc = fr_t::load(&out[i]);
+    int step;
+#pragma unroll 1
+    for (int k0 = 0; k0 < t.count; k0 += step) {  // whole groups, then what is left in groups of 2 or 1
+        const int left = t.count - k0;
+        if (left >= FR_ROWCHECK_G)
+            fr_rowcheck_group<MODE, FR_ROWCHECK_G>(t, k0, i, acc, bad), step = FR_ROWCHECK_G;
+        else if (left == 2)
+            fr_rowcheck_group<MODE, (FR_ROWCHECK_G >= 2 ? 2 : 1)>(t, k0, i, acc, bad), step = FR_ROWCHECK_G >= 2 ? 2 : 1;
+        else
+            fr_rowcheck_group<MODE, 1>(t, k0, i, acc, bad), step = 1;
+    }
+    if (MODE & FR_ROWCHECK_FOLD) acc.store(&out[i]);
+    return bad;
+}
+#if defined(__HIPCC__)
+// viol: the counters of this launch's members, zeroed by the host before the first launch
+template <int MODE>
+static __global__ void __launch_bounds__(256) fr_rowcheck_fold_kernel(fr_mem_t* out, unsigned long long* viol, uint32_t n, fr_rowcheck_t t) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < n; i += st) {
+        const uint32_t bad = fr_rowcheck_at<MODE>(t, out, (uint32_t)i);
+        if ((MODE & FR_ROWCHECK_CHECK) && __ballot(bad != 0)) {
+            for (int m = 0; m < t.count; m++) {
+                const unsigned long long who = __ballot((bad >> m) & 1);
+                if (who && (int)(threadIdx.x & 63) == __ffsll(who) - 1) atomicAdd(&viol[m], (unsigned long long)__popcll(who));
+            }
+        }
+    }
+}
+#endif
 
 // ---- reductions: a vector -> a value ----------------------------------------------------------------------------------------
 // The third family of Fr passes beside the maps and the scans: ONE streaming read with a tree at the end, so that a question about a

@@ -15,8 +15,13 @@ The transpose is circuit data like the matrix itself: built once on the host (`t
 
 Round 3 is driven here from the registered transposes to its two oracles: the sparse products, the transforms and the per-member products
 are entry points that already exist, and the selector of every (instance, matrix) member, the running h_1 / x g_1 sums, the mask polynomial
-and the sums over the variable domain are ONE pass (`snarkvm_hip_fr_selector_fold`).  Nothing here builds a circuit index; rounds 1 and 2
-have no driver function.
+and the sums over the variable domain are ONE pass (`snarkvm_hip_fr_selector_fold`).
+
+    w = (gather of the private variables - x) / (X^|X| - 1)     round_functions/first.rs:127-161 (`witness_poly_device`)
+    h_0 = sum mu (z_a z_b - z_c) / v_R                          round_functions/second.rs:76-142 with ahp/selectors.rs:88-99 (`rowcheck_witness`)
+
+Rounds 1 and 2 open a proof: w by the gather `snarkvm_hip_fr_witness_evals` between two transforms at |V|, h_0 for all instances of all circuits
+on one coset per domain size with `snarkvm_hip_fr_rowcheck_fold` as both the divisibility test and the sum.  Nothing here builds a circuit index.
 """
 import collections
 import ctypes
@@ -414,3 +419,142 @@ def lineval_sumcheck_witness(circuits, alpha, eta_b, eta_c, lg_max_variable_doma
         first += count
     del keep
     return DevicePoly(d_h, h_len, out), DevicePoly(d_xg, N, out), DevicePoly(d_xg + 32, N - 1, out), sums
+
+
+# ---- rounds 1 and 2: w and the rowcheck witness h_0 ----------------------------------------------------------------------------------------------
+_COSET_GENERATOR = 22  # Fr::GENERATOR (curves/src/bls12_377/fr.rs): the shift of the coset transforms (NTTType::Coset)
+
+
+class _Scope:
+    """A deferred-synchronisation scope of the calling thread around a driver function, unless the thread has one open already (scopes do not
+    nest): every device-resident call inside is only enqueued and the host waits once.  `own`: this object opened it."""
+
+    def __init__(self, d_any):
+        self.d_any, self.own = int(d_any), False
+
+    def __enter__(self):
+        L = _lib.lib()
+        if not L.snarkvm_hip_scope_stream():
+            _lib.check(L.snarkvm_hip_scope_begin(ctypes.c_void_p(self.d_any)))
+            self.own = True
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.own:
+            err = _lib.lib().snarkvm_hip_scope_end()  # a failed call must not leave this thread's scope open
+            if exc_type is None:
+                _lib.check(err)
+        return False
+
+
+def witness_poly_device(d_w, w_len, d_x_poly, input_size, lg_variable_domain, d_out, device=-1):
+    """`calculate_w` (first.rs:127-161) for one instance on device memory: the private variables (w_len <= |V| - |X| elements at d_w) and x_poly
+    (input_size = |X| coefficients at d_x_poly: the interpolation of the padded public input) -> the |V| - |X| coefficients of w in d_out (the
+    caller's; it must overlap neither operand).  x_poly goes zero-padded to |V| = 2^lg_variable_domain through the forward transform, the gather
+    `snarkvm_hip_fr_witness_evals` runs in place on its evaluations, the inverse transform yields w (X^|X| - 1) and `fr_divide_by_vanishing` by
+    X^|X| - 1 the quotient; the remainder is tested with `fr_support` and a non-zero one raises ValueError (it cannot happen for valid sizes: the
+    gathered vector vanishes on the input subgroup).  Workspace: |V| + |X| elements on `device` (the device of d_out), released on return.  The five
+    calls run in one scope and wait once.  Call it outside a scope: it reads the remainder test back.  -> the number of coefficients written."""
+    L = _lib.lib()
+    V, X, w_len = 1 << int(lg_variable_domain), int(input_size), int(w_len)
+    if X < 1 or X & (X - 1) or X > V:
+        raise ValueError("witness_poly_device: input_size is a power of two, at most the variable domain")
+    if w_len < 0 or w_len > V - X:
+        raise ValueError("witness_poly_device: more private variables than the variable domain has room for")
+    if L.snarkvm_hip_scope_stream():
+        raise ValueError("witness_poly_device: call it outside a scope (it reads the remainder test back)")
+    work = HipMem(32 * (V + X), device)
+    d_rem = work.ptr + 32 * V
+    with _Scope(work.ptr):
+        work.fill(32 * X, 0, 32 * (V - X))
+        work.copy_from(0, _dev_ptr(d_x_poly), 32 * X)
+        plugin.NTT_device_batch(int(lg_variable_domain), [work.ptr], directions=[0], types=[0])
+        plugin.fr_witness_evals_device(work.ptr, V, _dev_ptr(d_w) if w_len else None, w_len, work.ptr, X)
+        plugin.NTT_device_batch(int(lg_variable_domain), [work.ptr], directions=[1], types=[0])
+        _lib.check(L.snarkvm_hip_fr_divide_by_vanishing(_dev_ptr(d_out) if V > X else None, d_rem, work.ptr, V, X, 1))
+        support = plugin.fr_support_device(d_rem, X)
+    if int(support[0]) != 0:
+        raise ValueError("Failed to divide by vanishing polynomial - non-zero remainder")
+    return V - X
+
+
+RowcheckCircuit = collections.namedtuple("RowcheckCircuit", "lg_r circuit_combiner instance_combiners z")
+RowcheckCircuit.__doc__ = """One circuit of round 2: the constraint domain 2^lg_r, `circuit_combiner` ((4,) Montgomery limbs), `instance_combiners`
+((instances, 4)) and `z`: per instance the three device vectors (z_a, z_b, z_c) of 2^lg_r evaluations each - pointers or DevicePoly, the
+n_out-padded outputs of `RegisteredMatrix.mul_device`."""
+
+
+class RowcheckWitness(DevicePoly):
+    """h_0 as a DevicePoly, with the divisibility test of the round: `violations` = per (circuit, instance) member, in the order of `members`, the
+    number of rows with z_a z_b != z_c - filled when the scope the calls were enqueued in has ended."""
+
+    def __init__(self, ptr, n, owner, members, counts):
+        super().__init__(ptr, n, owner)
+        self.members, self._counts = members, counts
+
+    @property
+    def violations(self):
+        return [int(c) for arr in self._counts for c in arr]
+
+    def ensure_divisible(self):
+        """the `ensure!` of selectors.rs:92-93: raises ValueError naming the first member with a violated row"""
+        for (circuit, instance), count in zip(self.members, self.violations):
+            if count:
+                raise ValueError(f"Failed to divide by vanishing polynomial - non-zero remainder (circuit {circuit}, instance {instance}: "
+                                 f"{count} rows with z_a z_b != z_c)")
+        return self
+
+
+def rowcheck_witness(circuits, lg_max_constraint_domain, device=-1):
+    """`calculate_rowcheck_witness` (second.rs:76-142) over the RowcheckCircuit list `circuits`, on device memory: h_0 = the sum over every instance
+    of every circuit of instance_combiner * circuit_combiner * |R| / |R_max| * (z_a z_b - z_c) / v_R (apply_randomized_selector without a remainder
+    witness, selectors.rs:88-99).  z_a z_b - z_c has degree <= 2 |R| - 2 and its quotient by v_R degree <= |R| - 2, so the quotient is fixed by
+    its values on ONE coset g R (g = 22, the shift of NTTType::Coset), where v_R is the constant g^|R| - 1 - no transform at 2 |R|.  Per distinct
+    domain size: one check-only `snarkvm_hip_fr_rowcheck_fold` over the evaluations as given (the remainder by v_R is zero iff z_a z_b = z_c on
+    all of R), one inverse transform batch, one forward coset batch, ONE fold with mu = instance_combiner * circuit_combiner * |R| / |R_max| /
+    (g^|R| - 1) and - the inverse transform being linear - ONE inverse coset transform where the reference runs one per instance; then one
+    `fr_lincomb` across the sizes when there are several (or a size below |R_max|).  Field arithmetic is exact: the coefficients are the
+    reference's bytes whenever the reference succeeds.
+    The input vectors are CONSUMED, as `z_a.take()` does (second.rs:104-106): on return they hold coset evaluations.
+    Every call is only enqueued: in a scope of its own when the calling thread has none open - then the host waits once, a violated row raises
+    ValueError with the reference's message "Failed to divide by vanishing polynomial - non-zero remainder", naming the first offending member,
+    and no h_0 is returned - or in the caller's open scope: nothing is waited for, and the caller runs `ensure_divisible()` on the result after
+    its scope has ended (the counts arrive with `snarkvm_hip_scope_end`, like the result of `fr_support`).
+    -> RowcheckWitness (a DevicePoly) of |R_max| = 2^lg_max_constraint_domain coefficients, untrimmed."""
+    lg_max = int(lg_max_constraint_domain)
+    n_max = 1 << lg_max
+    by_size = collections.OrderedDict()
+    for ci, c in enumerate(circuits):
+        lg = int(c.lg_r)
+        if lg < 0 or lg > lg_max:
+            raise ValueError("rowcheck_witness: a constraint domain is larger than the maximal one")
+        inst = _from_mont(c.instance_combiners)
+        if len(inst) != len(c.z):
+            raise ValueError("rowcheck_witness: one instance combiner per instance")
+        cc = _from_mont(c.circuit_combiner)[0]
+        for i, (za, zb, zc) in enumerate(c.z):
+            by_size.setdefault(lg, []).append(((ci, i), (_dev_ptr(za), _dev_ptr(zb), _dev_ptr(zc)), cc * inst[i] % R_MOD))
+    sizes = sorted(by_size)
+    direct = len(sizes) == 1 and sizes[0] == lg_max  # the one fold's output is h_0 itself
+    total = sum(1 << lg for lg in sizes) + (0 if direct else n_max)
+    mem = HipMem(32 * max(total, 1), device)
+    members, counts, parts, at = [], [], [], 0 if direct else n_max
+    with _Scope(mem.ptr) as scope:
+        for lg in sizes:
+            n, group = 1 << lg, by_size[lg]
+            a, b, c3 = ([m[1][j] for m in group] for j in range(3))
+            members += [m[0] for m in group]
+            counts.append(plugin.fr_rowcheck_fold_device(None, n, a, b, c3, None))
+            ptrs = a + b + c3
+            plugin.NTT_device_batch(lg, ptrs, directions=[1] * len(ptrs), types=[0] * len(ptrs))
+            plugin.NTT_device_batch(lg, ptrs, directions=[0] * len(ptrs), types=[1] * len(ptrs))
+            scale = (1 << lg) * pow(n_max, -1, R_MOD) % R_MOD * pow(pow(_COSET_GENERATOR, n, R_MOD) - 1, -1, R_MOD) % R_MOD
+            d_part = mem.ptr + 32 * at
+            plugin.fr_rowcheck_fold_device(d_part, n, a, b, c3, _mont_limbs([m[2] * scale % R_MOD for m in group]), violations=False)
+            plugin.NTT_device_batch(lg, [d_part], directions=[1], types=[1])
+            parts.append((d_part, n))
+            at += n
+        if not direct:
+            plugin.fr_lincomb_device(mem.ptr, n_max, [p for p, _ in parts], [n for _, n in parts], _mont_limbs([1] * len(parts)))
+    out = RowcheckWitness(mem.ptr, n_max, mem, members, counts)
+    return out.ensure_divisible() if scope.own else out

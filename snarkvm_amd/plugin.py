@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -112,6 +112,45 @@ def fr_selector_fold_device(d_h, h_len, d_xg, target_size, d_sums, d_polys, lens
     ps = (ctypes.c_size_t * max(1, k))(*[int(n) for n in src_sizes])
     _lib.check(_lib.lib().snarkvm_hip_fr_selector_fold(int(d_h) if d_h else None, int(h_len), int(d_xg) if d_xg else None, int(target_size),
                                                        int(d_sums) if d_sums else None, k, pp, pl, ps, _ptr(mu), 1))
+
+
+def fr_witness_evals_device(d_out, n, d_w, w_len, d_x_evals, input_size):
+    """Extension (no reference counterpart): the gather of Varuna's round 1 over vectors that live in device memory (`snarkvm_hip_fr_witness_evals`,
+    on_device = 1; first.rs:127-161).  With ratio = n / input_size: d_out[k] = 0 when ratio divides k, d_w[k - k // ratio - 1] - d_x_evals[k]
+    otherwise; d_w counts as zero from w_len <= n - input_size on.  d_out may equal d_x_evals (in place).  Inside a scope the call is only
+    enqueued."""
+    n, w_len, input_size = int(n), int(w_len), int(input_size)
+    if input_size <= 0 or n % input_size:
+        raise ValueError("input_size must divide n")
+    if w_len < 0 or w_len > n - input_size:
+        raise ValueError("w is longer than n - input_size")
+    _lib.check(_lib.lib().snarkvm_hip_fr_witness_evals(_dp(d_out), n, _dp(d_w) if w_len else None, w_len, _dp(d_x_evals), input_size, 1))
+
+
+FR_ROWCHECK_CHUNK = 24  # members per kernel launch of snarkvm_hip_fr_rowcheck_fold (include/snarkvm_hip.h; csrc/poly.hip.h FR_ROWCHECK_CHUNK)
+
+
+def fr_rowcheck_fold_device(d_out, n, d_a, d_b, d_c, multipliers, violations=True):
+    """Extension (no reference counterpart): the sums of Varuna's round 2 over members that live in device memory (`snarkvm_hip_fr_rowcheck_fold`,
+    on_device = 1; second.rs:76-142 with apply_randomized_selector, selectors.rs:88-99).  Member k = the n-element vectors d_a[k], d_b[k], d_c[k]
+    with multiplier multipliers[k] ((k, 4) Montgomery limbs on the host; may be None when d_out is None):
+        d_out[i]      = sum_k mu_k (a_k[i] b_k[i] - c_k[i])          i < n        (skipped when d_out is None: the check alone)
+        violations[k] = the number of i < n with a_k[i] b_k[i] != c_k[i]           (skipped with violations=False: the fold alone)
+    -> the counts as a (len(d_a),) uint64 array, or None.  No member is written.  Inside a scope the call is only enqueued and the returned array
+    is filled when the scope ends: keep it alive until then."""
+    k = len(d_a)
+    if len(d_b) != k or len(d_c) != k:
+        raise ValueError("length mismatch")
+    mu = None
+    if d_out:
+        mu = np.ascontiguousarray(multipliers, dtype=np.uint64).reshape(-1, 4) if k else np.zeros((0, 4), dtype=np.uint64)
+        if mu.shape[0] != k:
+            raise ValueError("length mismatch")
+    counts = np.zeros(k, dtype=np.uint64) if violations else None
+    lists = [(ctypes.c_void_p * max(1, k))(*[_dp(p) for p in ps]) for ps in (d_a, d_b, d_c)]
+    _lib.check(_lib.lib().snarkvm_hip_fr_rowcheck_fold(_dp(d_out), _ptr(counts) if violations and k else None, int(n), k, lists[0], lists[1], lists[2],
+                                                       _ptr(mu) if mu is not None and k else None, 1))
+    return counts
 
 
 FR_REDUCE_SUM, FR_REDUCE_DOT = 0, 1  # include/snarkvm_hip.h: SNARKVM_HIP_FR_REDUCE_*

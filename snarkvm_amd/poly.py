@@ -6,6 +6,8 @@ Host mirror of the reference functions the Varuna prover runs between its NTTs a
     `polynomial / (X - point)` (Polynomial::divide_with_q_and_r)                    fft/polynomial/mod.rs:222-256
     `poly += (coeff, cur_poly)` over the terms of a linear combination              polycommit/sonic_pc/mod.rs:413-473, 548-564
     apply_randomized_selector summed over the members of round 3 (`selector_fold`)  ahp/selectors.rs:100-121, round_functions/third.rs:179-213
+    the gather of calculate_w between its two transforms (`witness_evals`)          round_functions/first.rs:127-161
+    calculate_rowcheck_witness's sum and divisibility test (`rowcheck_fold`)        round_functions/second.rs:76-142, ahp/selectors.rs:88-99
     Evaluations::evaluate_with_coeffs (an inner product), sums over a domain        fft/evaluations.rs:90-92, round_functions/first.rs:119
     DensePolynomial::{degree, is_zero}, skip_leading_zeros_and_convert_to_bigints   fft/polynomial/dense.rs:66-96, kzg10/mod.rs:455-467
     batch_inversion / batch_inversion_and_mul                                       fields/src/lib.rs:66-129
@@ -92,6 +94,42 @@ def selector_fold(polys, src_sizes, multipliers, target_size, h_len=None, want="
     nz = lambda a: a.ctypes.data if a is not None and a.size else None
     _lib.check(_lib.lib().snarkvm_hip_fr_selector_fold(nz(h), int(h_len), nz(xg), int(target_size), nz(sums), k, ptrs, lens, srcs, _p(mu), 0))
     return h, xg, sums
+
+
+def witness_evals(w, x_evals, input_size):
+    """The gather of Varuna's round 1 over host arrays in one device pass (`snarkvm_hip_fr_witness_evals`; calculate_w, first.rs:127-161): x_evals =
+    the n evaluations of x_poly over the variable domain, w = the private variables (at most n - input_size).  -> (n, 4): zero where
+    ratio = n / input_size divides k, w[k - k // ratio - 1] - x_evals[k] elsewhere (w zero past its end)."""
+    w, x = _v(w), _v(x_evals)
+    n = x.shape[0]
+    if int(input_size) <= 0 or n % int(input_size) or w.shape[0] > n - int(input_size):
+        raise ValueError("input_size must divide n and w hold at most n - input_size elements")
+    out = np.empty_like(x)
+    _lib.check(_lib.lib().snarkvm_hip_fr_witness_evals(_p(out) if n else None, n, _p(w) if w.shape[0] else None, w.shape[0], _p(x) if n else None, int(input_size), 0))
+    return out
+
+
+def rowcheck_fold(a, b, c, multipliers=None, want="ov"):
+    """The sums of Varuna's round 2 over host arrays in ONE device pass (`snarkvm_hip_fr_rowcheck_fold`; calculate_rowcheck_witness,
+    second.rs:76-142): a, b, c = one (n, 4) array per member each.  -> (out, violations): out[i] = sum_k multipliers[k] (a_k[i] b_k[i] - c_k[i])
+    as (n, 4), violations[k] = the number of i with a_k[i] b_k[i] != c_k[i] as (len(a),) uint64; None for the outputs whose letter is not in `want`
+    ("o", "v").  multipliers is needed for "o" only."""
+    a, b, c = ([_v(x) for x in xs] for xs in (a, b, c))
+    k = len(a)
+    n = a[0].shape[0] if k else 0
+    if len(b) != k or len(c) != k or any(x.shape[0] != n for x in a + b + c):
+        raise ValueError("length mismatch")  # the reference zips with zip_eq
+    mu = None
+    if "o" in want:
+        mu = _v(multipliers) if k else np.zeros((0, 4), dtype=np.uint64)
+        if mu.shape[0] != k:
+            raise ValueError("length mismatch")
+    out = np.empty((n, 4), dtype=np.uint64) if "o" in want else None
+    counts = np.zeros(k, dtype=np.uint64) if "v" in want else None
+    lists = [(ctypes.c_void_p * max(1, k))(*[x.ctypes.data if n else None for x in xs]) for xs in (a, b, c)]
+    nz = lambda v: v.ctypes.data if v is not None and v.size else None
+    _lib.check(_lib.lib().snarkvm_hip_fr_rowcheck_fold(nz(out), nz(counts), n, k, lists[0], lists[1], lists[2], nz(mu), 0))
+    return out, counts
 
 
 def inner_product(a, b):
