@@ -383,6 +383,41 @@ RustError snarkvm_hip_fr_mul_by_vanishing(void *out, const void *poly, size_t le
 RustError snarkvm_hip_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs,
                                  int on_device);
 
+/* Opening fold: a linear combination of polynomials, its quotient by X - point and its value at `point` in one sweep up and one sweep down -
+ * the polynomial side of one query point of SonicKZG10::open_combinations / batch_open (polycommit/sonic_pc/mod.rs:286-342, 413-473 into
+ * KZG10::compute_witness_polynomial, kzg10/mod.rs:213-236) once the opening challenges have been folded into the coefficients on the host
+ * (sum_lc xi_lc sum_k a_(lc,k) p_k = sum_k (sum_lc xi_lc a_(lc,k)) p_k), and with quotient = NULL the get_lc_eval of snark/varuna/varuna.rs:583-590.
+ *    comb[i] = sum_k coeffs[k] * polys[k][i]  for i < n, polys[k][i] counting as zero from lens[k] on
+ *    h_i     = sum_{j >= i} comb[j] * point^(j - i)
+ *  - quotient (optional): a buffer of n elements, ALL written: quotient[i] = h_(i+1).  The first n - 1 elements are the coefficients of
+ *    comb / (X - point); quotient[n - 1] = h_n = 0.
+ *  - remainder (optional): a 32-byte HOST value, h_0 = comb(point).
+ * `polys`, `lens`, `coeffs` (count x 32 bytes, Montgomery form) and `point` are HOST arrays, read during the call and not retained; on_device
+ * governs `quotient` and every polys[k], as in snarkvm_hip_fr_lincomb.  A pointer may be NULL iff its length is 0.
+ * The combination is formed once and parked in quotient[i]; the up sweep folds it into block values, the down sweep replaces it by h_(i+1)
+ * in place (every thread writes only the indices it has just read).  Against snarkvm_hip_fr_lincomb per combination, one more to fold them and
+ * snarkvm_hip_fr_divide_by_linear - L + 4 launches, K + 2L + 4 vector passes, L + 1 intermediate vectors, (K + L + 2) n products for L
+ * combinations over K members - a single member is combined inside the sweep: 3 launches, 4 passes, 3 n products.  A thread of the sweep
+ * reads its own run of consecutive coefficients, which does not coalesce, so of two or more members all go through accumulating fr_lincomb
+ * launches into the quotient buffer first (24 per launch, FR_LINCOMB_CHUNK; measured faster at every shape than forming the combination
+ * inside the sweep, profiles/fr_open_fold.md) and the sweep finds the combination parked there: 4 launches up to K = 24, K + 4 passes,
+ * (K + 2) n products, still no vector beside the quotient.  Without a quotient there is no buffer to accumulate in: every table of 24
+ * members gets an up sweep of its own and the values are added.  The route is the one
+ * snarkvm_hip_fr_divide_by_linear takes for n: three launches with a scan inside every workgroup for 2048 <= n <= 2^20 and a quotient, the
+ * chunk recursion otherwise.  No atomics, a fixed order of additions: the bytes do not depend on the launch geometry.
+ *  - n == 0: success, a given remainder is set to zero, nothing else is touched, no device is needed.
+ *  - count == 0, or every lens[k] == 0: the quotient is zero-filled, the remainder is zero.
+ *  - Refused with hipErrorInvalidValue before anything is launched, no partial result: lens[k] > n; a missing pointer with a non-zero length;
+ *    a missing `point`; missing `coeffs`, `polys` or `lens` with count > 0; an operand on another device than `quotient`; `quotient`
+ *    overlapping any operand, its own start included (no in-place form: the quotient buffer is the pass's only workspace).  Operands may
+ *    overlap each other and repeat; they are never written.
+ *  - With on_device = 1 inside a snarkvm_hip_scope the call is only enqueued and the remainder is delivered by snarkvm_hip_scope_end, like
+ *    that of snarkvm_hip_fr_divide_by_linear.
+ *  - With on_device = 0 the operands are staged into one lane buffer (n + sum lens[k] elements): one upload each, one download.
+ *  - Workspace: the lane's scratch for block values only; a repeated call grows nothing (snarkvm_hip_alloc_stats). */
+RustError snarkvm_hip_fr_open_fold(void *quotient, void *remainder, size_t n, size_t count, const void *const *polys, const size_t *lens,
+                                   const void *coeffs, const void *point, int on_device);
+
 /* Selector fold: the sums of Varuna's round 3 (calculate_lineval_sumcheck_witness, snark/varuna/ahp/prover/round_functions/third.rs:126-327) in
  * one pass.  Member k is a polynomial polys[k] of L_k = lens[k] coefficients, a source domain of n_k = src_sizes[k] elements and a multiplier
  * mu_k = multipliers[k] (combiner * n_k / N).  apply_randomized_selector (ahp/selectors.rs:100-121) scales the member, divides it by X^n_k - 1,
@@ -656,6 +691,18 @@ int snarkvm_hip_selftest_ntt_host(void *inout, uint32_t lg, const int32_t *plan,
  * every launch a loop over i through the kernel's own per-element routine (csrc/poly.hip.h: fr_lincomb_at, Fp::sum_of_products).  0, or -1
  * when the arguments are refused. */
 int snarkvm_hip_selftest_fr_lincomb(void *out, size_t n_out, size_t count, const void *const *polys, const size_t *lens, const void *coeffs);
+/* snarkvm_hip_fr_open_fold over host memory with the CPU in the kernels' place, over a GIVEN geometry: the same validation, operand order and
+ * split into launches, every launch a loop over its threads through the kernels' own per-thread routines (csrc/poly.hip.h: fr_lincomb_at,
+ * fr_open_up_chunk, fr_open_down_chunk, the scan step and carry routines), a workgroup's exchanges through LDS as loops over its threads.
+ *   route 1 (a quotient is required): the scan form - workgroups of 256 threads, C >= 1 coefficients per thread, `blocks` workgroups with
+ *           ceil(n / (256 C)) <= blocks <= 257 (a workgroup past the end owns nothing)
+ *   route 0: the chunk recursion - chunks of C >= 2 coefficients at every level, blocks = ceil(ceil(n / C) / 256), the workgroups of level 0
+ * 0, or -1 when the arguments or the geometry are refused.  fr_open_fold_geometry: out5 = {route, C, blocks} of what the device call launches
+ * for n coefficients when a quotient is wanted (without one: always route 0, C = 32), the operands per table (FR_LINCOMB_CHUNK) and the
+ * terms the fused sweep takes at most (FR_OPEN_FUSE). */
+int snarkvm_hip_selftest_fr_open_fold(void *quotient, void *remainder, size_t n, size_t count, const void *const *polys, const size_t *lens,
+                                      const void *coeffs, const void *point, int route, uint32_t C, uint32_t blocks);
+int snarkvm_hip_selftest_fr_open_fold_geometry(size_t n, uint32_t *out5);
 /* snarkvm_hip_fr_selector_fold over host memory with the CPU in the kernels' place: the same validation, member tables and split into launches,
  * every launch a loop over i through the kernel's own per-index routine (csrc/poly.hip.h: fr_selector_at), then the tiling of xg_out.  0, or
  * -1 when the arguments are refused. */

@@ -201,6 +201,21 @@ inline void fr_lincomb(void* out, size_t n_out, const std::vector<DevicePoly>& p
     check(snarkvm_hip_fr_lincomb(out, n_out, pptrs.size(), pptrs.data(), plens.data(), coeffs, on_device ? 1 : 0));
 }
 
+// Opening fold (snarkvm_hip.h: snarkvm_hip_fr_open_fold): comb = sum_k coeffs[k] * polys[k] over n coefficients, formed once; quotient (n elements,
+// all written, or nullptr) = comb / (X - point) with a trailing zero; remainder (32 bytes of HOST memory, or nullptr) = comb(point).  coeffs:
+// polys.size() x 32 bytes of HOST memory, Montgomery form; point: 32 bytes of HOST memory; on_device governs `quotient` and every polys[k].data.
+// No operand is written and none may overlap the quotient.  With on_device inside a Scope the call is only enqueued and the remainder arrives
+// when the Scope ends.
+inline void fr_open_fold(void* quotient, void* remainder, size_t n, const std::vector<DevicePoly>& polys, const void* coeffs, const void* point, bool on_device) {
+    std::vector<const void*> pptrs;
+    std::vector<size_t> plens;
+    for (auto& p : polys) {
+        pptrs.push_back(p.data);
+        plens.push_back(p.len);
+    }
+    check(snarkvm_hip_fr_open_fold(quotient, remainder, n, pptrs.size(), pptrs.data(), plens.data(), coeffs, point, on_device ? 1 : 0));
+}
+
 // The sums of Varuna's round 3 in one device pass (snarkvm_hip.h: snarkvm_hip_fr_selector_fold): member k = members[k] with source domain
 // src_sizes[k] and multiplier multipliers[k] (members.size() x 32 bytes of HOST memory, Montgomery form).  h_out (h_len coefficients): the sum of
 // the scaled quotients by X^n_k - 1; xg_out (target_size coefficients): the sum of the scaled remainders, tiled; sums (members.size() elements):

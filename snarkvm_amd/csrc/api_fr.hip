@@ -691,6 +691,339 @@ int snarkvm_hip_selftest_fr_lincomb(void* out, size_t n_out, size_t count, const
     return 0;
 }
 
+// ---- opening fold: a combination, its quotient by X - point and its value (poly.hip.h: fr_open_up_kernel ... fr_open2_down_kernel) -------
+// What the device call and its host replay share: validation, operand order, the split into launches and the choice of the route.
+static void fr_same_device(lane_t& c, const void* p, const char* what);
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  Nothing has been touched either way.  An empty plan: the
+// combination is zero.  The LAST launch of the plan is the fused sweep, the ones before it are plain fr_lincomb_kernel launches.  With a
+// quotient every launch after the first takes the quotient buffer - the sum so far - back in as its first term (src -1, coefficient one);
+// without one every launch is an up sweep that stands alone, and the values of the launches are added.
+static const char* fr_open_plan(const void* quotient, size_t n, size_t count, const void* const* polys, const size_t* lens, const void* coeffs, const void* point,
+                                std::vector<fr_lincomb_launch_t>& plan) {
+    if (!point) return "missing point";
+    if (count && (!polys || !lens)) return "missing operand list";
+    if (count && !coeffs) return "missing coeffs";
+    struct entry_t {
+        size_t k, len;
+    };
+    std::vector<entry_t> live;
+    const uint8_t* o = (const uint8_t*)quotient;
+    for (size_t k = 0; k < count; k++) {
+        const size_t len = lens[k];
+        if (len > n) return "an operand is longer than n";
+        if (!len) continue;
+        const uint8_t* q = (const uint8_t*)polys[k];
+        if (!q) return "null operand of non-zero length";
+        // the quotient buffer is the pass's only workspace: no operand may touch it, not even start where it starts
+        if (o && q < o + sizeof(fr_mem_t) * n && o < q + sizeof(fr_mem_t) * len) return "quotient overlaps an operand";
+        live.push_back({k, len});
+    }
+    if (live.empty()) return nullptr;
+    std::stable_sort(live.begin(), live.end(), [](const entry_t& a, const entry_t& b) { return a.len > b.len; });
+    size_t at = 0;
+    // one table: the sum so far first (every launch into a quotient buffer but the first), then the members from `at` up to `end`
+    const auto table = [&](size_t end) {
+        fr_lincomb_launch_t L{};
+        int m = 0;
+        if (at && quotient) {
+            L.t.p[0] = (const fr_mem_t*)quotient, L.t.len[0] = n, L.src[0] = -1;
+            for (int l = 0; l < 9; l++) L.t.c[0][l] = FrP::ONE[l];
+            m = 1;
+        }
+        for (; m < FR_LINCOMB_CHUNK && at < end; m++, at++) {
+            const entry_t& e = live[at];
+            const fr_mem_t c_mem = fr_mem_from_host((const uint8_t*)coeffs + sizeof(fr_mem_t) * e.k);
+            const fr_t c = fr_t::load(&c_mem).from_mem_mont();
+            L.t.p[m] = (const fr_mem_t*)polys[e.k], L.t.len[m] = e.len, L.src[m] = (int64_t)e.k;
+            for (int l = 0; l < 9; l++) L.t.c[m][l] = c.v[l];
+        }
+        L.t.count = m;
+        plan.push_back(L);
+    };
+    // with a quotient the fused sweep takes FR_OPEN_FUSE terms at most (poly.hip.h: one), the sum of the other members among them: those go
+    // through plain accumulating launches first
+    const size_t lead = quotient && live.size() > (size_t)FR_OPEN_FUSE ? live.size() - (FR_OPEN_FUSE - 1) : 0;
+    while (at < lead) table(lead);
+    do table(live.size());  // the fused launch (it may hold the sum alone); without a quotient one table after the other
+    while (at < live.size());
+    return nullptr;
+}
+// route 1: the three-launch scan (C coefficients per thread, `blocks` workgroups of HORNER2_B); route 0: the chunk recursion (C = POLY_CHUNK,
+// `blocks` workgroups of 256 at its level 0).  The choice of fr_suffix_horner, which the quotient of a plain division goes through.
+struct fr_open_geometry_t {
+    int route;
+    uint32_t C;
+    size_t blocks;
+};
+static fr_open_geometry_t fr_open_geometry(size_t n, bool want_quotient) {
+    if (want_quotient && n >= 2048 && n <= ((size_t)1 << 20) && tuning().horner2) {
+        uint32_t C = 8;
+        while (((n + C - 1) / C + HORNER2_B - 1) / HORNER2_B > 256) C *= 2;
+        return {1, C, ((n + C - 1) / C + HORNER2_B - 1) / HORNER2_B};
+    }
+    const size_t T = (n + POLY_CHUNK - 1) / POLY_CHUNK;
+    return {0, (uint32_t)POLY_CHUNK, (T + 255) / 256};
+}
+// the sizes of the levels of the chunk recursion: n, then the chunk values of the level below until one is left (always at least two levels:
+// level 0 is the fused one, and its chunk values exist even for a single coefficient)
+static std::vector<size_t> fr_open_levels(size_t n, size_t chunk) {
+    std::vector<size_t> sizes{n};
+    do sizes.push_back((sizes.back() + chunk - 1) / chunk);
+    while (sizes.back() > 1);
+    return sizes;
+}
+// enqueues the pass on the lane's stream; -> where the value h_0 will be (device memory, the lane's poly[4])
+static const fr_mem_t* fr_open_run(lane_t& c, fr_mem_t* dq, size_t n, const fr_mem_t& z, const std::vector<fr_lincomb_launch_t>& plan) {
+    hipStream_t st = c.stream;
+    const fr_open_geometry_t g = fr_open_geometry(n, dq != nullptr);
+    // a list longer than one table, quotient wanted: the leading tables are plain accumulating passes into the quotient buffer
+    if (dq)
+        for (size_t j = 0; j + 1 < plan.size(); j++) hipLaunchKernelGGL(fr_lincomb_kernel, dim3(fr_grid(n)), dim3(256), 0, st, dq, n, plan[j].t);
+    if (g.route == 1) {
+        const size_t nblocks = g.blocks;
+        c.poly[4].ensure(sizeof(fr_mem_t) * (HORNER2_TAB + nblocks * HORNER2_B + nblocks + 1));
+        fr_mem_t* tab = c.poly[4].as<fr_mem_t>();
+        fr_mem_t* hs = tab + HORNER2_TAB;
+        fr_mem_t* bv = hs + nblocks * HORNER2_B;
+        fr_mem_t* res = bv + nblocks;
+        hipLaunchKernelGGL(fr_horner2_tables_kernel, dim3(1), dim3(HORNER2_B), 0, st, z, tab, g.C);
+        hipLaunchKernelGGL(fr_open2_up_kernel, dim3((unsigned)nblocks), dim3(HORNER2_B), 0, st, dq, n, z, (const fr_mem_t*)tab, hs, bv, g.C, plan.back().t);
+        hipLaunchKernelGGL(fr_open2_down_kernel, dim3((unsigned)nblocks), dim3(HORNER2_B), 0, st, dq, n, z, (const fr_mem_t*)tab, (const fr_mem_t*)hs, (const fr_mem_t*)bv,
+                           g.C, res);
+        HIP_TRY(hipGetLastError());
+        return res;
+    }
+    const std::vector<size_t> sizes = fr_open_levels(n, POLY_CHUNK);
+    const int top = (int)sizes.size() - 1;
+    std::vector<size_t> off(sizes.size(), 0);  // level k >= 1 at cv + off[k]
+    size_t total = 0;
+    for (int k = 1; k <= top; k++) off[k] = total, total += sizes[k];
+    const size_t nl = plan.size();
+    // mult[top + 1] | res | tops[nl] | cv[total]
+    c.poly[4].ensure(sizeof(fr_mem_t) * ((size_t)top + 1 + 1 + nl + total));
+    fr_mem_t* mult = c.poly[4].as<fr_mem_t>();
+    fr_mem_t* res = mult + top + 1;
+    fr_mem_t* tops = res + 1;
+    fr_mem_t* cv = tops + nl;
+    hipLaunchKernelGGL(fr_horner_multipliers_kernel, dim3(1), dim3(1), 0, st, z, mult, top + 1);
+    // level k's chunk values; the single value of the top level goes to `top_at`
+    const auto level = [&](int k, fr_mem_t* top_at) { return k == top ? top_at : cv + off[k]; };
+    const auto up_from = [&](const fr_lincomb_t& t, fr_mem_t* q, fr_mem_t* top_at) {
+        hipLaunchKernelGGL(fr_open_up_kernel, dim3((unsigned)((sizes[1] + 255) / 256)), dim3(256), 0, st, q, n, (const fr_mem_t*)mult, level(1, top_at), sizes[1], t);
+        for (int k = 1; k < top; k++)
+            hipLaunchKernelGGL(fr_horner_up_kernel, dim3((unsigned)((sizes[k + 1] + 255) / 256), 1u), dim3(256), 0, st, (const fr_mem_t*)level(k, top_at), sizes[k],
+                               (const fr_mem_t*)(mult + k), level(k + 1, top_at), sizes[k + 1], (size_t)0, (size_t)0);
+    };
+    if (!dq) {
+        // the value alone: by linearity one up sweep per table, the top values added in list order
+        for (size_t j = 0; j < nl; j++) up_from(plan[j].t, nullptr, tops + j);
+        if (nl > 1) hipLaunchKernelGGL(fr_open_sum_kernel, dim3(1), dim3(1), 0, st, (const fr_mem_t*)tops, (uint32_t)nl, res);
+        HIP_TRY(hipGetLastError());
+        return nl > 1 ? res : tops;
+    }
+    up_from(plan.back().t, dq, tops);
+    // down: every level's chunk values become its suffix sums in place, level 0 turns the parked combination into the quotient
+    for (int k = top - 1; k >= 1; k--)
+        hipLaunchKernelGGL(fr_horner_down_kernel, dim3((unsigned)((sizes[k + 1] + 255) / 256), 1u), dim3(256), 0, st, (const fr_mem_t*)level(k, tops), sizes[k],
+                           (const fr_mem_t*)(mult + k), (const fr_mem_t*)level(k + 1, tops), sizes[k + 1], level(k, tops), 0, (fr_mem_t*)nullptr, (size_t)0, (size_t)0,
+                           (size_t)0);
+    hipLaunchKernelGGL(fr_open_down_kernel, dim3((unsigned)((sizes[1] + 255) / 256)), dim3(256), 0, st, dq, n, (const fr_mem_t*)mult, (const fr_mem_t*)level(1, tops),
+                       sizes[1], res);
+    HIP_TRY(hipGetLastError());
+    return res;
+}
+RustError snarkvm_hip_fr_open_fold(void* quotient, void* remainder, size_t n, size_t count, const void* const* polys, const size_t* lens, const void* coeffs,
+                                   const void* point, int on_device) {
+    if (n == 0) {
+        if (remainder) memset(remainder, 0, sizeof(fr_mem_t));
+        return ok();
+    }
+    std::vector<fr_lincomb_launch_t> plan;
+    if (const char* why = fr_open_plan(quotient, n, count, polys, lens, coeffs, point, plan)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_open_fold: ") + why);
+    if (plan.empty() && !(on_device && quotient)) {  // the zero combination, nothing to write on a device
+        if (quotient) memset(quotient, 0, sizeof(fr_mem_t) * n);
+        if (remainder) memset(remainder, 0, sizeof(fr_mem_t));
+        return ok();
+    }
+    const void* anchor = quotient ? quotient : (const void*)plan[0].t.p[0];
+    API_BEGIN_DEV(device_for(anchor, on_device ? 1 : 0))
+    fr_mem_t* dq = (fr_mem_t*)quotient;
+    if (on_device) {
+        for (size_t k = 0; k < count; k++)
+            if (lens[k]) fr_same_device(c, polys[k], "fr_open_fold: an operand lives on another device than the quotient (or the first operand)");
+    } else {
+        // host operands: one lane buffer holds the quotient and, behind it, every operand; one upload each, one download
+        size_t total = quotient ? n : 0;
+        for (size_t k = 0; k < count; k++) total += lens[k];
+        c.poly[0].ensure(sizeof(fr_mem_t) * total);
+        fr_mem_t* next = c.poly[0].as<fr_mem_t>();
+        if (quotient) dq = next, next += n;
+        std::vector<const fr_mem_t*> staged(count, nullptr);
+        for (size_t k = 0; k < count; k++) {
+            if (!lens[k]) continue;
+            HIP_TRY(hipMemcpyAsync(next, polys[k], sizeof(fr_mem_t) * lens[k], hipMemcpyHostToDevice, c.stream));
+            staged[k] = next;
+            next += lens[k];
+        }
+        for (fr_lincomb_launch_t& L : plan)
+            for (int m = 0; m < L.t.count; m++) L.t.p[m] = L.src[m] < 0 ? dq : staged[(size_t)L.src[m]];
+    }
+    if (plan.empty()) {  // device quotient of the zero combination
+        HIP_TRY(hipMemsetAsync(dq, 0, sizeof(fr_mem_t) * n, c.stream));
+        if (remainder) memset(remainder, 0, sizeof(fr_mem_t));
+    } else {
+        const fr_mem_t* dres = fr_open_run(c, dq, n, fr_mem_from_host(point), plan);
+        if (dq) fr_finish_out(c, dq, quotient, n, on_device);
+        // device operands inside a scope: delivered by snarkvm_hip_scope_end; host operands: the call waits below, the value is there on return
+        if (remainder) c.host_result(remainder, dres, sizeof(fr_mem_t), on_device != 0);
+    }
+    fr_call_done(c, on_device);
+    API_END
+}
+// what the call launches for n coefficients when a quotient is wanted: out5 = {route (1: scan, 0: chunk recursion), coefficients per thread C,
+// workgroups of the fused launches, operands per table (FR_LINCOMB_CHUNK), terms of the fused sweep at most (FR_OPEN_FUSE)}.  Without a
+// quotient the route is always 0.
+int snarkvm_hip_selftest_fr_open_fold_geometry(size_t n, uint32_t* out5) {
+    if (!out5) return -1;
+    const fr_open_geometry_t g = fr_open_geometry(n ? n : 1, true);
+    out5[0] = (uint32_t)g.route, out5[1] = g.C, out5[2] = (uint32_t)g.blocks, out5[3] = FR_LINCOMB_CHUNK, out5[4] = FR_OPEN_FUSE;
+    return 0;
+}
+// The same call on host memory with the CPU in the kernels' place, over a GIVEN geometry: the same plan, every launch a loop over its threads
+// through the kernels' own per-thread routines, a workgroup's LDS exchanges as loops over its threads.
+//   route 1 (needs a quotient): workgroups of HORNER2_B threads, C >= 1 coefficients per thread, ceil(n / (HORNER2_B C)) <= blocks <= 257
+//   route 0: chunks of C >= 2 coefficients at every level, blocks = the workgroups of 256 threads of level 0 = ceil(ceil(n / C) / 256)
+// 0, or -1 when the arguments or the geometry are refused.
+int snarkvm_hip_selftest_fr_open_fold(void* quotient, void* remainder, size_t n, size_t count, const void* const* polys, const size_t* lens, const void* coeffs,
+                                      const void* point, int route, uint32_t C, uint32_t blocks) {
+    if (n == 0) {
+        if (remainder) memset(remainder, 0, sizeof(fr_mem_t));
+        return 0;
+    }
+    std::vector<fr_lincomb_launch_t> plan;
+    if (fr_open_plan(quotient, n, count, polys, lens, coeffs, point, plan)) return -1;
+    if (route == 1) {
+        if (!quotient || C < 1 || blocks > 257 || (size_t)blocks * HORNER2_B * C < n || (n - 1) / C > 0xFFFFFFFFull) return -1;
+    } else if (route == 0) {
+        if (C < 2 || (size_t)blocks != ((n + C - 1) / C + 255) / 256) return -1;
+    } else {
+        return -1;
+    }
+    fr_mem_t* q = (fr_mem_t*)quotient;
+    fr_mem_t res;
+    fr_t::zero().store(&res);
+    if (plan.empty()) {
+        if (q) memset(q, 0, sizeof(fr_mem_t) * n);
+        if (remainder) memcpy(remainder, &res, sizeof res);
+        return 0;
+    }
+    if (q)
+        for (size_t j = 0; j + 1 < plan.size(); j++)
+            for (size_t i = 0; i < n; i++) fr_lincomb_at(plan[j].t, i).store(&q[i]);
+    const fr_mem_t z = fr_mem_from_host(point);
+    const fr_t m = fr_t::load(&z).from_mem_mont();
+    if (route == 1) {
+        const uint32_t B = HORNER2_B;
+        // fr_horner2_tables_kernel: step[j] = m^(C 2^j), pw[j] = m^(C j), pwB[j] = m^(256 C j)
+        const fr_t mC = m.pow_u64(C), mB = mC.pow_u64(B);
+        std::vector<fr_t> step(8), pw(B + 1), pwB(B);
+        for (uint32_t t = 0; t < B; t++) pw[t] = mC.pow_u64(t), pwB[t] = mB.pow_u64(t);
+        pw[B] = mB;
+        for (uint32_t j = 0; j < 8; j++) step[j] = mC.pow_u64(1u << j);
+        // up: hs and bv pass through memory, as on the device
+        std::vector<fr_mem_t> hs((size_t)blocks * B), bv(blocks);
+        for (uint32_t b = 0; b < blocks; b++) {
+            std::vector<fr_t> h(B);
+            for (uint32_t t = 0; t < B; t++) {
+                const size_t lo0 = ((size_t)b * B + t) * C, lo = lo0 < n ? lo0 : n, hi = lo + C < n ? lo + C : n;
+                h[t] = fr_open_up_chunk(plan.back().t, q, m, lo, hi);
+            }
+            for (int j = 0; j < 8; j++) {
+                const std::vector<fr_t> sh = h;  // what the workgroup put into LDS before the barrier
+                for (uint32_t t = 0; t + (1u << j) < B; t++) h[t] = fr_open_scan_step(sh[t], step[j], sh[t + (1u << j)]);
+            }
+            for (uint32_t t = 0; t < B; t++) h[t].store(&hs[(size_t)b * B + t]);
+            h[0].store(&bv[b]);
+        }
+        for (uint32_t b = 0; b < blocks; b++) {
+            std::vector<fr_t> term(B, fr_t::zero());
+            for (uint32_t t = 0; t < B; t++)
+                if (b + 1 + t < blocks) term[t] = fr_open_carry_term(pwB[t], fr_t::load(&bv[b + 1 + t]));
+            for (uint32_t off = B / 2; off >= 1; off >>= 1) {
+                const std::vector<fr_t> sh = term;
+                for (uint32_t t = 0; t < off; t++) term[t] = sh[t] + sh[t + off];
+            }
+            const fr_t carry = term[0];
+            for (uint32_t t = 0; t < B; t++) {
+                const size_t lo = ((size_t)b * B + t) * C;
+                if (lo >= n) continue;
+                const size_t hi = lo + C < n ? lo + C : n;
+                fr_t h = fr_open_thread_carry(pw[B - 1 - t], carry);
+                if (t + 1 < B) h = h + fr_t::load(&hs[(size_t)b * B + t + 1]);
+                h = fr_open_down_chunk(q, m, h, lo, hi);
+                if (lo == 0) h.store(&res);
+            }
+        }
+    } else {
+        const std::vector<size_t> sizes = fr_open_levels(n, C);
+        const int top = (int)sizes.size() - 1;
+        std::vector<fr_t> mult(top + 1);  // fr_horner_multipliers_kernel: mult[k] = m^(C^k), through memory form
+        {
+            fr_t p = m;
+            for (int k = 0; k <= top; k++) {
+                fr_mem_t mm;
+                p.to_mem_mont().store(&mm);
+                mult[k] = fr_t::load(&mm).from_mem_mont();
+                p = p.pow_u64(C);
+            }
+        }
+        const auto chunk_hi = [&](size_t t, size_t cur) { return (t + 1) * (size_t)C < cur ? (t + 1) * (size_t)C : cur; };
+        // level k >= 1 of one up sweep; -> the levels' values, cv[top] the single top value
+        const auto up_from = [&](const fr_lincomb_t& tb, fr_mem_t* qq) {
+            std::vector<std::vector<fr_mem_t>> cv(top + 1);
+            cv[1].resize(sizes[1]);
+            for (size_t t = 0; t < sizes[1]; t++) fr_open_up_chunk(tb, qq, mult[0], t * C, chunk_hi(t, n)).store(&cv[1][t]);
+            for (int k = 1; k < top; k++) {
+                cv[k + 1].resize(sizes[k + 1]);
+                for (size_t t = 0; t < sizes[k + 1]; t++) {  // fr_horner_up_kernel
+                    fr_t acc = fr_t::zero();
+                    for (size_t i = chunk_hi(t, sizes[k]); i-- > t * C;) acc = fr_t::load(&cv[k][i]) + mult[k] * acc;
+                    acc.store(&cv[k + 1][t]);
+                }
+            }
+            return cv;
+        };
+        if (!q) {
+            fr_t s = fr_t::zero();
+            for (size_t j = 0; j < plan.size(); j++) {
+                const fr_t v = fr_t::load(&up_from(plan[j].t, nullptr)[top][0]);
+                if (plan.size() == 1)
+                    v.store(&res);
+                else
+                    s = s + v;
+            }
+            if (plan.size() > 1) s.store(&res);
+        } else {
+            std::vector<std::vector<fr_mem_t>> cv = up_from(plan.back().t, q);
+            for (int k = top - 1; k >= 1; k--)
+                for (size_t t = 0; t < sizes[k + 1]; t++) {  // fr_horner_down_kernel, shift 0, in place
+                    fr_t acc = t + 1 < sizes[k + 1] ? fr_t::load(&cv[k + 1][t + 1]) : fr_t::zero();
+                    for (size_t i = chunk_hi(t, sizes[k]); i-- > t * C;) {
+                        acc = fr_t::load(&cv[k][i]) + mult[k] * acc;
+                        acc.store(&cv[k][i]);
+                    }
+                }
+            for (size_t t = 0; t < sizes[1]; t++) {
+                const fr_t h_hi = t + 1 < sizes[1] ? fr_t::load(&cv[1][t + 1]) : fr_t::zero();
+                const fr_t h = fr_open_down_chunk(q, mult[0], h_hi, t * C, chunk_hi(t, n));
+                if (t == 0) h.store(&res);
+            }
+        }
+    }
+    if (remainder) memcpy(remainder, &res, sizeof res);
+    return 0;
+}
+
 // ---- selector fold: Varuna round 3 (poly.hip.h: fr_selector_fold_kernel) ---------------------------------------------------
 // What the device call and its host replay share: validation, the member tables and the split into launches.  src[m]: the caller's index
 // of table entry m (its pointers are bound later: to the caller's memory, or to the staged copies).

@@ -14,6 +14,7 @@
 //   fr_witness_evals_kernel     w's evaluations on the variable domain: the interleaving gather minus x     first.rs:127-161 (round 1)
 //   fr_rowcheck_fold_kernel     sum_k mu_k (a_k b_k - c_k) and the per-member counts of a_k b_k != c_k      second.rs:76-142, selectors.rs:88-99 (round 2)
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
+//   fr_open(2)_up/down_kernel   (sum_k c_k p_k) / (X - z) and its value at z, the combination formed once  sonic_pc/mod.rs:286-342, varuna.rs:572-605
 //   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
 //   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
 //   fr_spmv_seg_kernel          y = M x over a registered CSR matrix, segment by segment  round_functions/mod.rs:131-188 (z_M), third.rs:303-306 (M(alpha, .))
@@ -326,6 +327,134 @@ static __global__ void __launch_bounds__(256) fr_lincomb_kernel(fr_mem_t* out, s
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t st = (size_t)gridDim.x * blockDim.x;
     for (; i < n_out; i += st) fr_lincomb_at(t, i).store(&out[i]);
+}
+
+// ---- opening fold: the combination and its quotient by X - m in one sweep up and one sweep down --------------------------------------
+// comb[i] = sum_k c_k p_k[i] is formed ONCE, in the up sweep of the suffix Horner sums above: a thread evaluates fr_lincomb_at over its
+// chunk, parks every comb[i] in q[i] and folds it into its chunk value.  The down sweep then runs IN PLACE on q with the ownership shifted
+// by one: walking downwards from its incoming h_hi, a thread reads comb[i] from q[i], writes q[i] = h_(i+1) - its running value BEFORE the
+// step - and forms h_i.  A thread writes only indices of its own chunk [lo, hi), each after its one read of it, and nobody else touches
+// them: no hazard across threads, no staging; q[n - 1] = h_n = 0 falls out for the thread that owns the end, and the thread that owns
+// index 0 is left with h_0 = comb(m), the remainder.  q == nullptr: the up sweep alone, nothing is stored (the value only).
+// q may be the START of one table entry (a list longer than FR_LINCOMB_CHUNK takes the sum so far back in as a term): index i of every
+// entry is read before q[i] is written.
+// A thread of the up sweep walks its own C (or POLY_CHUNK) consecutive coefficients, so its reads of a member are 32-byte pieces 32 C bytes
+// away from its neighbour's, and a proof-sized polynomial gives the sweep a quarter of the chip's lanes at most: forming a long combination
+// there loses to fr_lincomb_kernel's coalesced full grid.  Measured (profiles/fr_open_fold.md) with the sweep taking up to 24, 12, 6 and 1
+// terms - of a longer list the launcher sends the other members through accumulating fr_lincomb_kernel launches into q first and the sweep
+// takes that sum in as its first term: with 24 (everything in the sweep) 10 and 19 members ran at 0.80 - 0.93 of the speed of the chain of
+// calls this pass replaces, with 12 at 0.91 - 0.99, with 6 at 1.01 - 1.24, with 1 at 1.18 - 1.44 (1.26 - 1.54 since the sweep reads the
+// parked sum as it is, below); every shape was fastest with 1.  So
+// FR_OPEN_FUSE = 1: a single member is combined inside the sweep (three launches); of two or more ALL go through fr_lincomb_kernel, and the
+// sweep finds the combination parked in q (one launch more, K + 4 vector passes, still formed once and divided in place, no vector beside
+// q).  Without a quotient there is no q to park in: the sweep takes a whole table (fr_open_plan).
+static constexpr int FR_OPEN_FUSE = 1;
+static_assert(FR_OPEN_FUSE >= 1 && FR_OPEN_FUSE <= FR_LINCOMB_CHUNK, "the fused sweep takes one table");
+// The per-thread routines: the kernels below and the host replay (snarkvm_hip_selftest_fr_open_fold) both call them.
+SV_HD fr_t fr_open_up_chunk(const fr_lincomb_t& t, fr_mem_t* q, const fr_t& m, size_t lo, size_t hi) {
+    // the table holds the parked sum alone (every member has gone through fr_lincomb_kernel): comb[i] is in q[i] already
+    const bool parked = q && t.count == 1 && t.p[0] == q;
+    fr_t h = fr_t::zero();
+    for (size_t i = hi; i > lo;) {
+        i--;
+        const fr_t x = parked ? fr_t::load(&q[i]) : fr_lincomb_at(t, i);
+        if (q && !parked) x.store(&q[i]);
+        h = x + m * h;
+    }
+    return h;
+}
+// h: h_hi on entry; q[i] = h_(i+1) for lo <= i < hi on return, which is h_lo
+SV_HD fr_t fr_open_down_chunk(fr_mem_t* q, const fr_t& m, fr_t h, size_t lo, size_t hi) {
+    for (size_t i = hi; i > lo;) {
+        i--;
+        const fr_t x = fr_t::load(&q[i]);
+        h.store(&q[i]);
+        h = x + m * h;
+    }
+    return h;
+}
+// one Kogge-Stone step of the workgroup scan (fr_horner2_up_kernel), and the pieces of a workgroup's incoming carry (fr_horner2_down_kernel)
+SV_HD fr_t fr_open_scan_step(const fr_t& h, const fr_t& step, const fr_t& behind) { return h + step * behind; }
+SV_HD fr_t fr_open_carry_term(const fr_t& pw_block, const fr_t& block_value) { return pw_block * block_value; }
+SV_HD fr_t fr_open_thread_carry(const fr_t& pw_thread, const fr_t& carry) { return pw_thread * carry; }
+
+// level 0 of the chunk recursion (fr_horner_up_kernel / fr_horner_down_kernel), fused: cv[t] = the value of chunk t of the combination
+static __global__ void __launch_bounds__(256) fr_open_up_kernel(fr_mem_t* q, size_t n, const fr_mem_t* __restrict__ m_mem, fr_mem_t* __restrict__ cv, size_t T,
+                                                                fr_lincomb_t t) {
+    const size_t th = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (th >= T) return;
+    const fr_t m = fr_t::load(m_mem).from_mem_mont();
+    const size_t lo = th * POLY_CHUNK;
+    const size_t hi = (lo + POLY_CHUNK < n) ? lo + POLY_CHUNK : n;
+    fr_open_up_chunk(t, q, m, lo, hi).store(&cv[th]);
+}
+// carry[t + 1] = h at the first index of chunk t + 1 (nullptr when there is a single chunk); *first = h_0
+static __global__ void __launch_bounds__(256) fr_open_down_kernel(fr_mem_t* q, size_t n, const fr_mem_t* __restrict__ m_mem, const fr_mem_t* __restrict__ carry, size_t T,
+                                                                  fr_mem_t* __restrict__ first) {
+    const size_t th = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (th >= T) return;
+    const fr_t m = fr_t::load(m_mem).from_mem_mont();
+    const size_t lo = th * POLY_CHUNK;
+    const size_t hi = (lo + POLY_CHUNK < n) ? lo + POLY_CHUNK : n;
+    const fr_t h_hi = (carry && th + 1 < T) ? fr_t::load(&carry[th + 1]) : fr_t::zero();
+    const fr_t h = fr_open_down_chunk(q, m, h_hi, lo, hi);
+    if (th == 0 && first) h.store(first);
+}
+// first[0] = vals[0] + vals[1] + ... in list order (the values of the launches of a member list longer than one table, evaluation only)
+static __global__ void fr_open_sum_kernel(const fr_mem_t* __restrict__ vals, uint32_t count, fr_mem_t* __restrict__ first) {
+    if (blockIdx.x | threadIdx.x) return;
+    fr_t s = fr_t::zero();
+    for (uint32_t k = 0; k < count; k++) s = s + fr_t::load(&vals[k]);
+    s.store(first);
+}
+// the scan form (fr_horner2_up_kernel / fr_horner2_down_kernel over the tables of fr_horner2_tables_kernel), fused
+static __global__ void __launch_bounds__(HORNER2_B) fr_open2_up_kernel(fr_mem_t* q, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab, fr_mem_t* __restrict__ hs,
+                                                                       fr_mem_t* __restrict__ bv, uint32_t C, fr_lincomb_t t) {
+    __shared__ uint32_t sh[9 * HORNER2_B];
+    const uint32_t th = threadIdx.x;
+    const fr_t m = fr_t::load(&m_mem).from_mem_mont();
+    const size_t lo0 = ((size_t)blockIdx.x * HORNER2_B + th) * C;
+    const size_t lo = lo0 < n ? lo0 : n;
+    const size_t hi = lo + C < n ? lo + C : n;
+    fr_t h = fr_open_up_chunk(t, q, m, lo, hi);
+#pragma unroll 1
+    for (int j = 0; j < 8; j++) {
+        horner2_lds_put(sh, th, h);
+        __syncthreads();
+        if (th + (1u << j) < HORNER2_B) h = fr_open_scan_step(h, fr_t::load(&tab[j]), horner2_lds_get(sh, th + (1u << j)));
+        __syncthreads();
+    }
+    h.store(&hs[(size_t)blockIdx.x * HORNER2_B + th]);
+    if (th == 0) h.store(&bv[blockIdx.x]);
+}
+// nblocks <= 256 + 1
+static __global__ void __launch_bounds__(HORNER2_B) fr_open2_down_kernel(fr_mem_t* q, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab,
+                                                                         const fr_mem_t* __restrict__ hs, const fr_mem_t* __restrict__ bv, uint32_t C,
+                                                                         fr_mem_t* __restrict__ first) {
+    __shared__ uint32_t sh[9 * HORNER2_B];
+    const uint32_t th = threadIdx.x, b = blockIdx.x, nblocks = gridDim.x;
+    const fr_t m = fr_t::load(&m_mem).from_mem_mont();
+    // carry = h at the first coefficient of block b + 1 = sum_(s > b) bv[s] m^(256 C (s - b - 1)): one term per thread, then a tree of sums
+    fr_t term = fr_t::zero();
+    if (b + 1 + th < nblocks) term = fr_open_carry_term(fr_t::load(&tab[8 + 257 + th]), fr_t::load(&bv[b + 1 + th]));
+#pragma unroll 1
+    for (uint32_t off = HORNER2_B / 2; off >= 1; off >>= 1) {
+        horner2_lds_put(sh, th, term);
+        __syncthreads();
+        if (th < off) term = term + horner2_lds_get(sh, th + off);
+        __syncthreads();
+    }
+    horner2_lds_put(sh, th, term);
+    __syncthreads();
+    const fr_t carry = horner2_lds_get(sh, 0);
+    const size_t lo = ((size_t)b * HORNER2_B + th) * C;
+    if (lo >= n) return;
+    const size_t hi = lo + C < n ? lo + C : n;
+    // h behind this thread's coefficients: the block's own suffix sum from thread th + 1 on, plus the carry moved across the threads in between
+    fr_t h = fr_open_thread_carry(fr_t::load(&tab[8 + (HORNER2_B - 1 - th)]), carry);
+    if (th + 1 < HORNER2_B) h = h + fr_t::load(&hs[(size_t)b * HORNER2_B + th + 1]);
+    h = fr_open_down_chunk(q, m, h, lo, hi);
+    if (lo == 0 && first) h.store(first);
 }
 
 // ---- X^D - 1 -------------------------------------------------------------------------------------------------------

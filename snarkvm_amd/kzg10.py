@@ -106,6 +106,27 @@ def check_hiding_bound(hiding_poly_degree, num_powers):
         raise PCError(f"HidingBoundToolarge: hiding_poly_degree {hiding_poly_degree}, num_powers {num_powers}")
 
 
+def resident_range(trimmed_len, leading_zeros, num_powers):
+    """What `commit` asks a host vector, answered from the support the device reported for a resident one (`snarkvm_hip_fr_support`):
+    check_degree_is_too_large on the trimmed degree (mod.rs:407-415) and skip_leading_zeros (mod.rs:455-467).  -> (lz, n0): the MSM runs
+    over powers[lz .. lz + n0) and the scalars from element lz on; (0, 0) for the zero polynomial."""
+    if trimmed_len > num_powers:
+        raise PCError(f"TooManyCoefficients: {trimmed_len} > {num_powers}")
+    return (leading_zeros, trimmed_len - leading_zeros) if trimmed_len else (0, 0)
+
+
+def hiding_side(powers, point, randomness, hiding_witness_polynomial):
+    """The blinding half of an opening (mod.rs:251-262): -> (random_v = blinding_p(point), the hiding witness' coefficients for the MSM over
+    the gamma powers); (None, no coefficients) when the opening is not hiding."""
+    if hiding_witness_polynomial is None:
+        return None, np.zeros((0, 4), dtype=np.uint64)
+    random_v = poly.evaluate(randomness.blinding_polynomial, point)  # blinding_p.evaluate(point), mod.rs:254
+    blind = np.ascontiguousarray(hiding_witness_polynomial, dtype=np.uint64).reshape(-1, 4)  # untrimmed: convert_to_bigints(&coeffs)
+    if blind.shape[0] > powers.powers_of_beta_times_gamma_g.shape[0]:
+        raise PCError("HidingBoundToolarge")
+    return random_v, blind
+
+
 class KZGProof:
     """data_structures.rs:395-430: w = commitment to the witness polynomial (G1Affine record),
     random_v = evaluation of the blinding polynomial at the point ((1, 4) Montgomery limbs) or None."""
@@ -198,11 +219,9 @@ class KZG10:
         ptr = int(getattr(d_coeffs, "ptr", d_coeffs))
         trimmed_len, lz, _ = (int(x) for x in plugin.fr_support_device(ptr, n))
         degree = max(trimmed_len, 1) - 1
-        if trimmed_len and degree + 1 > powers.size():  # check_degree_is_too_large (mod.rs:407-415)
-            raise PCError(f"TooManyCoefficients: {degree + 1} > {powers.size()}")
+        lz, n0 = resident_range(trimmed_len, lz, powers.size())
         if degree_bound is not None and degree_bound < degree:  # check_degrees_and_bounds (mod.rs:439)
             raise PCError(f"IncorrectDegreeBound: poly_degree {degree}, degree_bound {degree_bound}")
-        n0 = trimmed_len - lz if trimmed_len else 0
         randomness = KZGRandomness.empty()
         if hiding_bound is not None:
             if rng is None:
@@ -272,13 +291,7 @@ class KZG10:
             raise PCError(f"TooManyCoefficients: {degree + 1} > {powers.size()}")
         nz = np.nonzero(witness.any(axis=1))[0]
         lz, plain = (0, witness[:0]) if nz.size == 0 else (int(nz[0]), witness[int(nz[0]):])
-        random_v = None
-        blind = np.zeros((0, 4), dtype=np.uint64)
-        if hiding_witness_polynomial is not None:
-            random_v = poly.evaluate(randomness.blinding_polynomial, point)  # blinding_p.evaluate(point), mod.rs:254
-            blind = np.ascontiguousarray(hiding_witness_polynomial, dtype=np.uint64).reshape(-1, 4)  # untrimmed: convert_to_bigints(&coeffs)
-            if blind.shape[0] > powers.powers_of_beta_times_gamma_g.shape[0]:
-                raise PCError("HidingBoundToolarge")
+        random_v, blind = hiding_side(powers, point, randomness, hiding_witness_polynomial)
         scalars = np.concatenate([plain, blind]) if blind.shape[0] else plain
         out = np.zeros(1, dtype=G1_PROJECTIVE)
         _lib.check(_lib.lib().snarkvm_hip_msm_registered_ex(

@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -88,6 +88,29 @@ def fr_lincomb_device(d_out, n_out, d_polys, lens, coeffs):
     pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
     pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
     _lib.check(_lib.lib().snarkvm_hip_fr_lincomb(int(d_out) if d_out else None, int(n_out), k, pp, pl, _ptr(cs), 1))
+
+
+def fr_open_fold_device(d_quot, n, d_polys, lens, coeffs, point, remainder=True):
+    """Extension (no reference counterpart): the opening fold over vectors that live in device memory (`snarkvm_hip_fr_open_fold`, on_device = 1).
+    With comb[i] = sum_k coeffs[k] * d_polys[k][i] for i < n (d_polys[k] counts as zero from lens[k] <= n on), formed once:
+        d_quot[i] = sum_{j > i} comb[j] * point^(j - i - 1)   for i < n: comb / (X - point) in the first n - 1 elements, then a zero
+                    (skipped when d_quot is None: the value alone)
+        value     = comb(point)                                (skipped with remainder=False)
+    coeffs: (k, 4) Montgomery limbs on the host, point: (4,).  -> the value as a (1, 4) array, or None.  No operand is written and none may
+    overlap d_quot.  Inside a scope the call is only enqueued and the returned array is filled when the scope ends: keep it alive until then."""
+    k = len(d_polys)
+    if len(lens) != k:
+        raise ValueError("length mismatch")
+    cs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4) if k else np.zeros((0, 4), dtype=np.uint64)
+    if cs.shape[0] != k:
+        raise ValueError("length mismatch")
+    z = _fr_scalar(point)
+    pp = (ctypes.c_void_p * max(1, k))(*[int(p) if p else None for p in d_polys])
+    pl = (ctypes.c_size_t * max(1, k))(*[int(x) for x in lens])
+    out = np.zeros((1, 4), dtype=np.uint64) if remainder else None
+    _lib.check(_lib.lib().snarkvm_hip_fr_open_fold(int(d_quot) if d_quot else None, _ptr(out) if remainder else None, int(n), k, pp, pl, _ptr(cs) if k else None,
+                                                   _ptr(z), 1))
+    return out
 
 
 FR_SELECTOR_CHUNK = 24  # members per kernel launch of snarkvm_hip_fr_selector_fold (include/snarkvm_hip.h; csrc/poly.hip.h FR_SELECTOR_CHUNK)

@@ -72,6 +72,24 @@ def lincomb(coeffs, polys):
     return trim(out)
 
 
+def open_fold(coeffs, polys, point):
+    """(quotient, value) of (sum_k coeffs[k] * polys[k]) / (X - point) in one sweep up and one down (`snarkvm_hip_fr_open_fold`): the combination
+    is formed once and never leaves the device.  The same values as `divide_by_linear(lincomb(coeffs, polys), point)` (sonic_pc/mod.rs:286-342
+    into kzg10/mod.rs:213-236); the quotient is trimmed like a DensePolynomial, the value is (1, 4)."""
+    polys = [_v(p) for p in polys]
+    k = len(polys)
+    cs = _v(coeffs) if k else np.zeros((0, 4), dtype=np.uint64)
+    if cs.shape[0] != k:
+        raise ValueError("length mismatch")
+    n = max([p.shape[0] for p in polys] + [0])
+    q = np.zeros((n, 4), dtype=np.uint64)
+    rem = np.zeros((1, 4), dtype=np.uint64)
+    ptrs = (ctypes.c_void_p * max(1, k))(*[p.ctypes.data if p.shape[0] else None for p in polys])
+    lens = (ctypes.c_size_t * max(1, k))(*[p.shape[0] for p in polys])
+    _lib.check(_lib.lib().snarkvm_hip_fr_open_fold(_p(q) if n else None, _p(rem), n, k, ptrs, lens, _p(cs) if k else None, _p(_v(point)), 0))
+    return trim(q), rem
+
+
 def selector_fold(polys, src_sizes, multipliers, target_size, h_len=None, want="hxs"):
     """The sums of Varuna's round 3 over host arrays in ONE device pass (`snarkvm_hip_fr_selector_fold`): per member k the reference scales
     polys[k] by multipliers[k], divides by X^n_k - 1 (n_k = src_sizes[k]), multiplies the remainder by X^target_size - 1 and divides by X^n_k - 1

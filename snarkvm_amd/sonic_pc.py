@@ -49,6 +49,28 @@ class LabeledPolynomial:
         return self.hiding_bound is not None
 
 
+class ResidentPolynomial:
+    """A labelled polynomial whose coefficients live in device memory and stay there: `d_coeffs` is a device pointer (an int) or a
+    `devmem.HipMem`, `n` the number of coefficients the caller vouches for.  Nothing is downloaded to find the degree: `n - 1` stands in
+    for it as its UPPER bound in `check_degrees_and_bounds`, and every pass reads exactly n elements.  A caller whose buffer is padded (a
+    full-domain product fills 2^lg elements) passes the trimmed length it already has from `snarkvm_hip_fr_support` - a padded `n` above
+    `max_degree + 1` is refused with TooManyCoefficients where a trimmed one would pass."""
+
+    def __init__(self, label, d_coeffs, n, degree_bound=None, hiding_bound=None):
+        self.label = label
+        self.ptr = int(getattr(d_coeffs, "ptr", d_coeffs)) if n else 0
+        self.n = int(n)
+        self.degree_bound = degree_bound
+        self.hiding_bound = hiding_bound
+        self._owner = d_coeffs  # a HipMem stays alive as long as its polynomial
+
+    def degree(self):  # the upper bound
+        return max(self.n - 1, 0)
+
+    def is_hiding(self):
+        return self.hiding_bound is not None
+
+
 class LabeledEvaluations:
     """`PolynomialWithBasis::Lagrange`: evaluations over a power-of-two domain, committed in the Lagrange basis."""
 
@@ -268,28 +290,146 @@ class SonicKZG10:
         label_map = {p.label: (p, r) for p, r in zip(polys, rands)}
         lc_polynomials, lc_randomness = [], []
         for lc in linear_combinations:
-            coeffs, cur_polys, cur_rands = [], [], []
-            degree_bound = hiding_bound = None
+            coeffs, members, degree_bound, hiding_bound = _lc_members(lc, label_map)
+            lc_polynomials.append(LabeledPolynomial(lc.label, poly.lincomb(coeffs, [p.coeffs for p, _ in members]), degree_bound, hiding_bound))
+            lc_randomness.append(KZGRandomness(poly.lincomb(coeffs, [r.blinding_polynomial for _, r in members])))
+        return SonicKZG10.batch_open(max_degree, ck, lc_polynomials, query_set, lc_randomness, fs_rng)
+
+    @staticmethod
+    def evaluate_combinations_device(linear_combinations, polynomials, query_set):
+        """The loop of snark/varuna/varuna.rs:583-590 (`get_lc_eval`, ahp/ahp.rs:469-487) over `ResidentPolynomial`s: the value of every queried
+        linear combination at its point, -> {(label, point_name): (4,) Montgomery limbs}.  One `snarkvm_hip_fr_open_fold` without a quotient
+        per (combination, point) - the combination is never materialised - all enqueued in one scope of its own, the values read when it
+        ends; a `ONE` term adds its coefficient on the host (ahp.rs:480-484).  Refused inside a caller's scope.
+        Measured (profiles/fr_open_fold.md): for a single member the call takes 0.75 - 0.81 of the time of `fr_divide_by_linear` without a
+        quotient; for the 10 members of a gamma point at 2^17 coefficients it LOSES to materialising the combination with `fr_lincomb` and
+        evaluating that (0.69 of its speed): without a quotient buffer the combination is formed inside the sweep, 32 coefficients to a
+        thread.  What it saves there is the intermediate vector, not time."""
+        from . import plugin
+
+        L = _lib.lib()
+        if L.snarkvm_hip_scope_stream():
+            raise PCError("evaluate_combinations_device: the values are needed at once - not inside a scope")
+        by_label = {p.label: p for p in polynomials}
+        lc_by_label = {lc.label: lc for lc in linear_combinations}
+        jobs = []
+        for label, (point_name, point) in query_set:
+            if label not in lc_by_label:
+                raise PCError(f"MissingEval({label})")
+            lc = lc_by_label[label]
+            constant, coeffs, members = None, [], []
             for coeff, term in lc.iter():
                 if term is ONE:
+                    constant = _fr_add(constant, coeff)
                     continue
-                if term not in label_map:
-                    raise PCError(f"MissingPolynomial {{ label: {term} }}")
-                cur_poly, cur_rand = label_map[term]
-                if cur_poly.degree_bound is not None:
-                    if len(lc) != 1:
-                        raise PCError(f"EquationHasDegreeBounds({lc.label})")
-                    if not np.array_equal(coeff, FR_ONE):
-                        raise PCError(f"Coefficient must be one for degree-bounded equations ({lc.label})")
-                    degree_bound = cur_poly.degree_bound
-                if cur_poly.hiding_bound is not None:  # Some(_) > None
-                    hiding_bound = cur_poly.hiding_bound if hiding_bound is None else max(hiding_bound, cur_poly.hiding_bound)
+                if term not in by_label:
+                    raise PCError(f"MissingEval(Missing {term} for {lc.label})")
                 coeffs.append(coeff)
-                cur_polys.append(cur_poly.coeffs)
-                cur_rands.append(cur_rand.blinding_polynomial)
-            lc_polynomials.append(LabeledPolynomial(lc.label, poly.lincomb(coeffs, cur_polys), degree_bound, hiding_bound))
-            lc_randomness.append(KZGRandomness(poly.lincomb(coeffs, cur_rands)))
-        return SonicKZG10.batch_open(max_degree, ck, lc_polynomials, query_set, lc_randomness, fs_rng)
+                members.append(by_label[term])
+            jobs.append(((label, point_name), point, constant, coeffs, members))
+        anchor = next((p.ptr for _, _, _, _, ms in jobs for p in ms if p.n), 0)
+        values = []
+        if anchor:
+            _lib.check(L.snarkvm_hip_scope_begin(ctypes.c_void_p(anchor)))
+        try:
+            for _, point, _, coeffs, members in jobs:
+                n = max([p.n for p in members] + [0])
+                values.append(plugin.fr_open_fold_device(None, n, [p.ptr for p in members], [p.n for p in members], coeffs, point) if n else None)
+        finally:
+            if anchor:
+                _lib.check(L.snarkvm_hip_scope_end())
+        return {key: _fr_add(None if v is None else v[0], constant) for (key, _, constant, _, _), v in zip(jobs, values)}
+
+    @staticmethod
+    def open_combinations_device(max_degree, ck, linear_combinations, polynomials, rands, query_set, fs_rng):
+        """`open_combinations` over `ResidentPolynomial`s: the same proofs as `open_combinations` on the downloaded polynomials - the same errors,
+        the same hiding-bound rule, point names and the labels of a point in sorted order, the same challenges squeezed in the same order (one
+        per combination of a point, then the unused `_randomizer`) - without materialising a combination.  Per point the challenges are folded
+        into the members' coefficients on the host (sum_lc xi_lc sum_k a_(lc,k) p_k = sum_k (sum_lc xi_lc a_(lc,k)) p_k, exact), ONE
+        `snarkvm_hip_fr_open_fold` writes the witness into a buffer of this call and a `snarkvm_hip_fr_support` of it is left pending, all
+        points in one scope; when it ends the witnesses pass check_degree_is_too_large and are committed in ONE batched MSM over the
+        registered powers, leading zeros skipped by offset.  The blinding side (hiding_bound + 1 coefficients) runs on host operands as in
+        `open_combinations`.  Refused inside a caller's scope."""
+        from . import plugin
+        from .devmem import HipMem
+
+        L = _lib.lib()
+        if L.snarkvm_hip_scope_stream():
+            raise PCError("open_combinations_device: the supports of the witnesses are needed at once - not inside a scope")
+        polys, rands = list(polynomials), list(rands)
+        if len(polys) != len(rands):
+            raise PCError("length mismatch")
+        label_map = {p.label: (p, r) for p, r in zip(polys, rands)}
+        lcs = {}
+        for lc in linear_combinations:
+            coeffs, members, degree_bound, _hiding_bound = _lc_members(lc, label_map)
+            for p, _ in members:
+                if p.n > max_degree + 1:
+                    raise PCError(f"TooManyCoefficients: {p.n} > {max_degree + 1} (label {p.label}; pass the trimmed length)")
+            lcs[lc.label] = (lc, coeffs, members, degree_bound)
+        query_to_labels = {}
+        for label, (point_name, point) in query_set:
+            query_to_labels.setdefault(point_name, (point, set()))[1].add(label)
+        view = _OpenPowers(ck.powers())
+        # ---- per point: the challenges, the folded coefficients and the blinding side (host)
+        points = []
+        for point_name in sorted(query_to_labels):
+            point, labels = query_to_labels[point_name]
+            folded, rand_terms = {}, []
+            for label in sorted(labels):
+                if label not in lcs:
+                    raise PCError(f"MissingPolynomial {{ label: {label} }}")
+                lc, coeffs, members, degree_bound = lcs[label]
+                # the combination as a labelled polynomial: only its bound and the upper bound of its degree are consulted
+                check_degrees_and_bounds(max_degree, ck.enforced_degree_bounds, ResidentPolynomial(lc.label, 0, max([p.n for p, _ in members] + [0]), degree_bound))
+                xi = fs_rng.squeeze_short_nonnative_field_element()
+                for a, (p, r) in zip(coeffs, members):
+                    c = _fr_mul(xi, a)
+                    entry = folded.setdefault(p.label, [p, None])
+                    entry[1] = _fr_add(entry[1], c)
+                    rand_terms.append((c, r.blinding_polynomial))
+            fs_rng.squeeze_short_nonnative_field_element()  # `_randomizer` (mod.rs:331)
+            rand = KZGRandomness(poly.lincomb([c for c, _ in rand_terms], [b for _, b in rand_terms]))
+            hiding_witness = poly.divide_by_linear(rand.blinding_polynomial, point)[0] if rand.is_hiding() else None
+            random_v, blind = kzg10.hiding_side(view, point, rand, hiding_witness)
+            members = [p for p, _ in folded.values()]
+            n = max([p.n for p in members] + [0])
+            points.append({"point": point, "members": members, "coeffs": [c for _, c in folded.values()], "n": n, "random_v": random_v, "blind": blind,
+                           "quot": HipMem(32 * max(1, n + blind.shape[0]))})
+        # ---- one scope: a fused fold-and-divide and a pending support per point
+        anchor = next((pt["quot"].ptr for pt in points), 0)
+        if anchor:
+            _lib.check(L.snarkvm_hip_scope_begin(ctypes.c_void_p(anchor)))
+        try:
+            for pt in points:
+                pt["support"] = np.zeros(3, dtype=np.uint64)
+                if pt["n"]:
+                    plugin.fr_open_fold_device(pt["quot"].ptr, pt["n"], [p.ptr for p in pt["members"]], [p.n for p in pt["members"]], pt["coeffs"], pt["point"],
+                                               remainder=False)
+                    pt["support"] = plugin.fr_support_device(pt["quot"].ptr, pt["n"])
+        finally:
+            if anchor:
+                _lib.check(L.snarkvm_hip_scope_end())
+        # ---- one batched MSM: witness coefficients over powers[lz ..), the hiding witness (uploaded right behind them) over the gamma powers
+        k = len(points)
+        off0, n0, off1, n1, ptrs = [], [], [], [], []
+        for pt in points:
+            trimmed_len, lz = int(pt["support"][0]), int(pt["support"][1])
+            if trimmed_len and trimmed_len + 1 > view.size():  # KZG10::open's own check on the combination (mod.rs:310): one coefficient more than its witness
+                raise PCError(f"TooManyCoefficients: {trimmed_len + 1} > {view.size()}")
+            lz, plain = kzg10.resident_range(trimmed_len, lz, view.size())
+            if pt["blind"].shape[0]:
+                pt["quot"].upload(pt["blind"], 32 * (lz + plain))
+            off0.append(view._view.off + lz), n0.append(plain), off1.append(view._gamma_offset), n1.append(pt["blind"].shape[0])
+            ptrs.append(pt["quot"].ptr + 32 * lz)
+        outs = np.zeros(k, dtype=G1_PROJECTIVE)
+        if k:
+            arr = lambda v: (ctypes.c_size_t * k)(*v)  # noqa: E731
+            _lib.check(L.snarkvm_hip_msm_registered_batch_ex(outs.ctypes.data, ck._h, k, arr(off0), arr(n0), arr(off1), arr(n1), (ctypes.c_void_p * k)(*ptrs), 1, 1, 0))
+        affine = kzg10.to_affine(outs) if k else np.zeros(0, dtype=G1_AFFINE)
+        for pt in points:
+            pt["quot"].free()
+        return [kzg10.KZGProof(affine[i], pt["random_v"]) for i, pt in enumerate(points)]
 
 
 class _One:
@@ -337,6 +477,41 @@ class LinearCombination:
         """(coefficient, term) in the order of the reference's BTreeMap: `ONE` first, then the labels."""
         for t in sorted(self.terms, key=lambda t: (t is not ONE, "" if t is ONE else t)):
             yield self.terms[t], t
+
+
+def _lc_members(lc, label_map):
+    """The terms of one linear combination as `open_combinations` takes them (sonic_pc/mod.rs:427-447): -> (coefficients, [(polynomial,
+    randomness)], degree bound, hiding bound).  `ONE` terms are not committed to and skipped; a degree-bounded polynomial may only stand
+    alone, with coefficient one; the hiding bound is the largest of the terms'."""
+    coeffs, members = [], []
+    degree_bound = hiding_bound = None
+    for coeff, term in lc.iter():
+        if term is ONE:
+            continue
+        if term not in label_map:
+            raise PCError(f"MissingPolynomial {{ label: {term} }}")
+        cur_poly, cur_rand = label_map[term]
+        if cur_poly.degree_bound is not None:
+            if len(lc) != 1:
+                raise PCError(f"EquationHasDegreeBounds({lc.label})")
+            if not np.array_equal(coeff, FR_ONE):
+                raise PCError(f"Coefficient must be one for degree-bounded equations ({lc.label})")
+            degree_bound = cur_poly.degree_bound
+        if cur_poly.hiding_bound is not None:  # Some(_) > None
+            hiding_bound = cur_poly.hiding_bound if hiding_bound is None else max(hiding_bound, cur_poly.hiding_bound)
+        coeffs.append(coeff)
+        members.append((cur_poly, cur_rand))
+    return coeffs, members, degree_bound, hiding_bound
+
+
+def _fr_limbs(x):
+    return sum(int(w) << (64 * i) for i, w in enumerate(np.asarray(x, dtype=np.uint64).reshape(4)))
+
+
+def _fr_mul(a, b):
+    """a * b in Fr on (4,) Montgomery limbs: (a R)(b R) R^-1 = a b R, R = 2^256."""
+    s = _fr_limbs(a) * _fr_limbs(b) * pow(1 << 256, -1, FR_MODULUS) % FR_MODULUS
+    return np.array([(s >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
 
 
 def _fr_add(a, b):
