@@ -802,8 +802,15 @@ __global__ void __launch_bounds__(256, MINW) msm_accumulate_seg_kernel(const aff
     // entry = slot of the base relative to `bases` (31 bits) | sign << 31  (mask: timing experiments of profiling builds only)
     auto slot_of = [&](uint32_t e) -> const aff_mem_t<F>* { return &bases[(e & 0x7fffffffu) & debug_idx_mask]; };
     uint32_t e_next = sorted[lo];
+    // PREFETCH: the two-stage gather pipeline of msm_accumulate_lazy_kernel - the index of entry pos + 2 (e_n2) and the base of entry
+    // pos + 1 (raw_next), both requested unconditionally on clamped positions, and the bucket bookkeeping requested in every
+    // iteration: nothing an iteration requests is merged with an old value behind a branch, which is where the compiler waits
+    uint32_t e_n2 = 0;
     aff_mem_t<F> raw_next;
-    if (PREFETCH) raw_next = *slot_of(e_next);
+    if (PREFETCH) {
+        e_n2 = sorted[lo + 1 < hi ? lo + 1 : lo];
+        raw_next = *slot_of(e_next);
+    }
     for (uint32_t pos = lo; pos < hi; pos++) {
         if (pos >= kend) {  // bucket k ends inside this segment: flush and move to the bucket of `pos`
             store_xyzz<F>(&partial[start_k + part_off], acc);
@@ -815,6 +822,12 @@ __global__ void __launch_bounds__(256, MINW) msm_accumulate_seg_kernel(const aff
                 k++;
                 kend = boff[k + 1];
             }
+            if (!PREFETCH) {
+                kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];
+                start_k = start[k];
+            }
+        }
+        if (PREFETCH) {  // k < nbt: bucket k holds entry pos < boff[nbt]
             kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];
             start_k = start[k];
         }
@@ -822,10 +835,9 @@ __global__ void __launch_bounds__(256, MINW) msm_accumulate_seg_kernel(const aff
         aff_mem_t<F> raw;
         if (PREFETCH) {
             raw = raw_next;
-            if (pos + 1 < hi) {
-                e_next = sorted[pos + 1];
-                raw_next = *slot_of(e_next);
-            }
+            raw_next = *slot_of(pos + 1 < hi ? e_n2 : e);  // past the end: the base in hand again, never used
+            e_next = e_n2;
+            e_n2 = sorted[pos + 2 < hi ? pos + 2 : hi - 1];
         } else {
             raw = *slot_of(e);
             if (pos + 1 < hi) e_next = sorted[pos + 1];
@@ -871,12 +883,14 @@ __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_af
     uint32_t k = find_bucket(boff, nbt, lo);  // the non-empty bucket that contains entry `lo`
     uint32_t kend = boff[k + 1];
     // The bucket bookkeeping runs one bucket ahead: the end of the NEXT bucket (boff[k + 2]) and the partial-sum slot of the
-    // CURRENT one (start[k]) are requested when a lane enters bucket k, so the flush at the bucket's end - reached by some lane
-    // of a wave in most iterations - finds both in registers instead of waiting for two dependent loads from 8 MB arrays
-    // (boff / start: one entry per bucket) while the wave's arithmetic stands still.  boff has nbt + 1 entries: the index is
-    // clamped (a clamped value is only ever compared after the segment's last entry).
-    uint32_t kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];
-    uint32_t start_k = start[k];
+    // CURRENT one (start[k]) are in registers when the flush at the bucket's end - reached by some lane of a wave in most
+    // iterations - needs them.  Both are requested in EVERY iteration, once k is final, not only by the lanes that just flushed: a
+    // load inside the flush branch is merged with the old value behind the branch, and the compiler waited for it there (and,
+    // stores and loads sharing one counter, for the 13 flush stores issued before it) in front of the addition.  A lane that did
+    // not flush reads the values it already holds (the same two cache lines as one iteration earlier).  boff has nbt + 1 entries:
+    // the index is clamped (a clamped value is only ever compared after the segment's last entry); k < nbt, since bucket k holds
+    // an entry below hi <= boff[nbt].  The first iteration never flushes (lo < boff[k + 1]), so neither needs a value before the loop.
+    uint32_t kend2 = 0, start_k = 0;
     // slot of this thread's partial sum inside bucket k: start[k] + (t - first thread of the bucket).  Only the thread's FIRST bucket
     // can have started in an earlier thread; every later one starts inside this segment, i.e. its first thread is t (no division
     // inside the loop)
@@ -884,10 +898,15 @@ __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_af
     xyzz_lazy_t acc = xyzz_lazy_t::infinity();
     auto slot_of = [&](uint32_t e) -> const g1_lazy_slot_t* { return (const g1_lazy_slot_t*)&bases[(e & 0x7fffffffu) & debug_idx_mask]; };
     // Software pipeline of the gather (one wave per SIMD, nothing else hides latency): two stages - the INDEX of entry
-    // pos + 2 and the BASE of entry pos + 1 are requested before the addition of entry pos starts, so neither the index load nor
-    // the dependent base load (index -> address) is ever waited for with an idle SIMD.
+    // pos + 2 and the BASE of entry pos + 1 are requested before the addition of entry pos starts.  Both requests are
+    // UNCONDITIONAL, on clamped positions: behind `if (pos + 1 < hi)` every loaded register is merged with its old value at the
+    // end of the branch, and the compiler placed those copies - with a wait for the gather in front of each - before the
+    // addition.  Past the segment's end the lane asks again for what it already has (entry hi - 1, and the base of the entry it is
+    // adding), so no position at or beyond hi is read and no gather goes through an index that was not loaded; the values are
+    // never used.  In the compiled loop every wait for a request of an iteration stands behind that iteration's addition
+    // (tools/isa_waits.py, profiles/acc_waits.md); the empty-bucket loop and the cold call are the exceptions.
     uint32_t e_cur = sorted[lo];
-    uint32_t e_n1 = lo + 1 < hi ? sorted[lo + 1] : 0u;
+    uint32_t e_n1 = sorted[lo + 1 < hi ? lo + 1 : lo];
     g1_lazy_slot_t raw_next = *slot_of(e_cur);
     for (uint32_t pos = lo;; pos++) {
         const bool end = pos >= hi;
@@ -906,14 +925,14 @@ __global__ void __launch_bounds__(256, 1) msm_accumulate_lazy_kernel(const g1_af
                 k++;
                 kend = boff[k + 1];
             }
-            kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];
-            start_k = start[k];
         }
+        kend2 = boff[k + 2 <= nbt ? k + 2 : nbt];
+        start_k = start[k];
         const uint32_t e = e_cur;
         const g1_lazy_slot_t raw = raw_next;
-        if (pos + 1 < hi) raw_next = *slot_of(e_n1);  // e_n1 arrived during the previous addition
+        raw_next = *slot_of(pos + 1 < hi ? e_n1 : e);  // e_n1 arrived during the previous addition
         e_cur = e_n1;
-        if (pos + 2 < hi) e_n1 = sorted[pos + 2];
+        e_n1 = sorted[pos + 2 < hi ? pos + 2 : hi - 1];
         if (raw.w[26]) continue;  // the point at infinity
         const bool neg = (e >> 31) != 0;
         fql_t px, py;

@@ -24,7 +24,9 @@
 //   lazy2           1        G2 accumulation on the signed-limb Fq2 arithmetic, one value per lane pair (ffl2p.hip.h: c0 on the even lane, c1 on the odd lane; 0: exact kernel)
 //   fused           1        wide windows: scalar read fused with the level-1 partition (0: stand-alone digit matrix)
 //   acc_lds         98304    dynamic LDS request that keeps a second accumulate workgroup off a CU (single-round grids); 0: off
-//   acc_one_wg      0        1: one accumulate workgroup per CU for multi-round grids too
+//   acc_one_wg      0        1: one accumulate workgroup per CU for multi-round grids too.  Measured on the loop that still waited for its gather and its
+//                            flush stores in front of the addition (step 34.4 against 31.1 ms); NOT re-measured on the loop of profiles/acc_waits.md, where
+//                            the second resident wave has less to cover - the default stays until it is (tests/test_gpu_accumulate_segments.py keeps 1 exact)
 //   reduce_rounds   1        fixed reduce rounds of a multi-round MSM (0 .. 8), each shrinking a bucket's partial sums by the group size (seg2, 16).
 //                            Round 4: one round of 16 instead of two of 8 - for uniform scalars the second round only copied (0.84 -> 0.57 ms of
 //                            reduce time at 2^24, 29.84 -> 29.51 ms per step; one round of 64: 0.99 ms); what an all-equal scalar vector leaves in
