@@ -594,6 +594,46 @@ void snarkvm_hip_fr_arith_free(snarkvm_hip_fr_arith_t *handle);
 RustError snarkvm_hip_fr_matrix_sumcheck_evals(const snarkvm_hip_fr_arith_t *const *ariths, size_t count, void *const *a_evals, void *const *b_evals,
                                                void *const *f_evals, const void *alpha, const void *beta, const void *scales, int on_device);
 
+/* The circuit index: the arithmetization of one R1CS matrix on its non-zero domain K (csrc/poly.hip.h: fr_arithmetize_kernel) - matrix_evals of
+ * snark/varuna/ahp/matrices.rs:138-195, the data snarkvm_hip_fr_arith_register takes as three finished host arrays.  The matrix is CSR as in
+ * snarkvm_hip_fr_matrix_register: row r owns entries row_ptr[r] .. row_ptr[r+1]-1 (row_ptr: rows + 1 values), entry e is vals[e] (32 bytes, Montgomery
+ * form) at column col_idx[e]; nnz = row_ptr[rows].  With w_R, w_C the group generators of the constraint domain (2^lg_constraint elements) and the
+ * variable domain (2^lg_variable), for entry e = (val, j) of row i:
+ *    row[e] = w_R^i      col[e] = w_C^reindex(j)      row_col[e] = row[e] col[e]      row_col_val[e] = val row_col[e]
+ * and (1, 1, 1, 0) at the places nnz <= e < k.  reindex is EvaluationDomain::reindex_by_subdomain (fft/domain.rs:322-344) for the input domain of
+ * 2^lg_input elements: with period = 2^(lg_variable - lg_input), j period for j < 2^lg_input, otherwise t + t / (period - 1) + 1 with
+ * t = j - 2^lg_input.  k need not be a power of two.  Zero values and duplicate columns are legal (into_matrix_helper's rules are the caller's).
+ * fr_arithmetize: each of the four outputs (k elements) may be NULL, which skips it; of a given output every element is written.  on_device governs
+ * the CSR arrays AND the outputs: all host memory (0: staged like the other passes, the results are there on return) or all device memory on one
+ * device (1; inside a snarkvm_hip_scope the call is only enqueued).  No operand is written.
+ *  - k == 0, or all four outputs NULL: success (after the checks below), nothing is touched, no device is needed.
+ *  - Refused with hipErrorInvalidValue before anything is launched and before a device is needed, every output untouched: a NULL row_ptr; any lg above
+ *    28; lg_input >= lg_variable (the reference's "other.size() must be smaller than self.size()"); k > 2^28; rows > 2^lg_constraint; outputs that
+ *    overlap each other or vals; with on_device = 1, operands on different devices or not in device memory.  With HOST CSR arrays (on_device = 0, and
+ *    always for fr_arith_register_csr) also: row_ptr[0] != 0; a decreasing row_ptr; row_ptr[rows] > 2^32 - 1; NULL col_idx or vals of a matrix with
+ *    entries; k < nnz; any col_idx[e] >= 2^lg_variable.
+ *  - With DEVICE CSR arrays their contents cannot be read before the launch and are the CALLER'S CONTRACT, like the registered indices of
+ *    snarkvm_hip_fr_spmv: row_ptr[0] = 0, row_ptr non-decreasing, nnz <= k, col_idx[e] < 2^lg_variable; and since nnz is not known before the
+ *    launch, of the overlap with vals only its first element is checked - no output may touch the rest either.  The kernel clamps nothing, but it reads nnz
+ *    from row_ptr[rows], treats min(nnz, k) places as entries, keeps its row search inside row_ptr whatever that holds and reduces every exponent
+ *    modulo its domain size: broken contents give wrong elements, never an access outside row_ptr, col_idx, vals or the outputs.
+ * fr_arith_register_csr: HOST CSR arrays, not retained; every device of the current device set computes ITS OWN replica (row | col | row_col_val)
+ * with the same kernel - nothing but the CSR arrays crosses the bus.  The handle is indistinguishable from snarkvm_hip_fr_arith_register's: it goes to
+ * snarkvm_hip_fr_matrix_sumcheck_evals and is released by snarkvm_hip_fr_arith_free.  Refused like fr_arithmetize with host arrays, and for a NULL
+ * handle; *handle, when given, is NULL afterwards.  k == 0 is legal.
+ *  - The row of an entry is found by an upper-bound binary search over row_ptr (empty rows - leading, trailing, runs of them - are skipped: the
+ *    smallest row whose end lies behind the entry owns it).  A power w^x is the product of two table entries, x's low s bits and the rest
+ *    (s = ceil(lg / 2): at most 2 x 2^14 elements per domain).
+ *  - Workspace: the two table pairs (built on the device, on the call's stream) and, with host operands, the staged arrays come from the calling lane
+ *    and are kept for the next call; a repeated call grows nothing (snarkvm_hip_alloc_stats).
+ *  - No atomics; every thread owns its elements, field arithmetic is exact and results canonical: the 32 bytes of every output depend on neither the
+ *    table split, the thread count nor the grid. */
+RustError snarkvm_hip_fr_arithmetize(void *row, void *col, void *row_col, void *row_col_val, size_t k, size_t rows, const uint64_t *row_ptr,
+                                     const uint32_t *col_idx, const void *vals, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input,
+                                     int on_device);
+RustError snarkvm_hip_fr_arith_register_csr(snarkvm_hip_fr_arith_t **handle, size_t k, size_t rows, const uint64_t *row_ptr, const uint32_t *col_idx,
+                                            const void *vals, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input);
+
 /* Strided batches of the passes above on device memory - the same pass over one vector of every proof of a batch proved in lock
  * step (VarunaSNARK::prove_batch, snark/varuna/varuna.rs:336): member y of the batch uses every vector pointer advanced by
  * y * stride elements (stride >= the vector length); ONE kernel launch sequence for the whole batch.  fr_vec_op_strided: `scalar`
@@ -742,6 +782,15 @@ int snarkvm_hip_selftest_fr_spmv_geometry(size_t rows, size_t nnz, uint32_t *out
 int snarkvm_hip_selftest_fr_sumcheck(void *a, void *b, void *f, const void *row, const void *col, const void *rcv, size_t k, const void *alpha,
                                      const void *beta, const void *scales, uint32_t blocks, uint32_t threads);
 int snarkvm_hip_selftest_fr_sumcheck_geometry(size_t k, uint32_t *out);
+/* snarkvm_hip_fr_arithmetize over host memory with the CPU in the kernels' place, for a GIVEN table split (the low split_bits bits of an exponent go
+ * to the first table; a value above a domain's lg counts as that lg) and `threads` >= 1 threads in all, thread t owning e = t, t + threads, ...: the
+ * validation of the host-operand call, the tables and every element through the kernels' own routines (csrc/poly.hip.h: fr_arith_table_at,
+ * fr_arith_at).  0, or -1 when the arguments are refused.  fr_arithmetize_geometry: out4 = {workgroups, threads per workgroup, the cap on the
+ * workgroups} of what the device call launches for k elements, and the split bits it uses for a domain of 2^lg elements. */
+int snarkvm_hip_selftest_fr_arithmetize(void *row, void *col, void *row_col, void *row_col_val, size_t k, size_t rows, const uint64_t *row_ptr,
+                                        const uint32_t *col_idx, const void *vals, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input,
+                                        uint32_t split_bits, uint32_t threads);
+int snarkvm_hip_selftest_fr_arithmetize_geometry(size_t k, uint32_t lg, uint32_t *out4);
 /* Same field operations executed by a GPU kernel (one thread per element). */
 RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void *b, void *out, size_t n);
 /* Field arithmetic that the two operands of snarkvm_hip_selftest_field cannot express, one case per record, operands and results in memory

@@ -322,6 +322,12 @@ public:
     RegisteredArithmetization(size_t k, const void* row, const void* col, const void* row_col_val) : k_(k) {
         check(snarkvm_hip_fr_arith_register(&h_, k, row, col, row_col_val));
     }
+    // from the CSR arrays of the matrix alone (snarkvm_hip.h: snarkvm_hip_fr_arith_register_csr): every device in use computes its own replica
+    RegisteredArithmetization(size_t k, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals, uint32_t lg_constraint, uint32_t lg_variable,
+                              uint32_t lg_input)
+        : k_(k) {
+        check(snarkvm_hip_fr_arith_register_csr(&h_, k, rows, row_ptr, col_idx, vals, lg_constraint, lg_variable, lg_input));
+    }
     RegisteredArithmetization(const RegisteredArithmetization&) = delete;
     RegisteredArithmetization& operator=(const RegisteredArithmetization&) = delete;
     ~RegisteredArithmetization() { snarkvm_hip_fr_arith_free(h_); }  // waits for the device: safe with an evaluation still enqueued in this thread's Scope
@@ -336,6 +342,14 @@ private:
 inline void matrix_sumcheck_evals(const snarkvm_hip_fr_arith_t* const* ariths, size_t count, void* const* a_evals, void* const* b_evals, void* const* f_evals,
                                   const void* alpha, const void* beta, const void* scales, bool on_device) {
     check(snarkvm_hip_fr_matrix_sumcheck_evals(ariths, count, a_evals, b_evals, f_evals, alpha, beta, scales, on_device ? 1 : 0));
+}
+
+// The arithmetization on K of a CSR matrix (snarkvm_hip.h: snarkvm_hip_fr_arithmetize; matrix_evals of ahp/matrices.rs:138-195): row, col, row_col and
+// row_col_val, k elements each, a null output skipped; on_device governs the CSR arrays and the outputs alike.  With on_device inside a Scope the call
+// is only enqueued.
+inline void fr_arithmetize(void* row, void* col, void* row_col, void* row_col_val, size_t k, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx,
+                           const void* vals, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input, bool on_device) {
+    check(snarkvm_hip_fr_arithmetize(row, col, row_col, row_col_val, k, rows, row_ptr, col_idx, vals, lg_constraint, lg_variable, lg_input, on_device ? 1 : 0));
 }
 
 }  // namespace snarkvm_hip

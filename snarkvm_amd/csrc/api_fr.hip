@@ -1869,6 +1869,197 @@ int snarkvm_hip_selftest_fr_sumcheck_geometry(size_t k, uint32_t* out4) {
     return 0;
 }
 
+// ---- the circuit index: the arithmetization of a CSR matrix on K (poly.hip.h: fr_arithmetize_kernel) ---------------------------------
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device and touches nothing.  host_csr: the CSR arrays can be read here -
+// after it no index the kernel will ever see points outside row_ptr, col_idx, vals or a table.  Device CSR: the contents are the caller's contract.
+static const char* fr_arith_check(void* const* outs, size_t k, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals, uint32_t lg_constraint,
+                                  uint32_t lg_variable, uint32_t lg_input, bool host_csr) {
+    if (lg_constraint > (uint32_t)NTT_LG_MAX || lg_variable > (uint32_t)NTT_LG_MAX || lg_input > (uint32_t)NTT_LG_MAX) return "a domain of more than 2^28 elements";
+    if (lg_input >= lg_variable) return "other.size() must be smaller than self.size() (lg_input >= lg_variable)";
+    if (k > FR_ARITH_K_MAX) return "more than 2^28 elements";
+    if (rows > ((size_t)1 << lg_constraint)) return "more rows than the constraint domain has elements";
+    if (!row_ptr) return "null row_ptr";
+    size_t span_vals = 1;  // device CSR: nnz cannot be read here - the first element of vals is checked, the rest is the caller's contract
+    if (host_csr) {
+        if (row_ptr[0] != 0) return "row_ptr[0] != 0";
+        for (size_t r = 0; r < rows; r++)
+            if (row_ptr[r + 1] < row_ptr[r]) return "row_ptr decreases";
+        const uint64_t nnz = row_ptr[rows];
+        if (nnz > 0xFFFFFFFFull) return "more than 2^32 - 1 entries";
+        if (nnz && (!col_idx || !vals)) return "null col_idx or vals of a matrix with entries";
+        if (k < nnz) return "k is less than the number of entries";
+        for (uint64_t e = 0; e < nnz; e++)
+            if (col_idx[e] >> lg_variable) return "a column index is not below the variable domain size";
+        span_vals = (size_t)nnz;
+    }
+    for (int i = 0; i < 4; i++) {
+        if (fr_ranges_overlap(outs[i], k, vals, span_vals)) return "an output overlaps vals";
+        for (int j = i + 1; j < 4; j++)
+            if (fr_ranges_overlap(outs[i], k, outs[j], k)) return "two outputs overlap";
+    }
+    return nullptr;
+}
+static fr_mem_t fr_domain_generator_mem(uint32_t lg) {  // group_gen of the 2^lg domain (fft_field.rs:75-85), memory form
+    fr_t omega = fr_t::unpack(FR_TWO_ADIC_ROOT_MEM_HOST).from_mem_mont();
+    for (uint32_t i = lg; i < 47; i++) omega = omega.sqr();
+    fr_mem_t m;
+    omega.to_mem_mont().store(&m);
+    return m;
+}
+// everything of a kernel argument but the pointers
+static fr_arith_t fr_arith_args(size_t k, size_t rows, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input, uint32_t s_r, uint32_t s_c) {
+    fr_arith_t a{};
+    fr_t::one().to_mem_mont().store(&a.one);
+    const fr_t fix2 = fr_t::one().from_mem_mont().from_mem_mont();
+    for (int l = 0; l < 9; l++) a.fix2[l] = fix2.v[l];
+    a.k = (uint32_t)k, a.rows = (uint32_t)rows;
+    a.s_r = s_r, a.mask_r = (1u << lg_constraint) - 1, a.s_c = s_c, a.mask_c = (1u << lg_variable) - 1;
+    a.input_size = 1u << lg_input, a.period = 1u << (lg_variable - lg_input);
+    return a;
+}
+// the tables and the pass, enqueued on the lane's stream; every pointer is device memory of the lane's device.  Tables: c.poly[4].
+static void fr_arith_run(lane_t& c, fr_mem_t* const* outs, size_t k, size_t rows, const uint64_t* d_row_ptr, const uint32_t* d_col, const fr_mem_t* d_vals,
+                         uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input) {
+    const uint32_t s_r = fr_arith_split(lg_constraint), s_c = FR_ARITH_FULL_TABLE ? lg_variable : fr_arith_split(lg_variable);
+    const size_t n_r = ((size_t)1 << s_r) + ((size_t)1 << (lg_constraint - s_r)), n_c = ((size_t)1 << s_c) + ((size_t)1 << (lg_variable - s_c));
+    c.poly[4].ensure(sizeof(fr_mem_t) * (n_r + n_c));
+    fr_mem_t* t = c.poly[4].as<fr_mem_t>();
+    fr_arith_t a = fr_arith_args(k, rows, lg_constraint, lg_variable, lg_input, s_r, s_c);
+    a.row = outs[0], a.col = outs[1], a.row_col = outs[2], a.rcv = outs[3];
+    a.row_ptr = d_row_ptr, a.col_idx = d_col, a.vals = d_vals;
+    a.r_lo = t, a.r_hi = t + ((size_t)1 << s_r), a.c_lo = t + n_r, a.c_hi = t + n_r + ((size_t)1 << s_c);
+    hipLaunchKernelGGL(fr_arith_tables_kernel, dim3((unsigned)((n_r + 255) / 256)), dim3(256), 0, c.stream, t, t + ((size_t)1 << s_r), fr_domain_generator_mem(lg_constraint), s_r,
+                       (uint32_t)n_r);
+#if FR_ARITH_FULL_TABLE  // measurement variant: w_C^x for every x of the variable domain, as fr_lagrange_coefficients forms them
+    hipLaunchKernelGGL(fr_fill_kernel, dim3(fr_grid((size_t)1 << lg_variable)), dim3(256), 0, c.stream, t + n_r, (size_t)1 << lg_variable, a.one);
+    fr_distribute_powers_run(c, t + n_r, (size_t)1 << lg_variable, fr_domain_generator_mem(lg_variable), a.one);
+#else
+    hipLaunchKernelGGL(fr_arith_tables_kernel, dim3((unsigned)((n_c + 255) / 256)), dim3(256), 0, c.stream, t + n_r, t + n_r + ((size_t)1 << s_c),
+                       fr_domain_generator_mem(lg_variable), s_c, (uint32_t)n_c);
+#endif
+    hipLaunchKernelGGL(fr_arithmetize_kernel, dim3(fr_grid(k)), dim3(256), 0, c.stream, a);
+    HIP_TRY(hipGetLastError());
+}
+// the host CSR arrays as device pointers in c.poly[0 .. 2]
+static void fr_arith_stage_csr(lane_t& c, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals, const uint64_t*& d_row_ptr, const uint32_t*& d_col,
+                               const fr_mem_t*& d_vals) {
+    const size_t nnz = (size_t)row_ptr[rows];
+    c.poly[0].ensure(sizeof(uint64_t) * (rows + 1) + (FR_ARITH_ROW_INDEX ? sizeof(uint32_t) * nnz : 0));
+    c.poly[1].ensure(sizeof(uint32_t) * (nnz ? nnz : 1));
+    HIP_TRY(hipMemcpyAsync(c.poly[0].p, row_ptr, sizeof(uint64_t) * (rows + 1), hipMemcpyHostToDevice, c.stream));
+#if FR_ARITH_ROW_INDEX  // measurement variant: the row of every entry, expanded here and laid behind row_ptr (the copy is synchronous: pageable memory)
+    {
+        std::vector<uint32_t> row_of(nnz);
+        for (size_t r = 0; r < rows; r++)
+            for (uint64_t e = row_ptr[r]; e < row_ptr[r + 1]; e++) row_of[e] = (uint32_t)r;
+        if (nnz) HIP_TRY(hipMemcpy(c.poly[0].as<uint64_t>() + rows + 1, row_of.data(), sizeof(uint32_t) * nnz, hipMemcpyHostToDevice));
+    }
+#endif
+    if (nnz) HIP_TRY(hipMemcpyAsync(c.poly[1].p, col_idx, sizeof(uint32_t) * nnz, hipMemcpyHostToDevice, c.stream));
+    d_row_ptr = c.poly[0].as<uint64_t>(), d_col = c.poly[1].as<uint32_t>();
+    d_vals = fr_stage_in(c, 2, nnz ? vals : nullptr, nnz, 0);
+}
+RustError snarkvm_hip_fr_arithmetize(void* row, void* col, void* row_col, void* row_col_val, size_t k, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx,
+                                     const void* vals, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input, int on_device) {
+    void* const outs[4] = {row, col, row_col, row_col_val};
+    if (const char* why = fr_arith_check(outs, k, rows, row_ptr, col_idx, vals, lg_constraint, lg_variable, lg_input, !on_device))
+        return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_arithmetize: ") + why);
+    void* first = row ? row : (col ? col : (row_col ? row_col : row_col_val));
+    if (k == 0 || !first) return ok();
+    API_BEGIN_DEV(device_for(first, on_device ? 1 : 0))
+    fr_mem_t* d_outs[4] = {(fr_mem_t*)row, (fr_mem_t*)col, (fr_mem_t*)row_col, (fr_mem_t*)row_col_val};
+    const uint64_t* d_row_ptr = row_ptr;
+    const uint32_t* d_col = col_idx;
+    const fr_mem_t* d_vals = (const fr_mem_t*)vals;
+    if (on_device) {
+        const char* why = "fr_arithmetize: the operands live on different devices";
+        for (int i = 0; i < 4; i++) fr_same_device(c, outs[i], why);
+        fr_same_device(c, row_ptr, why);
+        fr_same_device(c, col_idx, why);
+        fr_same_device(c, vals, why);
+    } else {  // host operands: the CSR arrays in three lane buffers, the wanted outputs one behind the other in a fourth; one download each
+        fr_arith_stage_csr(c, rows, row_ptr, col_idx, vals, d_row_ptr, d_col, d_vals);
+        size_t wanted = 0;
+        for (int i = 0; i < 4; i++) wanted += outs[i] ? 1 : 0;
+        c.poly[3].ensure(sizeof(fr_mem_t) * wanted * k);
+        fr_mem_t* next = c.poly[3].as<fr_mem_t>();
+        for (int i = 0; i < 4; i++)
+            if (outs[i]) d_outs[i] = next, next += k;
+    }
+    fr_arith_run(c, d_outs, k, rows, d_row_ptr, d_col, d_vals, lg_constraint, lg_variable, lg_input);
+    if (!on_device)
+        for (int i = 0; i < 4; i++)
+            if (outs[i]) HIP_TRY(hipMemcpyAsync(outs[i], d_outs[i], sizeof(fr_mem_t) * k, hipMemcpyDeviceToHost, c.stream));
+    fr_call_done(c, on_device);
+    API_END
+}
+RustError snarkvm_hip_fr_arith_register_csr(snarkvm_hip_fr_arith_t** handle, size_t k, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx, const void* vals,
+                                            uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input) {
+    if (!handle) return fail((int)hipErrorInvalidValue, "snarkvm_hip: fr_arith_register_csr: null handle");
+    *handle = nullptr;
+    void* const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (const char* why = fr_arith_check(none, k, rows, row_ptr, col_idx, vals, lg_constraint, lg_variable, lg_input, true))
+        return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_arith_register_csr: ") + why);
+    API_TRY
+    std::unique_ptr<snarkvm_hip_fr_arith> h(new snarkvm_hip_fr_arith());
+    h->k = k;
+    const int nd = g_rt.ndev();
+    h->d.assign(nd, nullptr);
+    try {
+        std::vector<int> all;
+        for (int d = 0; d < nd; d++) all.push_back(d);
+        for_each_device(all, [&](int dev) {  // every device computes its own replica from the CSR arrays
+            lane_guard lg(dev);
+            lane_t& c = lg.c();
+            HIP_TRY(hipMalloc((void**)&h->d[dev], k ? 3 * sizeof(fr_mem_t) * k : 32));
+            if (k) {
+                const uint64_t* d_row_ptr;
+                const uint32_t* d_col;
+                const fr_mem_t* d_vals;
+                fr_arith_stage_csr(c, rows, row_ptr, col_idx, vals, d_row_ptr, d_col, d_vals);
+                fr_mem_t* const outs[4] = {h->d[dev], h->d[dev] + k, nullptr, h->d[dev] + 2 * k};
+                fr_arith_run(c, outs, k, rows, d_row_ptr, d_col, d_vals, lg_constraint, lg_variable, lg_input);
+                HIP_TRY(hipStreamSynchronize(c.stream));
+            }
+        });
+    } catch (...) {
+        h->free_all();
+        throw;
+    }
+    *handle = h.release();
+    API_CATCH
+}
+// snarkvm_hip_fr_arithmetize on host memory with the CPU in the kernel's place, for a GIVEN table split (split_bits low bits per domain, cut to the
+// domain's lg) and `threads` threads: the same validation, the tables through fr_arith_table_at, thread t over e = t, t + threads, ... through
+// fr_arith_at.  0, or -1 when refused.
+int snarkvm_hip_selftest_fr_arithmetize(void* row, void* col, void* row_col, void* row_col_val, size_t k, size_t rows, const uint64_t* row_ptr, const uint32_t* col_idx,
+                                        const void* vals, uint32_t lg_constraint, uint32_t lg_variable, uint32_t lg_input, uint32_t split_bits, uint32_t threads) {
+    void* const outs[4] = {row, col, row_col, row_col_val};
+    if (FR_ARITH_FULL_TABLE || FR_ARITH_ROW_INDEX) return -1;  // a measurement variant has no twin
+    if (threads < 1 || fr_arith_check(outs, k, rows, row_ptr, col_idx, vals, lg_constraint, lg_variable, lg_input, true)) return -1;
+    const uint32_t s_r = split_bits < lg_constraint ? split_bits : lg_constraint, s_c = split_bits < lg_variable ? split_bits : lg_variable;
+    const size_t n_r = ((size_t)1 << s_r) + ((size_t)1 << (lg_constraint - s_r)), n_c = ((size_t)1 << s_c) + ((size_t)1 << (lg_variable - s_c));
+    std::vector<fr_mem_t> tab(n_r + n_c);
+    const fr_mem_t w_r = fr_domain_generator_mem(lg_constraint), w_c = fr_domain_generator_mem(lg_variable);
+    for (size_t t = 0; t < n_r; t++) fr_arith_table_at(tab.data(), tab.data() + ((size_t)1 << s_r), fr_t::load(&w_r).from_mem_mont(), s_r, (uint32_t)t);
+    for (size_t t = 0; t < n_c; t++) fr_arith_table_at(tab.data() + n_r, tab.data() + n_r + ((size_t)1 << s_c), fr_t::load(&w_c).from_mem_mont(), s_c, (uint32_t)t);
+    fr_arith_t a = fr_arith_args(k, rows, lg_constraint, lg_variable, lg_input, s_r, s_c);
+    a.row = (fr_mem_t*)row, a.col = (fr_mem_t*)col, a.row_col = (fr_mem_t*)row_col, a.rcv = (fr_mem_t*)row_col_val;
+    a.row_ptr = row_ptr, a.col_idx = col_idx, a.vals = (const fr_mem_t*)vals;
+    a.r_lo = tab.data(), a.r_hi = tab.data() + ((size_t)1 << s_r), a.c_lo = tab.data() + n_r, a.c_hi = tab.data() + n_r + ((size_t)1 << s_c);
+    const uint32_t nnz = (uint32_t)row_ptr[rows];
+    for (size_t t = 0; t < threads && t < k; t++)
+        for (size_t e = t; e < k; e += threads) fr_arith_at(a, nnz, (uint32_t)e);
+    return 0;
+}
+// what snarkvm_hip_fr_arithmetize launches for k elements, and the table split of a domain of 2^lg elements: out4 = {workgroups, threads per
+// workgroup, the cap on workgroups, split bits s}
+int snarkvm_hip_selftest_fr_arithmetize_geometry(size_t k, uint32_t lg, uint32_t* out4) {
+    if (!out4 || k > FR_ARITH_K_MAX || lg > (uint32_t)NTT_LG_MAX) return -1;
+    out4[0] = fr_grid(k), out4[1] = 256, out4[2] = 8192, out4[3] = fr_arith_split(lg);
+    return 0;
+}
+
 // ---- setup-time group operations (group.hip.h) -------------------------------------------------------
 RustError snarkvm_hip_g1_fixed_base_msm(void* out_projective, const void* g_affine, const void* scalars, size_t n) {
     API_BEGIN

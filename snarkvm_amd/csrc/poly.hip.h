@@ -1120,4 +1120,112 @@ static __global__ void __launch_bounds__(FR_SUMCHECK_B) fr_sumcheck_evals_kernel
 }
 #endif
 
+// ---- the circuit index: the arithmetization of a CSR matrix on K ---------------------------------------------------------------------
+// matrix_evals (ahp/matrices.rs:138-195): entry e = (val, j) of row i gives row[e] = w_R^i, col[e] = w_C^reindex(j) with
+// EvaluationDomain::reindex_by_subdomain (fft/domain.rs:322-344), row_col[e] = row[e] col[e], row_col_val[e] = val row_col[e]; the places
+// nnz <= e < k hold (1, 1, 1, 0).  A map: one thread per output element, grid-stride past the launch cap.
+// Row lookup: the row of entry e is the one i with row_ptr[i] <= e < row_ptr[i + 1] - an upper-bound binary search over row_ptr, ~lg(rows)
+// dependent 8-byte loads of an array that stays in cache (neighbouring threads walk the same path).  Runs of empty rows give equal pointers;
+// the search keeps the SMALLEST i with row_ptr[i + 1] > e, which is the one row that owns the entry.
+// Powers: w^x for an arbitrary x < 2^lg is lo[x & (2^s - 1)] * hi[x >> s] over two tables of 2^s and 2^(lg - s) entries (s = ceil(lg / 2):
+// at most 2 * 2^14 elements per domain, cache-resident), built by fr_arith_tables_kernel in the calling lane's workspace.  Forms (top of this
+// file): lo holds memory images (raw reads are shifted values), hi TRUE internal values, so lo * hi is the memory form of the power with no
+// fix-up.  The product P of the two memory images row and col is the internal form of row col 2^-10: row_col = P * MEM2INT, and
+// row_col_val = (raw(val) * P) * MEM2INT^2 with the second constant formed once on the host - row, col, P, row_col and two for row_col_val:
+// SIX products per entry with all four outputs, five without row_col (registration), of which four are the function's own and the rest
+// the price of streaming every vector in memory form.  The exponent is masked to the domain (w^(2^lg) = 1), so no index - whatever col_idx
+// holds - reads outside a table.  Field arithmetic is exact and every product canonical: the bytes depend on neither s, the thread count nor
+// the grid (the host twin, snarkvm_hip_selftest_fr_arithmetize, replays forced geometries through fr_arith_at).
+// No atomics, no device-function call, no scratch.  Registers (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): fr_arithmetize_kernel 51 VGPRs,
+// 106 SGPRs (3 spilled to VGPR lanes), 7 waves per SIMD; fr_arith_tables_kernel 38 VGPRs.
+// Two measurement variants, built by tools/bench_fr_arithmetize.py alone (-D, never the product library and no tuning key): FR_ARITH_FULL_TABLE reads
+// w_C^x from ONE table of |V| elements (fr_distribute_powers) without a product; FR_ARITH_ROW_INDEX reads the row of entry e from a host-expanded
+// uint32 array laid behind row_ptr instead of searching.  What has been measured of both is in profiles/fr_arithmetize.md.
+#ifndef FR_ARITH_FULL_TABLE
+#define FR_ARITH_FULL_TABLE 0
+#endif
+#ifndef FR_ARITH_ROW_INDEX
+#define FR_ARITH_ROW_INDEX 0
+#endif
+struct fr_arith_t {
+    fr_mem_t *row, *col, *row_col, *rcv;  // outputs, k elements each; nullptr: skipped
+    const uint64_t* row_ptr;              // rows + 1 values
+    const uint32_t* col_idx;
+    const fr_mem_t* vals;
+    const fr_mem_t *r_lo, *r_hi, *c_lo, *c_hi;  // the power tables of the constraint and the variable domain
+    fr_mem_t one;                               // memory image of 1 (padding)
+    uint32_t fix2[9];                           // MEM2INT^2, true internal form
+    uint32_t k, rows;
+    uint32_t s_r, mask_r, s_c, mask_c;  // table split and 2^lg - 1 per domain
+    uint32_t input_size, period;        // |X| and |V| / |X| >= 2
+};
+// ceil(lg / 2): the split the launch uses
+SV_HD uint32_t fr_arith_split(uint32_t lg) { return (lg + 1) / 2; }
+// entry t of the two tables of one domain (t < 2^s + 2^(lg - s)): lo[x] = w^x as a memory image, hi[y] = w^(y 2^s) in true internal form
+SV_HD void fr_arith_table_at(fr_mem_t* lo, fr_mem_t* hi, const fr_t& omega, uint32_t s, uint32_t t) {
+    const uint32_t n_lo = 1u << s;
+    if (t < n_lo)
+        omega.pow_u64(t).to_mem_mont().store(&lo[t]);
+    else
+        omega.pow_u64((uint64_t)(t - n_lo) << s).store(&hi[t - n_lo]);
+}
+SV_HD uint32_t fr_arith_reindex(uint32_t j, uint32_t input_size, uint32_t period) {
+    if (j < input_size) return j * period;
+    const uint32_t t = j - input_size;
+    return t + t / (period - 1) + 1;
+}
+// the smallest i < rows with row_ptr[i + 1] > e; the caller vouches for e < row_ptr[rows]
+SV_HD uint32_t fr_arith_row_of(const uint64_t* row_ptr, uint32_t rows, uint32_t e) {
+    uint32_t lo = 0, hi = rows - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (row_ptr[mid + 1] > e)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+// output element e < k; nnz = min(row_ptr[rows], k)
+SV_HD void fr_arith_at(const fr_arith_t& a, uint32_t nnz, uint32_t e) {
+    if (e >= nnz) {
+        if (a.row) a.row[e] = a.one;
+        if (a.col) a.col[e] = a.one;
+        if (a.row_col) a.row_col[e] = a.one;
+        if (a.rcv) fr_t::zero().store(&a.rcv[e]);
+        return;
+    }
+#if FR_ARITH_ROW_INDEX
+    const uint32_t xr = ((const uint32_t*)(a.row_ptr + a.rows + 1))[e] & a.mask_r;
+#else
+    const uint32_t xr = fr_arith_row_of(a.row_ptr, a.rows, e) & a.mask_r;
+#endif
+    const uint32_t xc = fr_arith_reindex(a.col_idx[e], a.input_size, a.period) & a.mask_c;
+    const fr_t row = fr_t::load(&a.r_lo[xr & ((1u << a.s_r) - 1)]) * fr_t::load(&a.r_hi[xr >> a.s_r]);
+#if FR_ARITH_FULL_TABLE
+    const fr_t col = fr_t::load(&a.c_lo[xc]);
+#else
+    const fr_t col = fr_t::load(&a.c_lo[xc & ((1u << a.s_c) - 1)]) * fr_t::load(&a.c_hi[xc >> a.s_c]);
+#endif
+    if (a.row) row.store(&a.row[e]);
+    if (a.col) col.store(&a.col[e]);
+    if (!a.row_col && !a.rcv) return;
+    const fr_t p = row * col;
+    if (a.row_col) p.from_mem_mont().store(&a.row_col[e]);
+    if (a.rcv) ((fr_t::load(&a.vals[e]) * p) * fr_t::from_table(a.fix2)).store(&a.rcv[e]);
+}
+#if defined(__HIPCC__)
+static __global__ void __launch_bounds__(256) fr_arith_tables_kernel(fr_mem_t* lo, fr_mem_t* hi, fr_mem_t omega_mem, uint32_t s, uint32_t entries) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < entries) fr_arith_table_at(lo, hi, fr_t::load(&omega_mem).from_mem_mont(), s, t);
+}
+static __global__ void __launch_bounds__(256) fr_arithmetize_kernel(fr_arith_t a) {
+    const uint64_t total = a.row_ptr[a.rows];
+    const uint32_t nnz = total < a.k ? (uint32_t)total : a.k;
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t st = (size_t)gridDim.x * blockDim.x;
+    for (; i < a.k; i += st) fr_arith_at(a, nnz, (uint32_t)i);
+}
+#endif
+
 }  // namespace sv

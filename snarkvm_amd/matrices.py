@@ -21,7 +21,14 @@ and the sums over the variable domain are ONE pass (`snarkvm_hip_fr_selector_fol
     h_0 = sum mu (z_a z_b - z_c) / v_R                          round_functions/second.rs:76-142 with ahp/selectors.rs:88-99 (`rowcheck_witness`)
 
 Rounds 1 and 2 open a proof: w by the gather `snarkvm_hip_fr_witness_evals` between two transforms at |V|, h_0 for all instances of all circuits
-on one coset per domain size with `snarkvm_hip_fr_rowcheck_fold` as both the divisibility test and the sum.  Nothing here builds a circuit index.
+on one coset per domain size with `snarkvm_hip_fr_rowcheck_fold` as both the divisibility test and the sum.
+
+    row, col, row_col, row_col_val on K, the twelve index polynomials, their commitments and the certificate
+                                                                ahp/indexer/indexer.rs:126-260, circuit.rs:142-155, varuna.rs:103-117 (`CircuitIndex`)
+
+The circuit index is built here as well, from the three CSR matrices alone: `snarkvm_hip_fr_arithmetize` computes the arithmetization where it
+will live (`RegisteredArithmetization.from_csr`: every device its own replica), one inverse transform batch per matrix interpolates it, and the
+registered objects, resident polynomials and commitments that `CircuitIndex.build` leaves are the ones the drivers above and the gamma-point opening take.
 """
 import collections
 import ctypes
@@ -247,6 +254,18 @@ class RegisteredArithmetization:
     @classmethod
     def from_matrix(cls, matrix, non_zero_domain_size, variable_domain_size, input_domain_size, constraint_domain_size=None):
         return cls(*matrix_evals(matrix, non_zero_domain_size, variable_domain_size, input_domain_size, constraint_domain_size))
+
+    @classmethod
+    def from_csr(cls, matrix, non_zero_domain_size, lg_constraint, lg_variable, lg_input):
+        """The same object without the host-side arithmetization: the CSR arrays go to the device and every device in use computes its own
+        replica (`snarkvm_hip_fr_arith_register_csr`)."""
+        self = cls.__new__(cls)
+        self.k, self.handle = int(non_zero_domain_size), 0
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().snarkvm_hip_fr_arith_register_csr(ctypes.byref(h), self.k, matrix.rows, matrix.row_ptr.ctypes.data, matrix.col_idx.ctypes.data if matrix.nnz else None,
+                                                                matrix.vals.ctypes.data if matrix.nnz else None, int(lg_constraint), int(lg_variable), int(lg_input)))
+        self.handle = h.value or 0
+        return self
 
     def close(self):
         if self.handle:
@@ -558,3 +577,138 @@ def rowcheck_witness(circuits, lg_max_constraint_domain, device=-1):
             plugin.fr_lincomb_device(mem.ptr, n_max, [p for p, _ in parts], [n for _, n in parts], _mont_limbs([1] * len(parts)))
     out = RowcheckWitness(mem.ptr, n_max, mem, members, counts)
     return out.ensure_divisible() if scope.own else out
+
+
+# ---- the circuit index: arithmetize, interpolate, commit ---------------------------------------------------------------------------------------
+INDEX_KINDS = ("row", "col", "row_col", "row_col_val")  # the order of index_polynomial_labels_single (indexer.rs:104-115) and of a device block
+
+
+def _domain_lg(n):
+    """lg of EvaluationDomain::new(n): the smallest power of two >= n (one element for n = 0)"""
+    return max(0, (int(n) - 1).bit_length())
+
+
+def index_label(circuit_id, kind, matrix):
+    return f"circuit_{circuit_id}_{kind}_{matrix}"
+
+
+class CircuitIndex:
+    """What `AHPForR1CS::index` leaves for a circuit (indexer.rs:46-92, 126-228) - without constraint synthesis, `into_matrix_helper` and the id hash,
+    which stay with the caller: from the three CSR matrices alone, everything the round drivers of this module and the gamma-point opening consume.
+
+        matrices, transposes    RegisteredMatrix of A, B, C and of their transposes (z_M; `LinevalCircuit.transposes`)
+        ariths                  RegisteredArithmetization per matrix, computed on every device from the CSR arrays (`matrix_sumcheck_witness`)
+        polynomials             {label: sonic_pc.ResidentPolynomial}: the twelve index polynomials circuit_{id}_{row,col,row_col,row_col_val}_{a,b,c}
+                                (`Circuit::interpolate_matrix_evals`, circuit.rs:142-150), |K_M| coefficients each, no degree or hiding bound
+        commitments             with a committer key: their LabeledCommitments in label order (`batch_circuit_setup`, varuna.rs:103-117)
+
+    lg_r, lg_c, lg_x, lg_k[m]: the constraint, variable, input and non-zero domains as `index_helper` sizes them (indexer.rs:178-184)."""
+
+    @classmethod
+    def build(cls, a, b, c, num_public, circuit_id, ck=None, device=-1):
+        """a, b, c: SparseMatrix of the same shape (rows = constraints, cols = public + private variables); num_public: the padded public
+        variables; ck: a sonic_pc.CommitterUnionKey, or None for no verifying key.  Per matrix the four evaluation vectors are ONE
+        `snarkvm_hip_fr_arithmetize` into one device block with stride |K_M| and their copy goes through ONE inverse transform batch - every matrix
+        enqueued in one scope, the host waits once.  Call it outside a scope."""
+        from . import sonic_pc
+
+        mats = [a, b, c]
+        if any(m.rows != a.rows or m.cols != a.cols for m in mats):
+            raise ValueError("CircuitIndex.build: A, B and C differ in shape")
+        if _lib.lib().snarkvm_hip_scope_stream():
+            raise ValueError("CircuitIndex.build: call it outside a scope (registration and the commitments wait for the device)")
+        self = cls.__new__(cls)
+        self.circuit_id, self.device = circuit_id, device
+        self.lg_r, self.lg_c, self.lg_x = _domain_lg(a.rows), _domain_lg(a.cols), _domain_lg(num_public)
+        _check_subdomain(1 << self.lg_c, 1 << self.lg_x)
+        self.lg_k = [_domain_lg(m.nnz) for m in mats]
+        self.matrices, self.transposes, self.ariths, self._evals, self._polys = [], [], [], [], []
+        self.polynomials, self.commitments, self._pruned = {}, None, False
+        try:
+            for m, lg in zip(mats, self.lg_k):
+                self.matrices.append(RegisteredMatrix(m))
+                self.transposes.append(RegisteredMatrix(transpose(m, 1 << self.lg_c, 1 << self.lg_x)))
+                self.ariths.append(RegisteredArithmetization.from_csr(m, 1 << lg, self.lg_r, self.lg_c, self.lg_x))
+            csr = []
+            for m, lg in zip(mats, self.lg_k):
+                at_col = (8 * (m.rows + 1) + 31) & ~31
+                at_val = (at_col + 4 * m.nnz + 31) & ~31
+                mem = HipMem(at_val + 32 * max(m.nnz, 1), device)
+                mem.upload(m.row_ptr)
+                if m.nnz:
+                    mem.upload(m.col_idx, at_col)
+                    mem.upload(m.vals, at_val)
+                csr.append((mem, at_col, at_val))
+                self._evals.append(HipMem(32 * 4 << lg, device))
+                self._polys.append(HipMem(32 * 4 << lg, device))
+            with _Scope(self._evals[0].ptr):
+                for m, lg, (mem, at_col, at_val), ev, po in zip(mats, self.lg_k, csr, self._evals, self._polys):
+                    k = 1 << lg
+                    plugin.fr_arithmetize_device(*(ev.ptr + 32 * k * j for j in range(4)), k, m.rows, mem.ptr, mem.ptr + at_col, mem.ptr + at_val, self.lg_r, self.lg_c, self.lg_x)
+                    po.copy_from(0, ev.ptr, 32 * 4 * k)
+                    plugin.NTT_device_batch(lg, [po.ptr + 32 * k * j for j in range(4)], directions=[1] * 4, types=[0] * 4)
+            for mem, _, _ in csr:
+                mem.free()
+            for name, lg, po in zip("abc", self.lg_k, self._polys):
+                for j, kind in enumerate(INDEX_KINDS):
+                    label = index_label(circuit_id, kind, name)
+                    self.polynomials[label] = sonic_pc.ResidentPolynomial(label, po.ptr + (32 * j << lg), 1 << lg)
+            if ck is not None:
+                ordered = [self.polynomials[label] for label in sorted(self.polynomials)]  # varuna.rs:116 sorts the commitments by label
+                self.commitments, _ = sonic_pc.SonicKZG10.commit((1 << max(self.lg_k)) - 1, ck, ordered)
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    def evaluate_index_polynomials(self, point, combiners):
+        """`evaluate_index_polynomials` (indexer.rs:232-260), the core of prove_vk / verify_vk: per matrix the Lagrange coefficients of K_M at `point`
+        in device memory (`snarkvm_hip_fr_lagrange_coefficients`) and the four inner products with the kept evaluation vectors (ONE strided
+        `snarkvm_hip_fr_reduce`), all in one scope; the twelve values meet the combiners in label order on the host.  point: (4,) Montgomery limbs,
+        combiners: (12, 4).  -> (sonic_pc.LinearCombination "circuit_check", the sum as (4,) Montgomery limbs).  Call it outside a scope."""
+        from . import sonic_pc
+
+        if self._pruned:
+            raise ValueError("row_col evaluations are not available")  # matrices.rs: MatrixEvals::evaluate
+        if _lib.lib().snarkvm_hip_scope_stream():
+            raise ValueError("evaluate_index_polynomials: call it outside a scope (the values are needed at once)")
+        tau = np.ascontiguousarray(point, dtype=np.uint64).reshape(1, 4)
+        combiners = np.ascontiguousarray(combiners, dtype=np.uint64).reshape(-1, 4)
+        lags = [HipMem(32 << lg, self.device) for lg in self.lg_k]
+        with _Scope(lags[0].ptr):
+            values = []
+            for lg, ev, lag in zip(self.lg_k, self._evals, lags):
+                _lib.check(_lib.lib().snarkvm_hip_fr_lagrange_coefficients(lag.ptr, lg, tau.ctypes.data, 1))
+                values.append(plugin.fr_reduce_strided_device(plugin.FR_REDUCE_DOT, ev.ptr, lag.ptr, 1 << lg, 4, 1 << lg, b_shared=True))
+        for lag in lags:
+            lag.free()
+        evals = {index_label(self.circuit_id, kind, name): v[j] for name, v in zip("abc", values) for j, kind in enumerate(INDEX_KINDS)}
+        labels = sorted(evals)
+        if combiners.shape[0] < len(labels):
+            raise ValueError("No combiner left")
+        if combiners.shape[0] > len(labels):
+            raise ValueError("Found more combiners than sorted_evals")
+        lc, total = sonic_pc.LinearCombination.empty("circuit_check"), None
+        for label, combiner in zip(labels, combiners):
+            lc.add(combiner, label)
+            total = sonic_pc._fr_add(total, sonic_pc._fr_mul(evals[label], combiner))
+        return lc, total
+
+    def prune_row_col_evals(self):
+        """circuit.rs:151-155: the row_col evaluations are not part of a proving key; `evaluate_index_polynomials` is refused afterwards"""
+        self._pruned = True
+
+    def close(self):
+        """releases the registered objects, the evaluations and the polynomials (every ResidentPolynomial of `polynomials` dangles afterwards);
+        safe to call twice"""
+        for reg in self.matrices + self.transposes + self.ariths:
+            reg.close()
+        for mem in self._evals + self._polys:
+            mem.free()
+        self.matrices, self.transposes, self.ariths, self._evals, self._polys, self.polynomials = [], [], [], [], [], {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown / a dead device: nothing left to do
+            pass

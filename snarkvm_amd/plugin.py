@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "fr_arithmetize_device", "fr_arithmetize", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -264,6 +264,30 @@ def fr_sumcheck_evals(handles, sizes, alpha, beta, scales, want="abf"):
     lists = [(ctypes.c_void_p * max(1, k))(*[o.ctypes.data if o.size else None for o in outs[w]]) if outs[w] is not None else None for w in "abf"]
     _lib.check(_lib.lib().snarkvm_hip_fr_matrix_sumcheck_evals(hs, k, lists[0], lists[1], lists[2], _ptr(al), _ptr(be), _ptr(sc), 0))
     return outs["a"], outs["b"], outs["f"]
+
+
+def fr_arithmetize_device(d_row, d_col, d_row_col, d_row_col_val, k, rows, d_row_ptr, d_col_idx, d_vals, lg_constraint, lg_variable, lg_input):
+    """Extension (no reference counterpart): the arithmetization on K of a CSR matrix that lives in device memory (`snarkvm_hip_fr_arithmetize`,
+    on_device = 1; `matrix_evals` of ahp/matrices.rs:138-195).  d_row_ptr: rows + 1 uint64, d_col_idx: uint32 and d_vals: Montgomery limbs per entry.
+    For entry e = (val, j) of row i: d_row[e] = w_R^i, d_col[e] = w_C^reindex_by_subdomain(j), d_row_col[e] their product, d_row_col_val[e] = val
+    times it; the places from the number of entries up to k hold (1, 1, 1, 0).  Each output (k elements) may be None (skipped).  The contents of the
+    CSR arrays are the caller's contract (include/snarkvm_hip.h).  Inside a scope the call is only enqueued."""
+    _lib.check(_lib.lib().snarkvm_hip_fr_arithmetize(_dp(d_row), _dp(d_col), _dp(d_row_col), _dp(d_row_col_val), int(k), int(rows), _dp(d_row_ptr), _dp(d_col_idx),
+                                                     _dp(d_vals), int(lg_constraint), int(lg_variable), int(lg_input), 1))
+
+
+def fr_arithmetize(k, rows, row_ptr, col_idx, vals, lg_constraint, lg_variable, lg_input, want=("row", "col", "row_col", "row_col_val")):
+    """The same on host arrays (on_device = 0): -> (row, col, row_col, row_col_val) as (k, 4) arrays, None for the outputs not in `want`."""
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64).reshape(-1)
+    col_idx = np.ascontiguousarray(col_idx, dtype=np.uint32).reshape(-1)
+    vals = np.ascontiguousarray(vals, dtype=np.uint64).reshape(-1, 4)
+    if row_ptr.shape[0] != int(rows) + 1 or col_idx.shape[0] != vals.shape[0]:
+        raise ValueError("length mismatch")
+    outs = [np.zeros((int(k), 4), dtype=np.uint64) if w in want else None for w in ("row", "col", "row_col", "row_col_val")]
+    p = lambda x: _ptr(x) if x is not None and x.size else None  # noqa: E731
+    _lib.check(_lib.lib().snarkvm_hip_fr_arithmetize(p(outs[0]), p(outs[1]), p(outs[2]), p(outs[3]), int(k), int(rows), _ptr(row_ptr), p(col_idx), p(vals),
+                                                     int(lg_constraint), int(lg_variable), int(lg_input), 0))
+    return tuple(outs)
 
 
 def msm(points, scalars):

@@ -188,6 +188,8 @@ class SonicKZG10:
         Montgomery limbs (required when a polynomial is hiding).  Returns ([LabeledCommitment], [KZGRandomness]), in input order.
         All commitments of the call are ONE batched device launch."""
         items = list(polynomials)
+        if items and all(isinstance(p, ResidentPolynomial) for p in items):
+            return SonicKZG10.commit_resident(max_degree, ck, items)
         off0, n0, off1, n1, scal, rands = [], [], [], [], [], []
         for p in items:
             check_degrees_and_bounds(max_degree, ck.enforced_degree_bounds, p)
@@ -231,6 +233,47 @@ class SonicKZG10:
             _lib.check(_lib.lib().snarkvm_hip_msm_registered_batch_ex(outs.ctypes.data, ck._h, k, arr(off0), arr(n0), arr(off1), arr(n1), ptrs, 0, 1, 0))
         affine = kzg10.to_affine(outs) if k else np.zeros(0, dtype=G1_AFFINE)
         return [LabeledCommitment(p.label, affine[i], p.degree_bound) for i, p in enumerate(items)], rands
+
+    @staticmethod
+    def commit_resident(max_degree, ck, polynomials):
+        """`commit` over non-hiding `ResidentPolynomial`s (what `commit` hands a list made of them alone): the supports of all of them in one
+        scope of its own (`snarkvm_hip_fr_support`: trimmed length for check_degree_is_too_large, leading zeros skipped by offset), then ONE
+        batched MSM over the registered powers with the coefficients read where they live.  Refused inside a caller's scope."""
+        from . import plugin
+
+        L = _lib.lib()
+        if L.snarkvm_hip_scope_stream():
+            raise PCError("commit_resident: the supports of the polynomials are needed at once - not inside a scope")
+        items = list(polynomials)
+        views = []
+        for p in items:
+            check_degrees_and_bounds(max_degree, ck.enforced_degree_bounds, p)
+            if p.hiding_bound is not None:
+                raise PCError(f"commit_resident: {p.label} is hiding - commit its downloaded coefficients with an rng")
+            view = ck.shifted_powers(p.degree_bound) if p.degree_bound is not None else ck.powers()
+            if view is None:
+                raise PCError(f"UnsupportedDegreeBound({p.degree_bound})")
+            views.append(view)
+        anchor = next((p.ptr for p in items if p.n), 0)
+        if anchor:
+            _lib.check(L.snarkvm_hip_scope_begin(ctypes.c_void_p(anchor)))
+        try:
+            supports = [plugin.fr_support_device(p.ptr, p.n) if p.n else np.zeros(3, dtype=np.uint64) for p in items]
+        finally:
+            if anchor:
+                _lib.check(L.snarkvm_hip_scope_end())
+        k = len(items)
+        off0, n0, ptrs = [], [], []
+        for p, view, s in zip(items, views, supports):
+            lz, plain = kzg10.resident_range(int(s[0]), int(s[1]), view.size())
+            off0.append(view.off + lz), n0.append(plain), ptrs.append((p.ptr + 32 * lz) if plain else anchor)  # an empty instance reads nothing
+        outs = np.zeros(k, dtype=G1_PROJECTIVE)
+        if k:
+            arr = lambda v: (ctypes.c_size_t * k)(*v)  # noqa: E731
+            _lib.check(L.snarkvm_hip_msm_registered_batch_ex(outs.ctypes.data, ck._h, k, arr(off0), arr(n0), arr([v._gamma_offset for v in views]), arr([0] * k),
+                                                             (ctypes.c_void_p * k)(*ptrs), 1, 1, 0))
+        affine = kzg10.to_affine(outs) if k else np.zeros(0, dtype=G1_AFFINE)
+        return [LabeledCommitment(p.label, affine[i], p.degree_bound) for i, p in enumerate(items)], [KZGRandomness.empty() for _ in items]
 
     @staticmethod
     def combine_polynomials(coeffs_polys_rands):
