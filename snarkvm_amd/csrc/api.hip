@@ -4,7 +4,7 @@
 // reference: a lazily constructed per-process runtime over every selected GPU (device arenas, streams, twiddle tables), a
 // pool of (device, stream) resource tokens handed to concurrent callers, staging of the caller's host buffers, the
 // point-range split of one MSM over the GPUs with a host-side combine, error reporting as RustError.
-// Fr entry points: api_fr.hip; point encoding + setup-time group operations: api_serde.hip; G2: api_g2.hip.
+// Fr entry points: api_fr.hip (NTT, polymul), api_poly.hip (polynomial passes), api_varuna.hip (prover rounds); point encoding + setup-time group operations: api_serde.hip; G2: api_g2.hip.
 #include "msm_batch.hip.h"
 #include "ffl.hip.h"
 

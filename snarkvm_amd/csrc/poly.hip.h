@@ -908,7 +908,7 @@ static __global__ void __launch_bounds__(FR_REDUCE_B) fr_support_final_kernel(co
 // y = M x for an R1CS matrix M in CSR form (z_M = M z, snark/varuna/ahp/prover/round_functions/mod.rs:131-188) or for its transpose
 // (M(alpha, .) = M^T l_alpha, third.rs:303-306).  R1CS rows hold a handful of entries, but a transposed matrix has a few rows - the column of
 // the constant one, of heavily used variables - that collect a large share of all non-zeros, so work is laid out by ENTRIES, on the host, once,
-// when the matrix is registered (api_fr.hip: fr_spmv_layout):
+// when the matrix is registered (api_varuna.hip: fr_spmv_layout):
 //   segments  every row is cut into segments of at most `seg` entries: table of fr_spmv_seg_t {row, first entry, count, part}.  part ==
 //             FR_SPMV_SOLE: the only segment of its row; otherwise the slot of this segment's partial sum (a row's slots are consecutive, in
 //             segment order).

@@ -1,4 +1,4 @@
-"""The Fr vector passes of a Varuna round (snarkvm_amd/csrc/poly.hip.h, api_fr.hip) at prover sizes, on device memory and strided.
+"""The Fr vector passes of a Varuna round (snarkvm_amd/csrc/poly.hip.h, api_poly.hip) at prover sizes, on device memory and strided.
 
 Four groups, every result bit for bit against oracle/cpu.py's restatement of the same reference function (Fr results are unique
 Montgomery residues: no tolerances):
@@ -29,7 +29,7 @@ OPS = ("add", "sub", "mul", "mul_sub", "scale", "sub_scalar", "axpy", "rsub_scal
 NEEDS_B = {"add", "sub", "mul", "mul_sub", "axpy"}
 NEEDS_S = {"scale", "sub_scalar", "axpy", "rsub_scalar"}
 
-# the caps as they stand in api_fr.hip: fr_grid 8192 x 256 threads, fr_mul_device / fr_convert_device 4096 x 256, inversion / powers T = 2^17
+# the caps as they stand in fr_call.hip.h (fr_grid 8192 x 256 threads, powers T = 2^17), api_fr.hip (fr_mul_device / fr_convert_device 4096 x 256) and api_poly.hip (inversion T = 2^17)
 T_CAP = 1 << 17
 N_TWO_TRIPS = (1 << 21) + (1 << 20) + 12345       # in (2^21, 2^22), not a multiple of 256: a partial second trip of every grid-stride loop
 N_T_CAPPED = (1 << 22) + 3 * (1 << 17) + 77        # T at its cap, 35 or 36 elements per thread, ragged tail

@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 R = rc.R
 CHUNK = rc.CHUNK
 FILL = 0x5A5A5A5A5A5A5A5A
-GRID_CAP = 8192 * 256  # the cap as it stands in api_fr.hip: fr_grid, 8192 workgroups of 256 threads
+GRID_CAP = 8192 * 256  # the cap as it stands in fr_call.hip.h: fr_grid, 8192 workgroups of 256 threads
 
 
 class Block:
