@@ -172,7 +172,7 @@ RustError snarkvm_hip_polymul_device(void *d_out, size_t pcount, const void *con
  * - snarkvm_hip_ntt_device, _ntt_device_batch, _polymul_device, _fr_mul_device, _fr_convert_device, _memcpy_d2d, _memset and the snarkvm_hip_fr_* vector
  * kernels (snarkvm_hip_fr_lincomb and snarkvm_hip_fr_spmv among them) with on_device = 1 - are enqueued on one stream, in call order, and return without waiting; snarkvm_hip_scope_end waits once.  The
  * 32-byte host `remainder` of snarkvm_hip_fr_divide_by_linear with on_device = 1 is delivered by scope_end, and so are the host results of
- * snarkvm_hip_fr_reduce[_strided], snarkvm_hip_fr_support[_strided] and the counts of snarkvm_hip_fr_rowcheck_fold over device operands (the same mechanism: parked in pinned memory, copied
+ * snarkvm_hip_fr_reduce[_strided], snarkvm_hip_fr_evaluate, snarkvm_hip_fr_support[_strided] and the counts of snarkvm_hip_fr_rowcheck_fold over device operands (the same mechanism: parked in pinned memory, copied
  * to the caller's buffer when the scope is flushed - the buffer must stay valid until then).  Every other call (MSMs,
  * host buffers, a pointer on another GPU) first waits for the scope's queued work, so results are the same as without a scope - and
  * then runs on the scope's own stream: a thread inside a scope never waits for a free stream.  Scopes do not nest; a scope must be
@@ -522,6 +522,29 @@ RustError snarkvm_hip_fr_reduce_strided(int op, void *results, const void *a, co
 RustError snarkvm_hip_fr_support(uint64_t *out3, const void *v, size_t n, int on_device);
 RustError snarkvm_hip_fr_support_strided(uint64_t *out, const void *v, size_t n, size_t count, size_t stride);
 
+/* Evaluation of many polynomials, each at its own point, in one launch sequence (csrc/poly.hip.h: fr_evaluate_kernel, the member of the reduction
+ * family that carries the powers of the point; fr_reduce_final_kernel folds the per-workgroup partials): results[k] = sum_{i < lens[k]}
+ * polys[k][i] * points[k]^i - DensePolynomial::evaluate (fft/polynomial/dense.rs:98-114), the `evaluations` of a proof (snark/varuna/varuna.rs:583-592)
+ * and, by linearity, every value of a linear combination (get_lc_eval, ahp/ahp.rs:469-487): each coefficient is read once, coalesced, five products
+ * and one Montgomery reduction per four coefficients.  0^0 = 1 (a zero point yields polys[k][0]); the zero polynomial and a length of 0 yield 0;
+ * trailing zero coefficients change nothing.
+ *  - polys, lens and points (count x 32 bytes, Montgomery form, ONE point per member) are HOST arrays, read during the call and not retained;
+ *    results is count x 32 bytes of HOST memory; on_device governs every polys[k].  Members may overlap and repeat and are never written.  Equal
+ *    points are recognised by their bytes and share their powers; a call carries any number of distinct points and any number of members up to
+ *    65535 (one kernel launch holds 64 members at 3 distinct points: the call splits itself, and the results depend on no split).
+ *  - count == 0: success, nothing is touched.  Every lens[k] == 0: results are zero-filled, no device is needed.  A member pointer may be NULL
+ *    iff its length is 0.
+ *  - With host operands (on_device = 0) the distinct member buffers are staged into one lane buffer, each uploaded once, and the values are there on
+ *    return.  With device operands inside a snarkvm_hip_scope the call is only enqueued on the scope's stream, in order, and the values are
+ *    delivered when the scope is flushed (snarkvm_hip_scope_end), like the result of snarkvm_hip_fr_reduce.
+ *  - Refused with hipErrorInvalidValue before anything is launched (and, but for the last, before a device is needed), `results` untouched: a NULL
+ *    results, polys, lens or points with count > 0; a NULL member of non-zero length; a length above 2^29; count > 65535; with on_device = 1,
+ *    members on different devices.
+ *  - Workspace (one partial per workgroup and member, at most 2048 per member, the results, and the table of powers of one launch: 72 KB per
+ *    point, filled by a launch of its own in front of every evaluation launch) comes from the calling lane; the powers z^(2^i) the table is built
+ *    from travel as kernel arguments.  A repeated call grows nothing (snarkvm_hip_alloc_stats). */
+RustError snarkvm_hip_fr_evaluate(void *results, size_t count, const void *const *polys, const size_t *lens, const void *points, int on_device);
+
 /* Sparse matrix times vector over a REGISTERED matrix (csrc/poly.hip.h: fr_spmv_seg_kernel, fr_spmv_fix_kernel): the one product of the Varuna
  * prover that is not dense - z_M = M z for M in {A, B, C} (snark/varuna/ahp/prover/round_functions/mod.rs:131-188) and M(alpha, .) = M^T l_alpha
  * (third.rs:303-306, with l_alpha left in device memory by snarkvm_hip_fr_lagrange_coefficients and the result going on to snarkvm_hip_ntt_device).
@@ -766,6 +789,19 @@ int snarkvm_hip_selftest_fr_rowcheck_geometry(uint32_t *out2);
 int snarkvm_hip_selftest_fr_reduce(int op, void *out, const void *a, const void *b, size_t n, uint32_t blocks, uint32_t threads);
 int snarkvm_hip_selftest_fr_support(uint64_t *out3, const void *v, size_t n, uint32_t blocks, uint32_t threads);
 int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t *out4);
+/* snarkvm_hip_fr_evaluate over host memory with the CPU in the kernels' place, over a GIVEN launch geometry (blocks >= 1 workgroups of threads = 64,
+ * 128 or 256 per member, blocks x threads <= 2^19): the same validation, the same grouping of the points and split into launches, every thread's
+ * Horner walk and power of the point, thread 0's factor on the workgroup's sum, the table of powers both come from and every combine step through
+ * the kernels' own routines (csrc/poly.hip.h: fr_evaluate_table_entry, fr_evaluate_thread, fr_evaluate_block, fr_reduce_thread), the trees level by
+ * level, the last launch included.  0, or -1 when the
+ * arguments are refused or the kernel does not take the geometry.  fr_evaluate_geometry: out (8 values) = {workgroups per member, threads per
+ * workgroup} the device call launches for a longest member of n_max, the cap on the workgroups, the coefficients per Montgomery reduction, the
+ * members and the distinct points one launch holds, how the power of the thread index is formed (2: one factor per thread and one per workgroup,
+ * both from a table in lane workspace; 0: the same two factors from the set bits of the exponent, in place; 1: per thread alone, in place) and the
+ * bits of a thread index the powers z^(2^i) cover. */
+int snarkvm_hip_selftest_fr_evaluate(void *results, size_t count, const void *const *polys, const size_t *lens, const void *points, uint32_t blocks,
+                                     uint32_t threads);
+int snarkvm_hip_selftest_fr_evaluate_geometry(size_t n_max, uint32_t *out);
 /* snarkvm_hip_fr_spmv (count = 1) over host memory with the CPU in the kernels' place, for a GIVEN segment size `seg` >= 1 and lane-group width
  * (4, 8, 16 or 64): the validation and the segmentation of snarkvm_hip_fr_matrix_register, every lane through the kernels' own accumulate routine
  * (csrc/poly.hip.h: fr_spmv_lane over Fp::sum_of_products), the butterfly level by level, the partials and the fix-up launch in the same order.  0, or

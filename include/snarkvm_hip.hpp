@@ -257,6 +257,19 @@ inline void fr_sum(void* result, const void* a, size_t n, bool on_device) { chec
 inline void fr_inner_product(void* result, const void* a, const void* b, size_t n, bool on_device) {
     check(snarkvm_hip_fr_reduce(SNARKVM_HIP_FR_REDUCE_DOT, result, a, b, n, on_device ? 1 : 0));
 }
+// Evaluation of many polynomials, each at its own point, in one launch sequence (snarkvm_hip.h: snarkvm_hip_fr_evaluate): results[k] =
+// polys[k](points[k]) - DensePolynomial::evaluate, the `evaluations` of a proof.  results and points: polys.size() x 32 bytes of HOST memory,
+// Montgomery form, one point per member (equal points share their powers); on_device governs every polys[k].data.  No member is written;
+// members may repeat and overlap.  With on_device inside a Scope the call is only enqueued and the values arrive when the Scope ends.
+inline void fr_evaluate(void* results, const std::vector<DevicePoly>& polys, const void* points, bool on_device) {
+    std::vector<const void*> pptrs;
+    std::vector<size_t> plens;
+    for (auto& p : polys) {
+        pptrs.push_back(p.data);
+        plens.push_back(p.len);
+    }
+    check(snarkvm_hip_fr_evaluate(results, pptrs.size(), pptrs.data(), plens.data(), points, on_device ? 1 : 0));
+}
 // trimmed_len (0: the zero vector; degree = max(trimmed_len, 1) - 1), leading_zeros (n: the zero vector), nonzero
 struct FrSupport {
     uint64_t trimmed_len, leading_zeros, nonzero;

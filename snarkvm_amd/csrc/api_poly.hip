@@ -3,6 +3,9 @@
 // with its host twin and geometry hook.  The frame they share: fr_call.hip.h.
 #include "fr_call.hip.h"
 
+#include <array>
+#include <map>
+
 static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
 
 // the butterflies of fr_block_sum / fr_block_support over `vals` (one per thread): lanes l and l ^ off meet, then the waves' values
@@ -791,6 +794,151 @@ int snarkvm_hip_selftest_fr_support(uint64_t* out3, const void* v, size_t n, uin
 int snarkvm_hip_selftest_fr_reduce_geometry(size_t n, uint32_t* out4) {
     if (!out4) return -1;
     out4[0] = fr_reduce_blocks(n), out4[1] = FR_REDUCE_B, out4[2] = FR_REDUCE_BLOCKS_MAX, out4[3] = FR_REDUCE_G;
+    return 0;
+}
+
+// ---- evaluation of many polynomials, each at its point (poly.hip.h: fr_evaluate_kernel) -----------------------------------------
+static constexpr size_t FR_EVALUATE_MAX_LEN = (size_t)1 << 29;
+// nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  n_max: the longest member.
+static const char* fr_evaluate_check(const void* results, size_t count, const void* const* polys, const size_t* lens, const void* points, size_t& n_max) {
+    if (!results || !polys || !lens || !points) return "missing argument";
+    if (count > 65535) return "more than 65535 members";
+    n_max = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (lens[k] > FR_EVALUATE_MAX_LEN) return "a member is longer than 2^29";
+        if (lens[k] && !polys[k]) return "null member of non-zero length";
+        n_max = std::max(n_max, lens[k]);
+    }
+    return nullptr;
+}
+// What the device call and its host replay share: the distinct points (recognised by their bytes) with their powers for T threads per member, the
+// members grouped by point (stable: the caller's order inside a group) and cut into launches of at most FR_EVALUATE_MEMBERS members and
+// FR_EVALUATE_POINTS points.  The point is converted to the true internal form HERE, once per distinct point (poly.hip.h: the pass's one fix-up).
+static std::vector<fr_evaluate_t> fr_evaluate_plan(size_t count, const void* const* polys, const size_t* lens, const void* points, size_t T) {
+    std::vector<std::array<uint8_t, sizeof(fr_mem_t)>> distinct;
+    std::vector<std::vector<size_t>> members;  // per distinct point, in the order of first appearance
+    {
+        std::map<std::array<uint8_t, sizeof(fr_mem_t)>, size_t> seen;
+        for (size_t k = 0; k < count; k++) {
+            std::array<uint8_t, sizeof(fr_mem_t)> key;
+            memcpy(key.data(), (const uint8_t*)points + sizeof(fr_mem_t) * k, sizeof(fr_mem_t));
+            const auto it = seen.emplace(key, distinct.size());
+            if (it.second) distinct.push_back(key), members.emplace_back();
+            members[it.first->second].push_back(k);
+        }
+    }
+    std::vector<fr_evaluate_t> plan;
+    int np = FR_EVALUATE_POINTS;  // points of the last table; a full one opens the next
+    for (size_t q = 0; q < distinct.size(); q++) {
+        fr_evaluate_point_t P;
+        {
+            const fr_mem_t z_mem = fr_mem_from_host(distinct[q].data());
+            fr_t s = fr_t::load(&z_mem).from_mem_mont();
+            const fr_t Z = s.pow_u64(T);
+            for (int i = 0; i < FR_EVALUATE_BITS; i++, s = s.sqr())
+                for (int l = 0; l < 9; l++) P.pw[i][l] = s.v[l];
+            fr_t Zg = fr_t::one();
+            for (int g = 0; g <= FR_EVALUATE_G; g++, Zg = Zg * Z)
+                for (int l = 0; l < 9; l++) P.Z[g][l] = Zg.v[l];
+        }
+        bool placed = false;  // is P in the last table of the plan?
+        for (size_t k : members[q]) {
+            if (plan.empty() || plan.back().count == (uint32_t)FR_EVALUATE_MEMBERS || (!placed && np == FR_EVALUATE_POINTS)) plan.emplace_back(), np = 0, placed = false;
+            fr_evaluate_t& t = plan.back();
+            if (!placed) t.pt[np++] = P, t.points = (uint32_t)np, placed = true;
+            const uint32_t m = t.count++;
+            t.p[m] = (const fr_mem_t*)polys[k], t.len[m] = (uint32_t)lens[k], t.point[m] = (uint16_t)(np - 1), t.row[m] = (uint16_t)k;
+        }
+    }
+    return plan;
+}
+RustError snarkvm_hip_fr_evaluate(void* results, size_t count, const void* const* polys, const size_t* lens, const void* points, int on_device) {
+    if (count == 0) return ok();
+    size_t n_max = 0;
+    if (const char* why = fr_evaluate_check(results, count, polys, lens, points, n_max)) return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_evaluate: ") + why);
+    if (n_max == 0) {
+        memset(results, 0, sizeof(fr_mem_t) * count);
+        return ok();
+    }
+    const void* first = nullptr;
+    for (size_t k = 0; k < count && !first; k++)
+        if (lens[k]) first = polys[k];
+    API_BEGIN_DEV(device_for(first, on_device ? 1 : 0))
+    const unsigned blocks = fr_reduce_blocks(n_max);
+    std::vector<fr_evaluate_t> plan = fr_evaluate_plan(count, polys, lens, points, (size_t)blocks * FR_REDUCE_B);
+    fr_host_pack_t pack(c);
+    if (on_device) {
+        for (size_t k = 0; k < count; k++)
+            if (lens[k]) fr_same_device(c, polys[k], "fr_evaluate: members live on different devices");
+    } else {  // every distinct buffer once, at the longest length it is read with
+        std::map<const void*, size_t> longest;
+        for (size_t k = 0; k < count; k++)
+            if (lens[k]) longest[polys[k]] = std::max(longest[polys[k]], lens[k]);
+        size_t total = 0;
+        for (const auto& e : longest) total += e.second;
+        pack.begin(0, total);
+        std::map<const void*, const fr_mem_t*> staged;
+        for (const auto& e : longest) staged[e.first] = pack.in(e.first, e.second);
+        for (fr_evaluate_t& t : plan)
+            for (uint32_t m = 0; m < t.count; m++)
+                if (t.len[m]) t.p[m] = staged[t.p[m]];
+    }
+    // workspace: count x blocks partials, then the count results, then the table of powers of one launch (every launch fills it anew: the stream is in order)
+    const size_t tab_n = fr_evaluate_table_size(FR_REDUCE_B, blocks);
+    c.poly[4].ensure(sizeof(fr_mem_t) * (count * ((size_t)blocks + 1) + tab_n));
+    fr_mem_t* parts = c.poly[4].as<fr_mem_t>();
+    fr_mem_t* dres = parts + count * (size_t)blocks;
+    fr_mem_t* tab = dres + count;
+    for (const fr_evaluate_t& t : plan) {
+        if (tab_n) hipLaunchKernelGGL(fr_evaluate_powers_kernel, dim3((FR_REDUCE_B + blocks + FR_REDUCE_B - 1) / FR_REDUCE_B, t.points), dim3(FR_REDUCE_B), 0, c.stream, tab, (uint32_t)FR_REDUCE_B, (uint32_t)blocks, t);
+        hipLaunchKernelGGL(fr_evaluate_kernel, dim3(blocks, t.count), dim3(FR_REDUCE_B), 0, c.stream, parts, (const fr_mem_t*)tab, t);
+    }
+    hipLaunchKernelGGL(fr_reduce_final_kernel, dim3(1, (unsigned)count), dim3(FR_REDUCE_B), 0, c.stream, (int)FR_REDUCE_SUM, (const fr_mem_t*)parts, (size_t)blocks, dres);
+    HIP_TRY(hipGetLastError());
+    // device operands inside a scope: delivered by snarkvm_hip_scope_end; host operands: the call waits below, the values are there on return
+    c.host_result(results, dres, sizeof(fr_mem_t) * count, on_device != 0);
+    fr_call_done(c, on_device);
+    API_END
+}
+// The same call on host memory with the CPU in the kernels' place, over a GIVEN geometry (blocks workgroups of `threads` threads, threads = 64, 128
+// or 256, blocks x threads <= 2^FR_EVALUATE_BITS): the same plan, per launch the table of powers entry by entry through fr_evaluate_table_entry, every thread
+// through fr_evaluate_thread, the workgroup's tree level by level, thread 0's fr_evaluate_block, the partials through memory, the last launch as in
+// snarkvm_hip_selftest_fr_reduce.  0, or -1 when the arguments or the
+// geometry are refused.
+int snarkvm_hip_selftest_fr_evaluate(void* results, size_t count, const void* const* polys, const size_t* lens, const void* points, uint32_t blocks, uint32_t threads) {
+    if (!fr_reduce_geometry_ok(blocks, threads) || (uint64_t)blocks * threads > (uint64_t)1 << FR_EVALUATE_BITS) return -1;
+    if (count == 0) return 0;
+    size_t n_max = 0;
+    if (fr_evaluate_check(results, count, polys, lens, points, n_max)) return -1;
+    const auto add = [](const fr_t& x, const fr_t& y) { return x + y; };
+    std::vector<fr_mem_t> parts(count * (size_t)blocks), tab(fr_evaluate_table_size(threads, blocks));
+    for (const fr_evaluate_t& t : fr_evaluate_plan(count, polys, lens, points, (size_t)blocks * threads)) {
+        if (!tab.empty())  // fr_evaluate_powers_kernel
+            for (uint32_t q = 0; q < t.points; q++)
+                for (uint32_t e = 0; e < threads + blocks; e++) fr_evaluate_table_entry(t.pt[q], e, threads).store(&tab[(size_t)q * (threads + blocks) + e]);
+        for (uint32_t y = 0; y < t.count; y++)
+            for (uint32_t x = 0; x < blocks; x++) {
+                std::vector<fr_t> vals(threads);
+                for (uint32_t tid = 0; tid < threads; tid++) vals[tid] = fr_evaluate_thread(t, tab.data(), y, x, tid, threads, blocks);
+                fr_evaluate_block(t, tab.data(), y, x, threads, blocks, fr_block_tree_host(vals, fr_t::zero(), add)).store(&parts[(size_t)t.row[y] * blocks + x]);
+            }
+    }
+    fr_mem_t* res = (fr_mem_t*)results;
+    for (size_t k = 0; k < count; k++) {
+        std::vector<fr_t> vals(FR_REDUCE_B);
+        for (uint32_t tid = 0; tid < (uint32_t)FR_REDUCE_B; tid++) vals[tid] = fr_reduce_thread<FR_REDUCE_SUM>(parts.data() + k * (size_t)blocks, nullptr, blocks, tid, FR_REDUCE_B);
+        fr_mem_t r;
+        fr_reduce_finish(FR_REDUCE_SUM, fr_block_tree_host(vals, fr_t::zero(), add)).store(&r);
+        memcpy(&res[k], &r, sizeof r);
+    }
+    return 0;
+}
+// what snarkvm_hip_fr_evaluate launches for a longest member of n_max: out8 = {workgroups per member, threads per workgroup, the cap on workgroups,
+// coefficients per Montgomery reduction, members per launch, distinct points per launch, how z^t is formed (FR_EVALUATE_POW), the bits of a thread index}
+int snarkvm_hip_selftest_fr_evaluate_geometry(size_t n_max, uint32_t* out) {
+    if (!out) return -1;
+    out[0] = fr_reduce_blocks(n_max), out[1] = FR_REDUCE_B, out[2] = FR_REDUCE_BLOCKS_MAX, out[3] = FR_EVALUATE_G;
+    out[4] = FR_EVALUATE_MEMBERS, out[5] = FR_EVALUATE_POINTS, out[6] = FR_EVALUATE_POW, out[7] = FR_EVALUATE_BITS;
     return 0;
 }
 

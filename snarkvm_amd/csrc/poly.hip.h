@@ -904,6 +904,124 @@ static __global__ void __launch_bounds__(FR_REDUCE_B) fr_support_final_kernel(co
 }
 #endif
 
+// ---- evaluation: many polynomials, each at its point -> one value each ----------------------------------------------------------
+// p_k(z_k) = sum_i c_k[i] z_k^i (DensePolynomial::evaluate, dense.rs:98-114; the `evaluations` of a proof, varuna.rs:583-592, and by linearity
+// every get_lc_eval, ahp.rs:469-487): the member of the reduction family above that carries the powers of the point.  The same two launches:
+//   launch 1  fr_evaluate_kernel: grid (blocks, members of this launch), T = blocks x blockDim threads per member.  Thread t owns the indices
+//             t, t + T, t + 2T, ... of its member - coalesced like fr_reduce_thread - and forms sum_j c[t + jT] Z^j with Z = z^T by a Horner walk
+//             from the top: FR_EVALUATE_G coefficients and the accumulator per step through ONE Fp::sum_of_products with {1, Z, .., Z^G}
+//             (G + 1 products and one Montgomery reduction per G coefficients; the partial top group goes by single Horner steps).  The factor
+//             z^t is split by linearity: a thread multiplies its value by z^threadIdx.x, the workgroup's sum - fr_block_sum, as in
+//             fr_reduce_kernel - is multiplied by z^(blockIdx.x blockDim.x) ONCE, by thread 0, and that is the partial it writes.  Both factors
+//             are ONE product each against a table in lane workspace (per point blockDim + gridDim entries, 72 KB for the full grid), which
+//   launch 0  fr_evaluate_powers_kernel fills from the set bits of the exponent against z^(2^i): at most 18 products per entry, once per point
+//             and launch instead of 8 per thread and 11 per workgroup of launch 1 - at proof sizes a thread owns one to eight coefficients, and
+//             forming its power in place (FR_EVALUATE_POW 0, measured: profiles/fr_evaluate.md) costs more than its whole walk.
+//   launch 2  fr_reduce_final_kernel (op SUM) folds the `blocks` partials of every member: the existing combine, no twin.
+// A workgroup that lies wholly behind the end of its member sums zeros and writes a zero partial; no atomics; field addition is exact, so the 32
+// bytes of a result depend on neither T, the split into launches nor the grouping of the points.
+// Representation.  Coefficients are streamed RAW: the memory image of c, read as an internal value, is "shifted" (the top of this file).  Every
+// power of a point in the table (z^(2^i), Z^g, and the 1 of the group) is in the TRUE internal form - the host ran from_mem_mont on the point
+// ONCE per distinct point, the single fix-up of this pass - so every product here is (true) x (shifted) = shifted, sums of shifted values are
+// shifted, and what thread 0 stores is the memory image of the result: neither kernel converts anything (launch 2 runs with op SUM, whose
+// fr_reduce_finish is the identity).  sum_of_products' operand conditions hold: the first factors are table entries (canonical), the second
+// are memory images (< 2^256) or the accumulator (canonical).
+// 0^0 = 1 falls out: for z = 0 every table entry but the group's 1 is zero, thread 0 of workgroup 0 has no bit set and keeps c[0], everything
+// else is multiplied by zero.  Length 0: every thread is behind the end.
+// The table travels BY KERNEL ARGUMENT like fr_lincomb_t: a member is its pointer, its length, the index of its point in the launch and the row
+// of its partials (its place in the caller's list, < 65536); pointers, lengths and powers are wave-uniform scalar loads.  A list with more
+// members or more distinct points than one table holds takes further launches; launch 2 runs once over all rows.
+#ifndef FR_EVALUATE_G
+#define FR_EVALUATE_G 4  // coefficients per Montgomery reduction; a -D override (with the one below) builds the variants tools/bench_fr_evaluate.py compares
+#endif
+#ifndef FR_EVALUATE_POW
+#define FR_EVALUATE_POW 2  // how z^t is formed - 2: the two factors from the table of launch 0; 0: the same two factors from the set bits, in place; 1: every thread forms all of z^t
+#endif
+static_assert(FR_EVALUATE_POW >= 0 && FR_EVALUATE_POW <= 2, "FR_EVALUATE_POW: 0, 1 or 2");
+static_assert(FR_EVALUATE_G >= 1 && FR_EVALUATE_G <= 5, "fr_evaluate_walk: G coefficients and the accumulator share one sum_of_products (at most 6 terms)");
+static constexpr int FR_EVALUATE_MEMBERS = 64;  // per launch
+static constexpr int FR_EVALUATE_POINTS = 3;    // distinct points per launch
+static constexpr int FR_EVALUATE_BITS = 19;     // t < FR_REDUCE_BLOCKS_MAX x FR_REDUCE_B = 2^19
+static_assert((uint64_t)FR_REDUCE_BLOCKS_MAX * FR_REDUCE_B <= (uint64_t)1 << FR_EVALUATE_BITS, "fr_evaluate_scale: every thread index must fit the table of z^(2^i)");
+struct fr_evaluate_point_t {
+    uint32_t pw[FR_EVALUATE_BITS][9];   // z^(2^i), true internal form
+    uint32_t Z[FR_EVALUATE_G + 1][9];   // Z^g, g = 0 .. G, Z = z^T: true internal form (Z[0] is the internal 1)
+};
+struct fr_evaluate_t {  // 64 x 16 B + 3 x (19 + 5) x 36 B + 8 = 3624 B of the 4 KB of kernel arguments
+    const fr_mem_t* p[FR_EVALUATE_MEMBERS];
+    uint32_t len[FR_EVALUATE_MEMBERS];
+    uint16_t point[FR_EVALUATE_MEMBERS];  // index into pt
+    uint16_t row[FR_EVALUATE_MEMBERS];    // partials[row * blocks + workgroup]
+    fr_evaluate_point_t pt[FR_EVALUATE_POINTS];
+    uint32_t count, points;  // members and points in use
+};
+// sum_j c[first + j step] Z^j over the indices below n, a shifted value; zero for a thread behind the end
+SV_HD fr_t fr_evaluate_walk(const fr_mem_t* c, size_t n, size_t first, size_t step, const fr_evaluate_point_t& P) {
+    constexpr int G = FR_EVALUATE_G;
+    if (first >= n) return fr_t::zero();
+    const size_t cnt = (n - first + step - 1) / step;  // the indices this thread owns
+    size_t j = cnt;
+    fr_t acc = fr_t::zero();
+    if (j % G) {  // the partial top group by single Horner steps, down to a multiple of G; the top coefficient itself costs no product
+        const fr_t Z1 = fr_t::from_table(P.Z[1]);
+        acc = fr_t::load(&c[first + --j * step]);
+#pragma unroll 1
+        for (; j % G; j--) acc = fr_t::load(&c[first + (j - 1) * step]) + acc * Z1;
+    }
+    fr_t x[G + 1], y[G + 1];
+#pragma unroll
+    for (int g = 0; g <= G; g++) x[g] = fr_t::from_table(P.Z[g]);
+#pragma unroll 1
+    for (; j; j -= G) {  // whole groups below: acc <- acc Z^G + sum_g c[j - G + g] Z^g
+#pragma unroll
+        for (int g = 0; g < G; g++) y[g] = fr_t::load(&c[first + (j - G + g) * step]);
+        y[G] = acc;
+        acc = fr_t::sum_of_products<G + 1>(x, y);
+    }
+    return acc;
+}
+// v z^e over the set bits of e < 2^FR_EVALUATE_BITS
+SV_HD fr_t fr_evaluate_scale(fr_t v, const fr_evaluate_point_t& P, uint32_t e) {
+#pragma unroll 1
+    for (int i = 0; e >> i; i++)
+        if ((e >> i) & 1) v = v * fr_t::from_table(P.pw[i]);
+    return v;
+}
+// The table of launch 0 for a grid of gdim workgroups of bdim threads: point q owns the bdim + gdim entries from q (bdim + gdim) on - entry
+// e < bdim is z^e (thread e's factor), entry bdim + x is z^(x bdim) (workgroup x's factor).  Entries are TRUE internal values, bit-packed
+// into 32 bytes by store() and taken back by load() (pure repacking of a canonical value: not a memory-form element).
+SV_HD size_t fr_evaluate_table_size(uint32_t bdim, uint32_t gdim) { return FR_EVALUATE_POW == 2 ? (size_t)FR_EVALUATE_POINTS * (bdim + gdim) : 0; }
+SV_HD fr_t fr_evaluate_table_entry(const fr_evaluate_point_t& P, uint32_t e, uint32_t bdim) {
+    return fr_evaluate_scale(fr_t::one(), P, e < bdim ? e : (e - bdim) * bdim);
+}
+// what thread `tid` of workgroup x (bdim threads, gdim workgroups) contributes for member y of the table, and what thread 0 does to the
+// workgroup's sum: the kernel below and the host replay (snarkvm_hip_selftest_fr_evaluate) both call them
+SV_HD fr_t fr_evaluate_thread(const fr_evaluate_t& t, const fr_mem_t* tab, uint32_t y, uint32_t x, uint32_t tid, uint32_t bdim, uint32_t gdim) {
+    const fr_evaluate_point_t& P = t.pt[t.point[y]];
+    const fr_t v = fr_evaluate_walk(t.p[y], t.len[y], (size_t)x * bdim + tid, (size_t)gdim * bdim, P);
+    if (FR_EVALUATE_POW == 2) return v * fr_t::load(&tab[(size_t)t.point[y] * (bdim + gdim) + tid]);
+    return fr_evaluate_scale(v, P, FR_EVALUATE_POW == 0 ? tid : x * bdim + tid);
+}
+SV_HD fr_t fr_evaluate_block(const fr_evaluate_t& t, const fr_mem_t* tab, uint32_t y, uint32_t x, uint32_t bdim, uint32_t gdim, const fr_t& sum) {
+    if (FR_EVALUATE_POW == 2) return sum * fr_t::load(&tab[(size_t)t.point[y] * (bdim + gdim) + bdim + x]);
+    return FR_EVALUATE_POW == 0 ? fr_evaluate_scale(sum, t.pt[t.point[y]], x * bdim) : sum;
+}
+#if defined(__HIPCC__)
+// launch 0: grid (ceil((bdim + gdim) / blockDim), points of the table); bdim, gdim: the geometry of launch 1
+static __global__ void __launch_bounds__(FR_REDUCE_B) fr_evaluate_powers_kernel(fr_mem_t* __restrict__ tab, uint32_t bdim, uint32_t gdim, fr_evaluate_t t) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < bdim + gdim) fr_evaluate_table_entry(t.pt[blockIdx.y], e, bdim).store(&tab[(size_t)blockIdx.y * (bdim + gdim) + e]);
+}
+// partials[row * gridDim.x + x]: the value of workgroup x over the member, stored raw (the memory image of its share of the result)
+static __global__ void __launch_bounds__(FR_REDUCE_B) fr_evaluate_kernel(fr_mem_t* __restrict__ partials, const fr_mem_t* __restrict__ tab, fr_evaluate_t t) {
+    __shared__ uint32_t sh[9 * (FR_REDUCE_B / 64)];
+    fr_t v = fr_evaluate_thread(t, tab, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x, gridDim.x);
+    v = fr_block_sum(v, sh);
+    if (threadIdx.x == 0)
+        fr_evaluate_block(t, tab, blockIdx.y, blockIdx.x, blockDim.x, gridDim.x, v).store(&partials[(size_t)t.row[blockIdx.y] * gridDim.x + blockIdx.x]);
+}
+#endif
+
 // ---- sparse matrix times vector over a registered matrix -----------------------------------------------------------------
 // y = M x for an R1CS matrix M in CSR form (z_M = M z, snark/varuna/ahp/prover/round_functions/mod.rs:131-188) or for its transpose
 // (M(alpha, .) = M^T l_alpha, third.rs:303-306).  R1CS rows hold a handful of entries, but a transposed matrix has a few rows - the column of

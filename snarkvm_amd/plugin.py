@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "fr_arithmetize_device", "fr_arithmetize", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_evaluate_device", "fr_evaluate", "FR_EVALUATE_MEMBERS", "FR_EVALUATE_POINTS","fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "fr_arithmetize_device", "fr_arithmetize", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -215,6 +215,39 @@ def fr_support_strided_device(d_v, n, count, stride):
     out = np.zeros((int(count), 3), dtype=np.uint64)
     _lib.check(_lib.lib().snarkvm_hip_fr_support_strided(_ptr(out), _dp(d_v), int(n), int(count), int(stride)))
     return out
+
+
+FR_EVALUATE_MEMBERS, FR_EVALUATE_POINTS = 64, 3  # members / distinct points per kernel launch of snarkvm_hip_fr_evaluate (csrc/poly.hip.h)
+
+
+def _fr_evaluate(ptrs, lens, points, on_device):
+    k = len(ptrs)
+    if len(lens) != k:
+        raise ValueError("length mismatch")
+    zs = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4) if k else np.zeros((0, 4), dtype=np.uint64)
+    if zs.shape[0] != k:
+        raise ValueError("length mismatch")
+    out = np.zeros((k, 4), dtype=np.uint64)
+    pp = (ctypes.c_void_p * max(1, k))(*ptrs)
+    pl = (ctypes.c_size_t * max(1, k))(*[int(n) for n in lens])
+    _lib.check(_lib.lib().snarkvm_hip_fr_evaluate(_ptr(out), k, pp, pl, _ptr(zs), on_device))
+    return out
+
+
+def fr_evaluate_device(d_polys, lens, points):
+    """Extension (no reference counterpart): result[k] = sum_{i < lens[k]} d_polys[k][i] * points[k]^i over coefficient vectors that live in device
+    memory (`snarkvm_hip_fr_evaluate`, on_device = 1; DensePolynomial::evaluate, dense.rs:98-114) -> (len(d_polys), 4) Montgomery limbs on the
+    host.  points: (k, 4) Montgomery limbs on the host, one per member; equal points share their powers.  Members may repeat and overlap; none
+    is written; a member of length 0 may be None.  Inside a scope the call is only enqueued and the returned array is filled when the scope
+    ends: keep it alive until then."""
+    return _fr_evaluate([_dp(p) for p in d_polys], lens, points, 1)
+
+
+def fr_evaluate(polys, points):
+    """The same on host arrays (on_device = 0): polys[k] an (n_k, 4) array of coefficients -> (len(polys), 4).  Every distinct buffer is
+    uploaded once; the values are there on return."""
+    ps = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
+    return _fr_evaluate([p.ctypes.data if p.shape[0] else None for p in ps], [p.shape[0] for p in ps], points, 0)
 
 
 def fr_spmv_device(handle, d_y, n_out, d_x, count=1, stride_x=0, stride_y=0):

@@ -26,6 +26,9 @@ from .layout import G1_AFFINE, G1_PROJECTIVE
 
 FR_MODULUS = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001  # r (fr.rs:137-142)
 FR_ONE = np.array([0x7D1C7FFFFFFFFFF3, 0x7257F50F6FFFFFF2, 0x16D81575512C0FEE, 0x0D4BDA322BBB9A9D], dtype=np.uint64)  # Fr R (fr.rs:158-163)
+# the route `SonicKZG10.evaluate_combinations_device` takes when none is named: "linear" was no slower than "fold" at any measured shape
+# (3.6x - 43x faster; profiles/fr_evaluate.md holds the table and the rule that decided it)
+EVALUATE_COMBINATIONS_ROUTE = "linear"
 
 
 def _pts(a):
@@ -339,17 +342,51 @@ class SonicKZG10:
         return SonicKZG10.batch_open(max_degree, ck, lc_polynomials, query_set, lc_randomness, fs_rng)
 
     @staticmethod
-    def evaluate_combinations_device(linear_combinations, polynomials, query_set):
-        """The loop of snark/varuna/varuna.rs:583-590 (`get_lc_eval`, ahp/ahp.rs:469-487) over `ResidentPolynomial`s: the value of every queried
-        linear combination at its point, -> {(label, point_name): (4,) Montgomery limbs}.  One `snarkvm_hip_fr_open_fold` without a quotient
-        per (combination, point) - the combination is never materialised - all enqueued in one scope of its own, the values read when it
-        ends; a `ONE` term adds its coefficient on the host (ahp.rs:480-484).  Refused inside a caller's scope.
-        Measured (profiles/fr_open_fold.md): for a single member the call takes 0.75 - 0.81 of the time of `fr_divide_by_linear` without a
-        quotient; for the 10 members of a gamma point at 2^17 coefficients it LOSES to materialising the combination with `fr_lincomb` and
-        evaluating that (0.69 of its speed): without a quotient buffer the combination is formed inside the sweep, 32 coefficients to a
-        thread.  What it saves there is the intermediate vector, not time."""
+    def evaluate_polynomials_device(polynomials, query_set):
+        """The `evaluations` a proof carries (snark/varuna/varuna.rs:583-592, for the labels that are polynomials: g_1 at beta, g_a, g_b, g_c per
+        circuit at gamma) over `ResidentPolynomial`s: query_set holds (label, (point_name, point)) -> {(label, point_name): (4,) Montgomery
+        limbs}, all from ONE `snarkvm_hip_fr_evaluate` call - every coefficient read once, the powers of a point shared by the polynomials
+        queried at it.  A label that is not among the polynomials raises MissingEval(label).  Refused inside a caller's scope."""
         from . import plugin
 
+        if _lib.lib().snarkvm_hip_scope_stream():
+            raise PCError("evaluate_polynomials_device: the values are needed at once - not inside a scope")
+        by_label = {p.label: p for p in polynomials}
+        keys, members, points = [], [], []
+        for label, (point_name, point) in query_set:
+            if label not in by_label:
+                raise PCError(f"MissingEval({label})")
+            keys.append((label, point_name))
+            members.append(by_label[label])
+            points.append(np.ascontiguousarray(point, dtype=np.uint64).reshape(4))
+        if not keys:
+            return {}
+        values = plugin.fr_evaluate_device([p.ptr if p.n else None for p in members], [p.n for p in members], np.stack(points))
+        return {key: values[i].copy() for i, key in enumerate(keys)}
+
+    @staticmethod
+    def evaluate_combinations_device(linear_combinations, polynomials, query_set, route=None):
+        """The loop of snark/varuna/varuna.rs:583-590 (`get_lc_eval`, ahp/ahp.rs:469-487) over `ResidentPolynomial`s: the value of every queried
+        linear combination at its point, -> {(label, point_name): (4,) Montgomery limbs}; a `ONE` term adds its coefficient on the host
+        (ahp.rs:480-484).  Refused inside a caller's scope.  Two routes to the same bytes:
+          route="fold":   one `snarkvm_hip_fr_open_fold` without a quotient per (combination, point) - the combination is never materialised -
+                          all enqueued in one scope of its own, the values read when it ends.
+          route="linear": evaluation is linear, lc(z) = sum_k a_k p_k(z): the distinct (member, point) pairs of every queried combination go
+                          through ONE `snarkvm_hip_fr_evaluate` call - each read once, coalesced - and the few values are combined on the
+                          host, exactly.
+        route=None takes EVALUATE_COMBINATIONS_ROUTE: "linear", which the measurement chose (profiles/fr_evaluate.md: device time 58 us
+        against 689 us for the 4 combinations over 10 members of a gamma point at 2^17 coefficients, 222 against 811 us at 2^20; the host
+        combination, 0.2 - 0.4 ms of Python integers for 10 - 28 members, is not in these figures and leaves it ahead at every shape).
+        Measured for the fold route (profiles/fr_open_fold.md): for a single member it takes 0.75 - 0.81 of the time of `fr_divide_by_linear`
+        without a quotient; for the 10 members of a gamma point at 2^17 coefficients it LOSES to materialising the combination with
+        `fr_lincomb` and evaluating that (0.69 of its speed): without a quotient buffer the combination is formed inside the sweep, 32
+        coefficients to a thread, and those reads do not coalesce.  That loss belongs to the sweep, not to the task: the linear route needs
+        neither the sweep nor the intermediate vector."""
+        from . import plugin
+
+        route = EVALUATE_COMBINATIONS_ROUTE if route is None else route
+        if route not in ("fold", "linear"):
+            raise ValueError("route must be 'fold' or 'linear'")
         L = _lib.lib()
         if L.snarkvm_hip_scope_stream():
             raise PCError("evaluate_combinations_device: the values are needed at once - not inside a scope")
@@ -370,7 +407,25 @@ class SonicKZG10:
                 coeffs.append(coeff)
                 members.append(by_label[term])
             jobs.append(((label, point_name), point, constant, coeffs, members))
-        anchor = next((p.ptr for _, _, _, _, ms in jobs for p in ms if p.n), 0)
+        if route == "linear":
+            pairs, d_polys, lens, points = {}, [], [], []  # (label, the point's bytes) -> its row in the one call
+            for _, point, _, _, members in jobs:
+                z = np.ascontiguousarray(point, dtype=np.uint64).reshape(4)
+                for p in members:
+                    if p.n and (p.label, z.tobytes()) not in pairs:
+                        pairs[(p.label, z.tobytes())] = len(d_polys)
+                        d_polys.append(p.ptr), lens.append(p.n), points.append(z)
+            vals = plugin.fr_evaluate_device(d_polys, lens, np.stack(points)) if d_polys else None
+            out = {}
+            for key, point, constant, coeffs, members in jobs:
+                zb = np.ascontiguousarray(point, dtype=np.uint64).reshape(4).tobytes()
+                acc = None
+                for a, p in zip(coeffs, members):
+                    if p.n:
+                        acc = _fr_add(acc, _fr_mul(a, vals[pairs[(p.label, zb)]]))
+                out[key] = _fr_add(acc, constant)
+            return out
+        anchor =next((p.ptr for _, _, _, _, ms in jobs for p in ms if p.n), 0)
         values = []
         if anchor:
             _lib.check(L.snarkvm_hip_scope_begin(ctypes.c_void_p(anchor)))
