@@ -1,7 +1,7 @@
 // api_g2.hip - the G2 (Fq2) entry points of the C ABI: the MSM engine, table precomputation and point encoding instantiated
-// over fq2_t.  A separate translation unit only because these instantiations are half of the compile time: build.py compiles
-// the units in parallel.
-#include "msm_batch.hip.h"
+// over fq2_t, behind the front end shared with G1 (msm_registered.hip.h).  A separate translation unit only because these instantiations
+// are half of the compile time: build.py compiles the units in parallel.
+#include "msm_registered.hip.h"
 #include "serde.hip.h"
 
 // this unit launches the scans (the G2 MSMs)
@@ -9,15 +9,29 @@ static void tu_set_kernel_attributes() {
     HIP_TRY(hipFuncSetAttribute((const void*)scan_one_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SCAN_ONE_MAX * 4)));
 }
 
-struct snarkvm_hip_bases_g2 : bases_handle_t<fq2_t> {};
-
 extern "C" {
+
+void snarkvm_hip_free_bases_g2(snarkvm_hip_bases_g2_t* h) {
+    if (!h) return;
+    h->free_all();
+    delete h;
+}
+
+#ifdef SV_NO_G2  // development builds only (python -m snarkvm_amd.build --fast): skips the Fq2 kernel instantiations; every entry point refuses
+static RustError no_g2() { return from_failure(hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__}); }
+RustError snarkvm_hip_msm_g2(void*, const void*, size_t, const void*, size_t) { return no_g2(); }
+RustError snarkvm_hip_register_bases_g2(snarkvm_hip_bases_g2_t**, const void*, size_t, size_t, int, int) { return no_g2(); }
+RustError snarkvm_hip_msm_g2_registered(void*, const snarkvm_hip_bases_g2_t*, size_t, size_t, const void*, int, int) { return no_g2(); }
+RustError snarkvm_hip_msm_g2_registered_batch(void*, const snarkvm_hip_bases_g2_t*, size_t, const size_t*, const size_t*, const void* const*, int, int) { return no_g2(); }
+RustError snarkvm_hip_g2_deserialize(void*, const void*, size_t, int) { return no_g2(); }
+RustError snarkvm_hip_g2_deserialize_compressed(void*, const void*, size_t, int) { return no_g2(); }
+RustError snarkvm_hip_g2_serialize(void*, const void*, size_t, size_t) { return no_g2(); }
+RustError snarkvm_hip_g2_serialize_compressed(void*, const void*, size_t, size_t) { return no_g2(); }
+RustError snarkvm_hip_devtest_g2_tail_repeat(const void*, size_t, int, int, int, int, int, int, int, uint32_t*) { return no_g2(); }
+#else
 
 RustError snarkvm_hip_msm_g2(void* out, const void* points, size_t npoints, const void* scalars, size_t ffi_affine_sz) {
     API_TRY
-#ifdef SV_NO_G2  // development builds only (python -m snarkvm_amd.build --fast): skips the Fq2 kernel instantiations
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
     if (!out) throw hip_failure{hipErrorInvalidValue, "msm_g2: null output", __LINE__};
     g_rt.configure();
     if (npoints == 0) {
@@ -26,7 +40,6 @@ RustError snarkvm_hip_msm_g2(void* out, const void* points, size_t npoints, cons
         if (!points || !scalars) throw hip_failure{hipErrorInvalidValue, "msm_g2: null argument", __LINE__};
         msm_host_chunked<fq2_t>(out, points, npoints, scalars, ffi_affine_sz);
     }
-#endif
     API_CATCH
 }
 
@@ -35,127 +48,39 @@ RustError snarkvm_hip_msm_g2(void* out, const void* points, size_t npoints, cons
 RustError snarkvm_hip_register_bases_g2(snarkvm_hip_bases_g2_t** handle, const void* points, size_t npoints, size_t ffi_affine_sz, int tables,
                                         int window_bits) {
     API_TRY
-#ifdef SV_NO_G2
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
     if (!handle || (npoints && !points)) throw hip_failure{hipErrorInvalidValue, "register_bases_g2: null argument", __LINE__};
     if (ffi_affine_sz < 200 || (ffi_affine_sz & 7)) throw hip_failure{hipErrorInvalidValue, "register_bases_g2: bad stride", __LINE__};
     check_tables(tables, window_bits, "register_bases_g2");
-    const int nd = g_rt.ndev();
-    std::unique_ptr<snarkvm_hip_bases_g2> h(new snarkvm_hip_bases_g2());
-    h->n = npoints;
-    h->tables = tables;
-    h->table_bits = window_bits ? window_bits : 256 / tables;
-    h->d.assign(nd, nullptr);
-    if (npoints) {
-        try {
-            std::vector<int> all;
-            for (int d = 0; d < nd; d++) all.push_back(d);
-            for_each_device(all, [&](int dev) {
-                lane_guard lg(dev);
-                lane_t& c = lg.c();
-                HIP_TRY(hipMalloc((void**)&h->d[dev], (size_t)tables * npoints * sizeof(aff_mem_t<fq2_t>)));
-                c.bases_tmp.ensure(npoints * ffi_affine_sz);
-                HIP_TRY(hipMemcpyAsync(c.bases_tmp.p, points, npoints * ffi_affine_sz, hipMemcpyHostToDevice, c.stream));
-                convert_bases<fq2_t>(c, c.bases_tmp.as<uint8_t>(), ffi_affine_sz, npoints, h->d[dev]);
-                precompute_tables_run<fq2_t>(c, h->d[dev], npoints, tables, h->table_bits);
-                bases_to_lazy_form(c, h->d[dev], (size_t)tables * npoints);  // last: the tables are derived from one another in the exact form
-                HIP_TRY(hipStreamSynchronize(c.stream));
-            });
-        } catch (...) {
-            h->free_all();
-            throw;
-        }
-    }
-    *handle = h.release();
-#endif
+    *handle = bases_build<fq2_t>(npoints, tables, window_bits ? window_bits : 256 / tables,
+                                 [&](lane_t& c, aff_mem_t<fq2_t>* table0) { bases_fill_from_host<fq2_t>(c, points, npoints, ffi_affine_sz, table0); });
     API_CATCH
 }
-void snarkvm_hip_free_bases_g2(snarkvm_hip_bases_g2_t* h) {
-    if (!h) return;
-    h->free_all();
-    delete h;
-}
-#ifndef SV_NO_G2
-// a proof-sized G2 MSM of one caller: concurrent callers over the same handle are fused (msm_batch.hip.h::msm_coalesced)
-static RustError msm_g2_single_coalesced(void* out, const snarkvm_hip_bases_g2_t* h, size_t offset, size_t npoints, const void* scalars, int scalars_on_device,
-                                         int window_bits) {
-    API_TRY
-    if (scalars_on_device && g_rt.device_of(scalars) < 0)
-        throw hip_failure{hipErrorInvalidValue, "device pointer does not belong to a device in use (snarkvm_hip_set_devices)", __LINE__};
-    msm_ticket_t t;
-    t.req.off0 = offset, t.req.n0 = npoints, t.req.scalars = scalars, t.req.out = out;
-    t.on_device = scalars_on_device ? 1 : 0;
-    t.window_bits = window_bits;
-    msm_coalesced<fq2_t>(*h, &t, 1);
-    API_CATCH
-}
-// the same call from a thread inside an SNARKVM_HIP_SCOPE_ASYNC_MSM scope: only enqueued (msm_batch.hip.h::msm_scope_enqueue)
-static RustError msm_g2_scope_enqueue(void* out, const snarkvm_hip_bases_g2_t* h, size_t offset, size_t npoints, const void* scalars, int window_bits, bool* queued) {
-    API_TRY
-    msm_req_t one;
-    one.off0 = offset, one.n0 = npoints, one.scalars = scalars, one.out = out;
-    *queued = msm_scope_enqueue<fq2_t>(*h, &one, 1, 1, 0, window_bits);
-    API_CATCH
-}
-#endif
+// One G2 MSM over a registered range (msm_registered.hip.h::msm_registered_single; an empty one is answered on return, also inside a scope)
 RustError snarkvm_hip_msm_g2_registered(void* out, const snarkvm_hip_bases_g2_t* h, size_t offset, size_t npoints, const void* scalars,
                                         int scalars_on_device, int window_bits) {
-#ifndef SV_NO_G2
-    if (h && out && scalars && offset + npoints <= h->n && (!window_bits || (window_bits >= 2 && window_bits <= MSM_C_MAX)) && g_rt.configured) {
-        if (tl_scope().lane && (tl_scope().flags & SNARKVM_HIP_SCOPE_ASYNC_MSM) && scalars_on_device && npoints) {
-            bool queued = false;
-            const RustError e = msm_g2_scope_enqueue(out, h, offset, npoints, scalars, window_bits, &queued);
-            if (e.code || queued) return e;
-        }
-        if (msm_coalescible(*h, npoints, window_bits)) return msm_g2_single_coalesced(out, h, offset, npoints, scalars, scalars_on_device, window_bits);
-    }
-#endif
-    API_BEGIN_DEV(device_for(scalars, (scalars_on_device && npoints) ? 1 : 0))
-#ifdef SV_NO_G2
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
+    API_TRY
     if (!h || offset + npoints > h->n) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered: range exceeds the registered bases", __LINE__};
-    if (window_bits && (window_bits < 2 || window_bits > MSM_C_MAX)) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered: window_bits must be 0 or 2..23", __LINE__};
+    if (!msm_window_bits_ok(window_bits)) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered: window_bits must be 0 or 2..23", __LINE__};
     if (!out || (npoints && !scalars)) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered: null argument", __LINE__};
-    const uint4* d_sc = (const uint4*)scalars;
-    if (!scalars_on_device && npoints) {
-        c.scalars_tmp.ensure(npoints * 32);
-        c.phase_begin("msm_h2d");
-        HIP_TRY(hipMemcpyAsync(c.scalars_tmp.p, scalars, npoints * 32, hipMemcpyHostToDevice, c.stream));
-        c.phase_end();
-        d_sc = c.scalars_tmp.as<uint4>();
-    }
     msm_req_t one;
-    one.off0 = offset, one.n0 = npoints;
-    msm_job_t<fq2_t> job = msm_handle_job<fq2_t>(*h, c.dev->logical, one);
-    job.scalars = d_sc;
-    job.window_bits = window_bits;
-    msm_run_sync<fq2_t>(c, job, out);
-#endif
-    API_END
+    one.off0 = offset, one.n0 = npoints, one.scalars = scalars, one.out = out;
+    msm_registered_single<fq2_t>(*h, one, scalars_on_device, 0, window_bits, false);
+    API_CATCH
 }
 // A batch of independent G2 MSMs over one registered vector (BASELINE configs[4]: one per proof), fanned out like the G1 batch.
 RustError snarkvm_hip_msm_g2_registered_batch(void* outs, const snarkvm_hip_bases_g2_t* h, size_t count, const size_t* offsets, const size_t* npoints,
                                               const void* const* scalars, int scalars_on_device, int window_bits) {
     API_TRY
-#ifdef SV_NO_G2
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
     if (!h) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered_batch: null handle", __LINE__};
-    if (window_bits && (window_bits < 2 || window_bits > MSM_C_MAX)) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered_batch: window_bits must be 0 or 2..23", __LINE__};
+    if (!msm_window_bits_ok(window_bits)) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered_batch: window_bits must be 0 or 2..23", __LINE__};
     if (count && (!outs || !offsets || !npoints || !scalars)) throw hip_failure{hipErrorInvalidValue, "msm_g2_registered_batch: null argument", __LINE__};
     std::vector<msm_req_t> req = msm_requests<fq2_t>(outs, count, offsets, npoints, nullptr, nullptr, scalars);
     msm_batch_dispatch<fq2_t>(*h, req, scalars_on_device, 0, window_bits);
-#endif
     API_CATCH
 }
 
 static RustError g2_deserialize_impl(void* out_affine, const void* bytes, size_t n, int compressed, int validate) {
     API_BEGIN
-#ifdef SV_NO_G2
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
     if (n) {
         if (!out_affine || !bytes) throw hip_failure{hipErrorInvalidValue, "g2_deserialize: null argument", __LINE__};
         const size_t psz = compressed ? 96 : 192;
@@ -173,14 +98,10 @@ static RustError g2_deserialize_impl(void* out_affine, const void* bytes, size_t
         HIP_TRY(hipStreamSynchronize(c.stream));
         serde_throw_on_status(st, "g2_deserialize");
     }
-#endif
     API_END
 }
 static RustError g2_serialize_impl(void* out_bytes, const void* affine, size_t n, size_t ffi_affine_sz, int compressed) {
     API_BEGIN
-#ifdef SV_NO_G2
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
     if (n) {
         if (!out_bytes || !affine) throw hip_failure{hipErrorInvalidValue, "g2_serialize: null argument", __LINE__};
         if (ffi_affine_sz < 200 || (ffi_affine_sz & 7)) throw hip_failure{hipErrorInvalidValue, "g2_serialize: bad stride", __LINE__};
@@ -194,7 +115,6 @@ static RustError g2_serialize_impl(void* out_bytes, const void* affine, size_t n
         HIP_TRY(hipMemcpyAsync(out_bytes, c.poly[0].p, n * psz, hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream));
     }
-#endif
     API_END
 }
 
@@ -207,74 +127,6 @@ RustError snarkvm_hip_g2_serialize_compressed(void* out_bytes, const void* affin
     return g2_serialize_impl(out_bytes, affine, n, ffi_affine_sz, 1);
 }
 
-// ---- test hook: the lane-pair Fq2 arithmetic of the G2 accumulate kernel (ffl2p.hip.h) against the exact arithmetic, on the host ----
-// The SAME source the kernel runs (fq2p::xyzz_pair_t) instantiated with the two-lane host exchange policy: a chain of `iters` mixed
-// additions of +- points[k] - the same point again (doubling, resolved inside the pair arithmetic), its negative (cancellation),
-// restarts from infinity - with every coordinate component compared with xyzz_t<fq2_t>::add_affine after every step, the raw partial-sum
-// image and its conversion on the way.  0 = identical; > 0: first differing step; < 0: a conversion case.
-int snarkvm_hip_selftest_fq2_pair(const void* points, size_t npoints, uint64_t seed, int iters) {
-#ifdef SV_NO_G2
-    (void)points, (void)npoints, (void)seed, (void)iters;
-    return -1;
-#else
-    if (!points || npoints < 2) return -2;
-    std::vector<aff_t<fq2_t>> pool;
-    for (size_t i = 0; i < npoints; i++) {
-        const uint32_t* src = (const uint32_t*)((const uint8_t*)points + 200 * i);
-        pool.push_back({fq2_t::from_raw_words(src), fq2_t::from_raw_words(src + 24)});
-    }
-    auto next = [&]() {
-        seed += 0x9E3779B97F4A7C15ull;
-        uint64_t z = seed;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    };
-    auto same = [](const fql_t (&l)[2], const fq2_t& e) { return l[0].to_exact() == e.c0 && l[1].to_exact() == e.c1; };
-    xyzz_t<fq2_t> exact = xyzz_t<fq2_t>::inf();
-    fq2p::xyzz_pair_t<fq2p::xp_host> pr;
-    pr.inf = true;
-    int prev = -1;
-    bool prev_neg = false;
-    for (int it = 0; it < iters; it++) {
-        const uint64_t r = next();
-        int k = (int)(r % npoints);
-        bool neg = ((r >> 8) & 1) != 0;
-        const int mode = (int)((r >> 16) % 16);
-        if (mode == 0 && prev >= 0) k = prev, neg = prev_neg;
-        if (mode == 1 && prev >= 0) k = prev, neg = !prev_neg;
-        if (mode == 2) {
-            exact = xyzz_t<fq2_t>::inf();
-            pr.inf = true;
-        }
-        prev = k;
-        prev_neg = neg;
-        const aff_t<fq2_t> p = pool[k];
-        exact.add_affine(p, neg);
-        // the base slot as the kernel reads it: component c of x and y
-        alignas(128) aff_mem_t<fq2_t> slot;
-        const fq_t c406 = fq_t::from_table(FqLConv::C406);
-        g2_lazy_slot_t::store(&slot, {p.x.c0 * c406, p.x.c1 * c406}, {p.y.c0 * c406, p.y.c1 * c406}, false);
-        fql_t px[2], py[2];
-        for (int c = 0; c < 2; c++) ((const g2_lazy_slot_t*)&slot)->component(c, px[c], py[c]);
-        pr.madd(px, py, neg);
-        if (pr.inf != exact.is_inf()) return it + 1;
-        if (!pr.inf && !(same(pr.x, exact.x) && same(pr.y, exact.y) && same(pr.zz, exact.zz) && same(pr.zzz, exact.zzz))) return it + 1;
-        if (!pr.inf && (it & 7) == 0) {  // the raw partial-sum image through the conversion the device kernel applies per component
-            const fql_t* cs[4] = {pr.x, pr.y, pr.zz, pr.zzz};
-            const fq2_t* es[4] = {&exact.x, &exact.y, &exact.zz, &exact.zzz};
-            for (int c4 = 0; c4 < 4; c4++)
-                for (int c = 0; c < 2; c++) {
-                    fql_t back;
-                    for (int j = 0; j < 13; j++) back.v[j] = cs[c4][c].v[j];
-                    if (!(back.to_exact() == (c ? es[c4]->c1 : es[c4]->c0))) return -(it + 1);
-                }
-        }
-    }
-    return 0;
-#endif
-}
-
 // The G2 fold and bit-plane kernels launched `iters` times over ONE fixed set of per-bucket partial-sum lists (2^(m + hb) buckets of one window; 0, 1 or 2
 // entries per bucket - the sparse shape of a small MSM over window tables - built from +- points[k]): every launch must leave the same group elements.
 // A difference is a race or a lost register, whatever the points are.  threads: per fold workgroup (64, 128, 256);
@@ -284,10 +136,6 @@ int snarkvm_hip_selftest_fq2_pair(const void* points, size_t npoints, uint64_t s
 RustError snarkvm_hip_devtest_g2_tail_repeat(const void* points, size_t npoints, int m, int hb, int threads, int plane_threads, int hex, int quads, int iters,
                                              uint32_t* report) {
     API_BEGIN
-#ifdef SV_NO_G2
-    (void)points, (void)npoints, (void)m, (void)hb, (void)threads, (void)plane_threads, (void)hex, (void)quads, (void)iters, (void)report;
-    throw hip_failure{hipErrorNotSupported, "this development build was compiled without G2 (SV_NO_G2)", __LINE__};
-#else
     if (!points || npoints < 2 || !report || m < 1 || hb < 1 || hb > m || m + hb > 16 || iters < 2 || (threads != 64 && threads != 128 && threads != 256) ||
         (plane_threads != 64 && plane_threads != 128 && plane_threads != 256))
         throw hip_failure{hipErrorInvalidValue, "devtest_g2_tail_repeat: bad arguments", __LINE__};
@@ -366,63 +214,9 @@ RustError snarkvm_hip_devtest_g2_tail_repeat(const void* points, size_t npoints,
     report[8] = report[9] = 0;  // outputs of the first launch the fast kernels flagged (fold slots, planes): the fix kernels' share of the work
     for (size_t sl = 0; sl + 1 < nslots; sl++) report[8] += flag_copy[sl] ? 1 : 0;  // (the slots no workgroup writes were cleared above)
     for (size_t pl = 0; pl < nplanes; pl++) report[9] += flag_copy[nslots + pl] ? 1 : 0;
-#endif
     API_END
 }
 
-// The sixteen-lane cooperative Fq2 addition of the G2 tail trees (csrc/hex2.hip.h) on sixteen SIMULATED lanes - the same source as the kernel's, every lane
-// with its own copy of the state, the pair exchange and the gathers indexing the other lanes' copies - against xyzz_t<fq2_t>::add: `iters` additions of partial
-// sums built from +- points[k] (general ZZ / ZZZ), with the cases a tree meets: an operand at infinity (either, both), P + P (every lane must ask for the
-// plain law), P + (-P).  0 = every lane of every addition ends with exactly the exact sum; > 0: first differing iteration; < 0: bad arguments.
-int snarkvm_hip_selftest_g2_hex(const void* points, size_t npoints, uint64_t seed, int iters) {
-#ifdef SV_NO_G2
-    (void)points, (void)npoints, (void)seed, (void)iters;
-    return -1;
-#else
-    if (!points || npoints < 2) return -2;
-    std::vector<aff_t<fq2_t>> pool;
-    for (size_t i = 0; i < npoints; i++) {
-        const uint32_t* src = (const uint32_t*)((const uint8_t*)points + 200 * i);
-        pool.push_back({fq2_t::from_raw_words(src), fq2_t::from_raw_words(src + 24)});
-    }
-    auto next = [&]() {
-        seed += 0x9E3779B97F4A7C15ull;
-        uint64_t z = seed;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    };
-    auto partial = [&](int terms) {  // a partial sum with general ZZ, ZZZ
-        xyzz_t<fq2_t> a = xyzz_t<fq2_t>::inf();
-        for (int t = 0; t < terms; t++) {
-            const uint64_t r = next();
-            a.add_affine(pool[r % npoints], ((r >> 40) & 1) != 0);
-        }
-        return a;
-    };
-    for (int it = 0; it < iters; it++) {
-        const int mode = (int)(next() % 12);
-        xyzz_t<fq2_t> a = partial(1 + (int)(next() % 3)), b = partial(1 + (int)(next() % 3));
-        if (mode == 0) b = a;                                  // doubling: the equal-x fallback on every lane
-        if (mode == 1) b = a, b.y = b.y.neg();                 // cancellation: equal x as well
-        if (mode == 2) a = xyzz_t<fq2_t>::inf();
-        if (mode == 3) b = xyzz_t<fq2_t>::inf();
-        if (mode == 4) a = xyzz_t<fq2_t>::inf(), b = xyzz_t<fq2_t>::inf();
-        xyzz_t<fq2_t> want = a;
-        want.add(b);
-        if (hex_add_host_check(a, b, want)) return it + 1;
-        // the flagged plain addition of the tail kernels (xyzz_t::add_flag): equal x coordinates of two finite operands raise the flag and leave the accumulator
-        // alone - P + P and P - P alike -, everything else is the exact sum and leaves the flag down
-        xyzz_t<fq2_t> f = a;
-        bool flagged = false;
-        f.add_flag(b, flagged);
-        const bool same_x = !a.is_inf() && !b.is_inf() && a.x * b.zz == b.x * a.zz;
-        if (flagged != same_x) return 100000 + it + 1;
-        const xyzz_t<fq2_t>& expect = flagged ? a : want;
-        if (!(f.x == expect.x && f.y == expect.y && f.zz == expect.zz && f.zzz == expect.zzz)) return 200000 + it + 1;
-    }
-    return 0;
-#endif
-}
+#endif  // SV_NO_G2
 
 }  // extern "C"

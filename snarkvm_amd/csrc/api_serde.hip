@@ -1,13 +1,10 @@
 // api_serde.hip - canonical (de)serialisation of G1 points on the device (serde.hip.h): the reference's point encoding
 // (curves/src/templates/macros.rs:66-140, utilities/src/serialize/flags.rs:72-99) and `.usrs` bodies straight into registered
 // bases.  A separate translation unit so that build.py compiles the square-root / subgroup-check kernels beside the MSM units.
-#include "msm_batch.hip.h"  // register_bases_serialized fills a bases handle: bases_handle_t, check_tables, bases_to_lazy_form
+#include "msm_registered.hip.h"  // register_bases_serialized builds a bases handle: bases_build, check_tables
 #include "serde.hip.h"
 
 static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
-
-snarkvm_hip_bases* sv_new_bases_handle(size_t npoints, int tables, int table_bits);  // api.hip
-void sv_precompute_tables(lane_t& c, snarkvm_hip_bases* h, g1_aff_mem_t* d);        // api.hip
 
 // bytes (host) -> native base slots and / or Rust-layout records (both device); returns the SERDE_* status bits
 static uint32_t g1_deserialize_run(lane_t& c, const void* bytes, size_t n, int compressed, int validate, g1_aff_mem_t* d_native, uint8_t* d_rust) {
@@ -32,26 +29,9 @@ RustError snarkvm_hip_register_bases_serialized(snarkvm_hip_bases_t** handle, co
     API_TRY
     if (!handle || (npoints && !bytes)) throw hip_failure{hipErrorInvalidValue, "register_bases_serialized: null argument", __LINE__};
     check_tables(tables, 0, "register_bases_serialized");
-    std::unique_ptr<snarkvm_hip_bases> h(sv_new_bases_handle(npoints, tables, 256 / tables));
-    if (npoints) {
-        try {
-            std::vector<int> all;
-            for (int d = 0; d < g_rt.ndev(); d++) all.push_back(d);
-            for_each_device(all, [&](int dev) {  // every device decodes its own replica from the host bytes
-                lane_guard lg(dev);
-                lane_t& c = lg.c();
-                HIP_TRY(hipMalloc((void**)&h->d[dev], (size_t)tables * npoints * sizeof(g1_aff_mem_t)));
-                serde_throw_on_status(g1_deserialize_run(c, bytes, npoints, compressed, validate, h->d[dev], nullptr), "register_bases_serialized");
-                sv_precompute_tables(c, h.get(), h->d[dev]);
-                bases_to_lazy_form(c, h->d[dev], (size_t)tables * npoints);
-                HIP_TRY(hipStreamSynchronize(c.stream));
-            });
-        } catch (...) {
-            h->free_all();
-            throw;
-        }
-    }
-    *handle = h.release();
+    *handle = bases_build<fq_t>(npoints, tables, 256 / tables, [&](lane_t& c, g1_aff_mem_t* table0) {  // every device decodes its own replica from the host bytes
+        serde_throw_on_status(g1_deserialize_run(c, bytes, npoints, compressed, validate, table0, nullptr), "register_bases_serialized");
+    });
     API_CATCH
 }
 RustError snarkvm_hip_g1_deserialize(void* out_affine, const void* bytes, size_t n, int compressed, int validate) {

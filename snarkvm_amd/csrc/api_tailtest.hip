@@ -6,6 +6,7 @@
 // A translation unit of its own (as api_msmtest.hip): the units that own the MSM entry points and the tail_*.hip units compile exactly as before; the fold and
 // bit-plane kernels are referenced through their external handles (msm.hip.h SV_TAIL_KERNELS), the small reduce / merge kernels are instantiated here.
 #include "msm_run.hip.h"
+#include "testrng.hip.h"
 
 static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
 
@@ -36,13 +37,8 @@ E tt_scale(uint64_t seed);  // a non-zero field element derived from the seed
 template <>
 fq_t tt_scale<fq_t>(uint64_t seed) {
     fq_t l = fq_t::zero();
-    for (int i = 0; i < 12; i++) {
-        seed += 0x9E3779B97F4A7C15ull;
-        uint64_t z = seed;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        l.v[i] = (uint32_t)((z ^ (z >> 31)) & LIMB_MASK);
-    }
+    splitmix64_t next{seed};
+    for (int i = 0; i < 12; i++) l.v[i] = (uint32_t)(next() & LIMB_MASK);
     l.v[0] |= 1;
     return l;
 }

@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _lib, plugin
-from .layout import G1_AFFINE, G1_PROJECTIVE
+from .layout import G1_AFFINE, G1_PROJECTIVE, G2_AFFINE, G2_PROJECTIVE
 
 
 class VariableBase:
@@ -20,8 +20,58 @@ class VariableBase:
         return plugin.msm(bases, scalars)
 
 
-class RegisteredBases:
+class _Registered:
+    """What the two registered classes share: the handle, the marshalling of `msm` / `msm_batch`, and its release.  A subclass names its symbols and the
+    dtype of a result; the public `msm` signatures stay with the subclasses (their positional orders differ)."""
+
+    _PROJECTIVE = None   # dtype of one result
+    _MSM = _BATCH = _FREE = None   # symbol names
+    _BATCH_HAS_MONTGOMERY = False  # the batch symbol takes a scalars_montgomery flag (G1)
+
+    def _msm(self, scalars, offset, device_ptr, npoints, window_bits):
+        out = np.zeros(1, dtype=self._PROJECTIVE)
+        fn = getattr(_lib.lib(), self._MSM)
+        if device_ptr is not None:
+            err = fn(out.ctypes.data, self._h, offset, int(npoints), device_ptr, 1, window_bits)
+        else:
+            scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+            err = fn(out.ctypes.data, self._h, offset, scalars.shape[0], scalars.ctypes.data, 0, window_bits)
+        _lib.check(err)
+        return out
+
+    def _msm_batch(self, scalars_list, offsets, device_ptrs, npoints, window_bits, montgomery=False):
+        if device_ptrs is not None:
+            count, ns, ptrs, on_dev, keep = len(device_ptrs), [int(v) for v in npoints], [int(p) for p in device_ptrs], 1, None
+        else:
+            keep = [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4) for s in scalars_list]  # alive until the call returns
+            count, ns, ptrs, on_dev = len(keep), [k.shape[0] for k in keep], [k.ctypes.data for k in keep], 0
+        offs = [0] * count if offsets is None else [int(o) for o in offsets]
+        out = np.zeros(count, dtype=self._PROJECTIVE)
+        c_offs = (ctypes.c_size_t * max(1, count))(*offs)
+        c_ns = (ctypes.c_size_t * max(1, count))(*ns)
+        c_ptrs = (ctypes.c_void_p * max(1, count))(*ptrs)
+        flags = (on_dev, 1 if montgomery else 0) if self._BATCH_HAS_MONTGOMERY else (on_dev,)
+        _lib.check(getattr(_lib.lib(), self._BATCH)(out.ctypes.data, self._h, count, c_offs, c_ns, c_ptrs, *flags, window_bits))
+        return out
+
+    def close(self):
+        if self._h:
+            getattr(_lib.lib(), self._FREE)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RegisteredBases(_Registered):
     """Device-resident base vector (snarkvm_hip_register_bases)."""
+
+    _PROJECTIVE = G1_PROJECTIVE
+    _MSM, _BATCH, _FREE = "snarkvm_hip_msm_registered", "snarkvm_hip_msm_registered_batch", "snarkvm_hip_free_bases"
+    _BATCH_HAS_MONTGOMERY = True
 
     def __init__(self, bases=None, device_ptr=None, npoints=None, tables=1, window_bits=0):
         """tables > 1 precomputes 2^(256/tables * j) * P_i (j < tables) once, shrinking the serial tail of every MSM.
@@ -59,59 +109,17 @@ class RegisteredBases:
 
     def msm(self, scalars=None, offset=0, device_ptr=None, npoints=None, window_bits=0):
         """sum_i scalars[i] * bases[offset + i]; scalars either a host (n,4) u64 array or a device pointer."""
-        L = _lib.lib()
-        out = np.zeros(1, dtype=G1_PROJECTIVE)
-        if device_ptr is not None:
-            n = int(npoints)
-            err = L.snarkvm_hip_msm_registered(out.ctypes.data, self._h, offset, n, device_ptr, 1, window_bits)
-        else:
-            scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
-            n = scalars.shape[0]
-            err = L.snarkvm_hip_msm_registered(out.ctypes.data, self._h, offset, n, scalars.ctypes.data, 0, window_bits)
-        _lib.check(err)
-        return out
+        return self._msm(scalars, offset, device_ptr, npoints, window_bits)
 
     def msm_batch(self, scalars_list=None, offsets=None, device_ptrs=None, npoints=None, window_bits=0, montgomery=False):
         """Independent MSMs over this base vector, pipelined on several HIP streams.  Either `scalars_list` (host
         (n_k, 4) arrays) or `device_ptrs` + `npoints` (device-resident scalar vectors).  Returns a G1_PROJECTIVE array."""
-        L = _lib.lib()
-        if device_ptrs is not None:
-            count = len(device_ptrs)
-            ns = [int(v) for v in npoints]
-            ptrs = [int(p) for p in device_ptrs]
-            on_dev = 1
-            keep = None
-        else:
-            keep = [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4) for s in scalars_list]
-            count = len(keep)
-            ns = [k.shape[0] for k in keep]
-            ptrs = [k.ctypes.data for k in keep]
-            on_dev = 0
-        offs = [0] * count if offsets is None else [int(o) for o in offsets]
-        out = np.zeros(count, dtype=G1_PROJECTIVE)
-        c_offs = (ctypes.c_size_t * max(1, count))(*offs)
-        c_ns = (ctypes.c_size_t * max(1, count))(*ns)
-        c_ptrs = (ctypes.c_void_p * max(1, count))(*ptrs)
-        _lib.check(L.snarkvm_hip_msm_registered_batch(out.ctypes.data, self._h, count, c_offs, c_ns, c_ptrs, on_dev, 1 if montgomery else 0, window_bits))
-        return out
-
-    def close(self):
-        if self._h:
-            _lib.lib().snarkvm_hip_free_bases(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._msm_batch(scalars_list, offsets, device_ptrs, npoints, window_bits, montgomery)
 
 
 def msm_g2(bases, scalars):
     """G2 variable-base MSM on the device (extension: the reference sends G2 to its CPU `standard::msm`,
     variable_base/mod.rs:45-47).  bases: G2_AFFINE array (200 B stride); returns a G2_PROJECTIVE record."""
-    from .layout import G2_AFFINE, G2_PROJECTIVE
-
     bases = np.ascontiguousarray(bases, dtype=G2_AFFINE).reshape(-1)
     scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
     n = scalars.shape[0]
@@ -123,12 +131,13 @@ def msm_g2(bases, scalars):
     return out
 
 
-class RegisteredBasesG2:
+class RegisteredBasesG2(_Registered):
     """Device-resident G2 base vector with precomputed tables (snarkvm_hip_register_bases_g2)."""
 
-    def __init__(self, bases, tables=16, window_bits=0):
-        from .layout import G2_AFFINE
+    _PROJECTIVE = G2_PROJECTIVE
+    _MSM, _BATCH, _FREE = "snarkvm_hip_msm_g2_registered", "snarkvm_hip_msm_g2_registered_batch", "snarkvm_hip_free_bases_g2"
 
+    def __init__(self, bases, tables=16, window_bits=0):
         bases = np.ascontiguousarray(bases, dtype=G2_AFFINE).reshape(-1)
         self.n = bases.shape[0]
         self._h = ctypes.c_void_p()
@@ -136,43 +145,11 @@ class RegisteredBasesG2:
 
     def msm(self, scalars=None, offset=0, window_bits=0, device_ptr=None, npoints=None):
         """sum_i scalars[i] * bases[offset + i]; scalars either a host (n,4) u64 array or a device pointer + npoints."""
-        from .layout import G2_PROJECTIVE
-
-        out = np.zeros(1, dtype=G2_PROJECTIVE)
-        if device_ptr is not None:
-            _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered(out.ctypes.data, self._h, offset, int(npoints), device_ptr, 1, window_bits))
-            return out
-        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
-        _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered(out.ctypes.data, self._h, offset, scalars.shape[0], scalars.ctypes.data, 0, window_bits))
-        return out
+        return self._msm(scalars, offset, device_ptr, npoints, window_bits)
 
     def msm_batch(self, scalars_list=None, offsets=None, device_ptrs=None, npoints=None, window_bits=0):
         """Independent G2 MSMs over this base vector fanned out over devices and lanes (snarkvm_hip_msm_g2_registered_batch)."""
-        from .layout import G2_PROJECTIVE
-
-        if device_ptrs is not None:
-            count, ns, ptrs, on_dev, keep = len(device_ptrs), [int(v) for v in npoints], [int(p) for p in device_ptrs], 1, None
-        else:
-            keep = [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4) for s in scalars_list]
-            count, ns, ptrs, on_dev = len(keep), [k.shape[0] for k in keep], [k.ctypes.data for k in keep], 0
-        offs = [0] * count if offsets is None else [int(o) for o in offsets]
-        out = np.zeros(count, dtype=G2_PROJECTIVE)
-        c_offs = (ctypes.c_size_t * max(1, count))(*offs)
-        c_ns = (ctypes.c_size_t * max(1, count))(*ns)
-        c_ptrs = (ctypes.c_void_p * max(1, count))(*ptrs)
-        _lib.check(_lib.lib().snarkvm_hip_msm_g2_registered_batch(out.ctypes.data, self._h, count, c_offs, c_ns, c_ptrs, on_dev, window_bits))
-        return out
-
-    def close(self):
-        if self._h:
-            _lib.lib().snarkvm_hip_free_bases_g2(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._msm_batch(scalars_list, offsets, device_ptrs, npoints, window_bits)
 
 
 def set_devices(ids):
