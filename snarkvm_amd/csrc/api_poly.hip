@@ -27,6 +27,111 @@ static T fr_block_tree_host(std::vector<T> vals, const T& identity, Combine comb
     return u[0];
 }
 
+// The two routes of a suffix Horner sweep over n coefficients (fr_horner_sweep).
+// route 1: the three-launch scan (C coefficients per thread, `blocks` workgroups of HORNER2_B); route 0: the chunk recursion (C = POLY_CHUNK,
+// `blocks` workgroups of 256 at its level 0).
+struct fr_horner_geometry_t {
+    int route;
+    uint32_t C;
+    size_t blocks;
+};
+static fr_horner_geometry_t fr_horner_geometry(size_t n, bool want_quotient) {
+    if (want_quotient && n >= 2048 && n <= ((size_t)1 << 20) && tuning().horner2) {
+        // quotient wanted, a proof-sized polynomial: the three-launch form with a scan inside every workgroup (poly.hip.h); C coefficients per thread keep
+        // <= 256 workgroups.  (Beyond 2^20 coefficients a thread would fold 32+ of them serially on a quarter of the chip's lanes - round 3 measured that
+        // shape at 2^24: 1.69 vs 1.04 ms - and the chunk recursion, 2^19 threads at its first level, is the better form.)
+        uint32_t C = 8;
+        while (((n + C - 1) / C + HORNER2_B - 1) / HORNER2_B > 256) C *= 2;
+        return {1, C, ((n + C - 1) / C + HORNER2_B - 1) / HORNER2_B};
+    }
+    const size_t T = (n + POLY_CHUNK - 1) / POLY_CHUNK;
+    return {0, (uint32_t)POLY_CHUNK, (T + 255) / 256};
+}
+// the sizes of the levels of the chunk recursion: n, then the chunk values of the level below until one is left (always at least two levels:
+// the chunk values of level 0 exist even for a single coefficient)
+static std::vector<size_t> fr_horner_levels(size_t n, size_t chunk) {
+    std::vector<size_t> sizes{n};
+    do sizes.push_back((sizes.back() + chunk - 1) / chunk);
+    while (sizes.back() > 1);
+    return sizes;
+}
+
+// One suffix Horner sweep, h_i = sum_{k >= i} a_k m^(k - i), over `count` vectors of n coefficients (blockIdx.y) on the lane's stream, for the plain
+// division and the opening fold alike: the workspace in the lane's poly[4], the level table and the launches - the constructor lays out and
+// enqueues the multipliers or tables, up() one sweep up, down() the sweep down behind it.  Level 0 is walked through the caller's span policy
+// (poly.hip.h), the levels above it - chunk values - through the plain policy in place.
+//   route 1: tab | hs[count][blocks 256] | bv[count][blocks] | kept[keep]
+//   route 0: mult[top + 1] | cv[count][levels 1 .. top - 1] | kept[keep]
+// kept: the caller's `keep` elements.  Route 0 puts the single value of the top level - h_0 - of vector y of the sweep up(walk, slot) at
+// kept[slot count + y]; the rest is the caller's own.
+struct fr_horner_sweep {
+    lane_t& c;
+    const fr_horner_geometry_t g;
+    const size_t n, count;
+    const fr_mem_t m;
+    std::vector<size_t> sizes, off;  // route 0: level k has sizes[k] values, those of 1 <= k < top at cv + off[k]
+    int top = 0;
+    size_t total = 0;
+    fr_mem_t *head = nullptr, *hs = nullptr, *bv = nullptr, *cv = nullptr, *kept = nullptr;
+
+    fr_horner_sweep(lane_t& c, const fr_horner_geometry_t& g, size_t n, const fr_mem_t& m, size_t count, size_t keep) : c(c), g(g), n(n), count(count), m(m) {
+        if (g.route == 1) {
+            const size_t hs_n = count * g.blocks * HORNER2_B, bv_n = count * g.blocks;
+            c.poly[4].ensure(sizeof(fr_mem_t) * (HORNER2_TAB + hs_n + bv_n + keep));
+            head = c.poly[4].as<fr_mem_t>(), hs = head + HORNER2_TAB, bv = hs + hs_n, kept = bv + bv_n;
+            hipLaunchKernelGGL(fr_horner2_tables_kernel, dim3(1), dim3(HORNER2_B), 0, c.stream, m, head, g.C);
+            return;
+        }
+        sizes = fr_horner_levels(n, POLY_CHUNK);
+        top = (int)sizes.size() - 1;
+        off.assign(sizes.size(), 0);
+        for (int k = 1; k < top; k++) off[k] = total, total += sizes[k];
+        c.poly[4].ensure(sizeof(fr_mem_t) * ((size_t)top + 1 + count * total + keep));
+        head = c.poly[4].as<fr_mem_t>(), cv = head + top + 1, kept = cv + count * total;
+        hipLaunchKernelGGL(fr_horner_multipliers_kernel, dim3(1), dim3(1), 0, c.stream, m, head, top + 1);
+    }
+    // level k >= 1 of vector 0 and the distance to the next vector's; the plain policy over it, in place
+    fr_mem_t* level(int k, size_t slot) const { return k == top ? kept + slot * count : cv + off[k]; }
+    size_t stride(int k) const { return k == top ? 1 : total; }
+    fr_span_plain_t in_place(int k, size_t slot) const { return {level(k, slot), level(k, slot), stride(k), stride(k), 0}; }
+    dim3 grid(int k) const { return dim3((unsigned)((sizes[k + 1] + 255) / 256), (unsigned)count); }
+
+    template <class S>
+    void up_level(int k, const S& walk, size_t slot) {
+        hipLaunchKernelGGL((fr_horner_up_kernel<S>), grid(k), dim3(256), 0, c.stream, walk, sizes[k], (const fr_mem_t*)(head + k), level(k + 1, slot), sizes[k + 1], stride(k + 1));
+    }
+    template <class S>
+    void down_level(int k, const S& walk, fr_mem_t* first) {
+        hipLaunchKernelGGL((fr_horner_down_kernel<S>), grid(k), dim3(256), 0, c.stream, walk, sizes[k], (const fr_mem_t*)(head + k), (const fr_mem_t*)level(k + 1, 0),
+                           sizes[k + 1], stride(k + 1), first);
+    }
+    template <class S>
+    void up(const S& walk, size_t slot = 0) {
+        if (g.route == 1) {
+            hipLaunchKernelGGL((fr_horner2_up_kernel<S>), dim3((unsigned)g.blocks, (unsigned)count), dim3(HORNER2_B), 0, c.stream, walk, n, m, (const fr_mem_t*)head, hs, bv,
+                               g.C, g.blocks * HORNER2_B, g.blocks);
+            return;
+        }
+        up_level(0, walk, slot);
+        for (int k = 1; k < top; k++) up_level(k, in_place(k, slot), slot);
+    }
+    // behind up(walk, 0): every level's chunk values become its suffix sums in place (the one value of the top level is its own), then level 0
+    // through the policy; first[y] = h_0 of vector y
+    template <class S>
+    void down(const S& walk, fr_mem_t* first) {
+        if (g.route == 1) {
+            hipLaunchKernelGGL((fr_horner2_down_kernel<S>), dim3((unsigned)g.blocks, (unsigned)count), dim3(HORNER2_B), 0, c.stream, walk, n, m, (const fr_mem_t*)head,
+                               (const fr_mem_t*)hs, (const fr_mem_t*)bv, g.C, g.blocks * HORNER2_B, g.blocks, first);
+            return;
+        }
+        down_above();
+        down_level(0, walk, first);
+    }
+    void down_above() {  // route 0, the levels above level 0 alone
+        for (int k = top - 1; k >= 1; k--) down_level(k, in_place(k, 0), nullptr);
+    }
+};
+
 extern "C" {
 
 // ---- prover-round polynomial kernels (poly.hip.h) ---------------------------------------------------
@@ -61,95 +166,29 @@ RustError snarkvm_hip_fr_vec_op_strided(int op, void* out, const void* a, const 
     return fr_vec_op_impl(op, out, a, b, c3, scalar, n, 1, count, stride);
 }
 
-// The two routes of a suffix Horner sweep over n coefficients, for the plain division (fr_suffix_horner) and the opening fold (fr_open_run) alike.
-// route 1: the three-launch scan (C coefficients per thread, `blocks` workgroups of HORNER2_B); route 0: the chunk recursion (C = POLY_CHUNK,
-// `blocks` workgroups of 256 at its level 0).
-struct fr_horner_geometry_t {
-    int route;
-    uint32_t C;
-    size_t blocks;
-};
-static fr_horner_geometry_t fr_horner_geometry(size_t n, bool want_quotient) {
-    if (want_quotient && n >= 2048 && n <= ((size_t)1 << 20) && tuning().horner2) {
-        // quotient wanted, a proof-sized polynomial: the three-launch form with a scan inside every workgroup (poly.hip.h); C coefficients per thread keep
-        // <= 256 workgroups.  (Beyond 2^20 coefficients a thread would fold 32+ of them serially on a quarter of the chip's lanes - round 3 measured that
-        // shape at 2^24: 1.69 vs 1.04 ms - and the chunk recursion, 2^19 threads at its first level, is the better form.)
-        uint32_t C = 8;
-        while (((n + C - 1) / C + HORNER2_B - 1) / HORNER2_B > 256) C *= 2;
-        return {1, C, ((n + C - 1) / C + HORNER2_B - 1) / HORNER2_B};
-    }
-    const size_t T = (n + POLY_CHUNK - 1) / POLY_CHUNK;
-    return {0, (uint32_t)POLY_CHUNK, (T + 255) / 256};
-}
-// the sizes of the levels of the chunk recursion: n, then the chunk values of the level below until one is left (always at least two levels:
-// the chunk values of level 0 exist even for a single coefficient)
-static std::vector<size_t> fr_horner_levels(size_t n, size_t chunk) {
-    std::vector<size_t> sizes{n};
-    do sizes.push_back((sizes.back() + chunk - 1) / chunk);
-    while (sizes.back() > 1);
-    return sizes;
-}
-
-// out[i - shift] = h_i = sum_{k >= i} in[k] m^(k - i) (and *first = h_0 when shift == 1); `out` may be null (only h_0 wanted).
-// Scratch for the chunk values of every level lives in the lane's poly[4].
-static void fr_suffix_horner(lane_t& c, const fr_mem_t* d_in, size_t n, const fr_mem_t& m, fr_mem_t* d_out, int shift, fr_mem_t* d_first, size_t count = 1,
-                             size_t in_stride = 0, size_t out_stride = 0) {
-    // `count` vectors in one launch sequence (blockIdx.y): inputs / outputs `in_stride` / `out_stride` elements apart, the chunk values
-    // of vector y in its own slice of the scratch area, d_first[y] = h_0 of vector y
-    hipStream_t st = c.stream;
-    const fr_horner_geometry_t g = fr_horner_geometry(n, d_out != nullptr);
-    if (g.route == 1) {
-        const uint32_t C = g.C;
-        const size_t nblocks = g.blocks;
-        const size_t hs_stride = nblocks * HORNER2_B, bv_stride = nblocks;
-        c.poly[4].ensure(sizeof(fr_mem_t) * (HORNER2_TAB + count * (hs_stride + bv_stride)));
-        fr_mem_t* tab = c.poly[4].as<fr_mem_t>();
-        fr_mem_t* hs = tab + HORNER2_TAB;
-        fr_mem_t* bv = hs + count * hs_stride;
-        hipLaunchKernelGGL(fr_horner2_tables_kernel, dim3(1), dim3(HORNER2_B), 0, st, m, tab, C);
-        hipLaunchKernelGGL(fr_horner2_up_kernel, dim3((unsigned)nblocks, (unsigned)count), dim3(HORNER2_B), 0, st, d_in, n, m, (const fr_mem_t*)tab, hs, bv, C, in_stride,
-                           hs_stride, bv_stride);
-        hipLaunchKernelGGL(fr_horner2_down_kernel, dim3((unsigned)nblocks, (unsigned)count), dim3(HORNER2_B), 0, st, d_in, n, m, (const fr_mem_t*)tab, (const fr_mem_t*)hs,
-                           (const fr_mem_t*)bv, C, d_out, shift, d_first, in_stride, hs_stride, bv_stride, out_stride);
-        HIP_TRY(hipGetLastError());
-        return;
-    }
-    // a lone coefficient is its own h_0: one level and no chunk values, where the fused sweeps of fr_open_run always have two
-    const std::vector<size_t> n_at = n > 1 ? fr_horner_levels(n, POLY_CHUNK) : std::vector<size_t>{n};
-    const int top = (int)n_at.size() - 1, levels = top + 1;
-    size_t total = 0;
-    for (int k = 1; k <= top; k++) total += n_at[k];
-    c.poly[4].ensure(sizeof(fr_mem_t) * (total * count + levels + 2));
-    fr_mem_t* mult = c.poly[4].as<fr_mem_t>();
-    fr_mem_t* cvbase = mult + levels + 1;
-    const unsigned ny = (unsigned)count;
-    hipLaunchKernelGGL(fr_horner_multipliers_kernel, dim3(1), dim3(1), 0, st, m, mult, levels);
-    // up-sweep: level k holds the chunk values of level k - 1 (level 0 = the input)
-    std::vector<const fr_mem_t*> in_at{d_in};
-    fr_mem_t* next = cvbase;
-    for (int k = 0; k < top; k++) {
-        const size_t T = n_at[k + 1];
-        hipLaunchKernelGGL(fr_horner_up_kernel, dim3((unsigned)((T + 255) / 256), ny), dim3(256), 0, st, in_at.back(), n_at[k], mult + k, next, T, k ? total : in_stride, total);
-        in_at.push_back(next);
-        next += T;
-    }
-    // the single value of the top level is h_0 of every level below; down-sweep turns each level's chunk values into
-    // its suffix sums in place, the input level writes to `out`
-    for (int k = top; k >= 0; k--) {
-        const size_t cur = n_at[k];
-        const size_t T = (cur + POLY_CHUNK - 1) / POLY_CHUNK;
-        const fr_mem_t* carry = (k < top) ? in_at[k + 1] : nullptr;
-        if (k > 0) {
-            if (k == top) continue;  // one element: it already is its own suffix sum
-            hipLaunchKernelGGL(fr_horner_down_kernel, dim3((unsigned)((T + 255) / 256), ny), dim3(256), 0, st, in_at[k], cur, mult + k, carry, T,
-                               (fr_mem_t*)in_at[k], 0, (fr_mem_t*)nullptr, total, total, total);
-        } else if (d_out) {
-            hipLaunchKernelGGL(fr_horner_down_kernel, dim3((unsigned)((T + 255) / 256), ny), dim3(256), 0, st, d_in, cur, mult, carry, T, d_out, shift,
-                               d_first, in_stride, total, out_stride);
-        } else if (d_first) {
-            // only h_0: the value of the top level, or of the lone input element
-            for (size_t y = 0; y < count; y++)
-                HIP_TRY(hipMemcpyAsync(d_first + y, (top > 0 ? in_at[top] : d_in) + y * (top > 0 ? total : in_stride), sizeof(fr_mem_t), hipMemcpyDeviceToDevice, st));
+// quotient and remainder of `count` vectors (`stride` elements apart, like their quotients) by X - z: d_out[i - 1] = h_i, d_first[y] = h_0;
+// `d_out` may be null (only h_0 wanted)
+static void fr_divide_by_linear_run(lane_t& c, const fr_mem_t* d_in, size_t n, const fr_mem_t& z, fr_mem_t* d_out, fr_mem_t* d_first, size_t count, size_t stride) {
+    const auto value_from = [&](const fr_mem_t* src, size_t src_stride) {
+        for (size_t y = 0; y < count; y++) HIP_TRY(hipMemcpyAsync(d_first + y, src + y * src_stride, sizeof(fr_mem_t), hipMemcpyDeviceToDevice, c.stream));
+    };
+    if (n == 1) {
+        // a lone coefficient is its own h_0: one level and no chunk values, where a sweep always has two
+        c.poly[4].ensure(sizeof(fr_mem_t) * 3);
+        hipLaunchKernelGGL(fr_horner_multipliers_kernel, dim3(1), dim3(1), 0, c.stream, z, c.poly[4].as<fr_mem_t>(), 1);
+        value_from(d_in, stride);
+    } else {
+        const fr_horner_geometry_t g = fr_horner_geometry(n, d_out != nullptr);
+        const fr_span_plain_t walk{d_in, d_out, stride, stride, 1};
+        fr_horner_sweep sweep(c, g, n, z, count, g.route ? 0 : count);
+        sweep.up(walk);
+        if (d_out) {
+            sweep.down(walk, d_first);
+        } else {
+            // only h_0: the value of the top level.  The levels above level 0 still take their way down, as they always have here (the fold's
+            // value-only path never did): launches nobody reads, kept so that this call's launch sequence stays what it was
+            sweep.down_above();
+            value_from(sweep.kept, 1);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -172,7 +211,7 @@ static RustError fr_divide_by_linear_impl(void* quotient, void* remainder, const
         fr_mem_t* dq = (quotient && n > 1) ? fr_stage_out(c, 1, quotient, n - 1, on_device) : nullptr;
         c.poly[2].ensure(sizeof(fr_mem_t) * count);
         fr_mem_t* drem = c.poly[2].as<fr_mem_t>();
-        fr_suffix_horner(c, din, n, z, dq, 1, drem, count, stride, stride);
+        fr_divide_by_linear_run(c, din, n, z, dq, drem, count, stride);
         if (dq) fr_finish_out(c, dq, quotient, n - 1, on_device);
         // device operands inside a scope: delivered by snarkvm_hip_scope_end; host operands: the call waits below, the value is there on return
         if (remainder) c.host_result(remainder, drem, sizeof(fr_mem_t) * count, on_device != 0);
@@ -396,7 +435,7 @@ int snarkvm_hip_selftest_fr_lincomb(void* out, size_t n_out, size_t count, const
     return 0;
 }
 
-// ---- opening fold: a combination, its quotient by X - point and its value (poly.hip.h: fr_open_up_kernel ... fr_open2_down_kernel) -------
+// ---- opening fold: a combination, its quotient by X - point and its value (poly.hip.h: fr_span_fold_t under fr_horner_sweep) -------------
 // What the device call and its host replay share: validation, operand order, the split into launches and the choice of the route.
 // nullptr, or why the call is refused (hipErrorInvalidValue); needs no device.  Nothing has been touched either way.  An empty plan: the
 // combination is zero.  The LAST launch of the plan is the fused sweep, the ones before it are plain fr_lincomb_kernel launches.  With a
@@ -431,66 +470,29 @@ static const char* fr_open_plan(const void* quotient, size_t n, size_t count, co
     while (at < live.size());
     return nullptr;
 }
-// enqueues the pass on the lane's stream (route and levels: fr_horner_geometry, fr_horner_levels - level 0 is the fused one); -> where the value
-// h_0 will be (device memory, the lane's poly[4])
+// enqueues the pass on the lane's stream: the leading accumulating launches, then one fr_horner_sweep over the fold's span policy; -> where the
+// value h_0 will be (device memory, the lane's poly[4]: the sweep's kept elements, a top value per table and the result behind them)
 static const fr_mem_t* fr_open_run(lane_t& c, fr_mem_t* dq, size_t n, const fr_mem_t& z, const std::vector<fr_lincomb_launch_t>& plan) {
     hipStream_t st = c.stream;
     const fr_horner_geometry_t g = fr_horner_geometry(n, dq != nullptr);
     // a list longer than one table, quotient wanted: the leading tables are plain accumulating passes into the quotient buffer
     if (dq)
         for (size_t j = 0; j + 1 < plan.size(); j++) hipLaunchKernelGGL(fr_lincomb_kernel, dim3(fr_grid(n)), dim3(256), 0, st, dq, n, plan[j].t);
-    if (g.route == 1) {
-        const size_t nblocks = g.blocks;
-        c.poly[4].ensure(sizeof(fr_mem_t) * (HORNER2_TAB + nblocks * HORNER2_B + nblocks + 1));
-        fr_mem_t* tab = c.poly[4].as<fr_mem_t>();
-        fr_mem_t* hs = tab + HORNER2_TAB;
-        fr_mem_t* bv = hs + nblocks * HORNER2_B;
-        fr_mem_t* res = bv + nblocks;
-        hipLaunchKernelGGL(fr_horner2_tables_kernel, dim3(1), dim3(HORNER2_B), 0, st, z, tab, g.C);
-        hipLaunchKernelGGL(fr_open2_up_kernel, dim3((unsigned)nblocks), dim3(HORNER2_B), 0, st, dq, n, z, (const fr_mem_t*)tab, hs, bv, g.C, plan.back().t);
-        hipLaunchKernelGGL(fr_open2_down_kernel, dim3((unsigned)nblocks), dim3(HORNER2_B), 0, st, dq, n, z, (const fr_mem_t*)tab, (const fr_mem_t*)hs, (const fr_mem_t*)bv,
-                           g.C, res);
-        HIP_TRY(hipGetLastError());
-        return res;
+    // the value alone (always route 0): by linearity one up sweep per table, the top values - kept[0 .. nl) - added in list order
+    const size_t nl = dq ? 1 : plan.size(), tops = g.route ? 0 : nl;
+    fr_horner_sweep sweep(c, g, n, z, 1, tops + 1);
+    fr_mem_t* res = sweep.kept + tops;
+    if (dq) {
+        // level 0 of the way down turns the combination, parked in the quotient buffer on the way up, into the quotient
+        const fr_span_fold_t walk{dq, plan.back().t};
+        sweep.up(walk);
+        sweep.down(walk, res);
+    } else {
+        for (size_t j = 0; j < nl; j++) sweep.up(fr_span_fold_t{nullptr, plan[j].t}, j);
+        if (nl > 1) hipLaunchKernelGGL(fr_open_sum_kernel, dim3(1), dim3(1), 0, st, (const fr_mem_t*)sweep.kept, (uint32_t)nl, res);
     }
-    const std::vector<size_t> sizes = fr_horner_levels(n, POLY_CHUNK);
-    const int top = (int)sizes.size() - 1;
-    std::vector<size_t> off(sizes.size(), 0);  // level k >= 1 at cv + off[k]
-    size_t total = 0;
-    for (int k = 1; k <= top; k++) off[k] = total, total += sizes[k];
-    const size_t nl = plan.size();
-    // mult[top + 1] | res | tops[nl] | cv[total]
-    c.poly[4].ensure(sizeof(fr_mem_t) * ((size_t)top + 1 + 1 + nl + total));
-    fr_mem_t* mult = c.poly[4].as<fr_mem_t>();
-    fr_mem_t* res = mult + top + 1;
-    fr_mem_t* tops = res + 1;
-    fr_mem_t* cv = tops + nl;
-    hipLaunchKernelGGL(fr_horner_multipliers_kernel, dim3(1), dim3(1), 0, st, z, mult, top + 1);
-    // level k's chunk values; the single value of the top level goes to `top_at`
-    const auto level = [&](int k, fr_mem_t* top_at) { return k == top ? top_at : cv + off[k]; };
-    const auto up_from = [&](const fr_lincomb_t& t, fr_mem_t* q, fr_mem_t* top_at) {
-        hipLaunchKernelGGL(fr_open_up_kernel, dim3((unsigned)((sizes[1] + 255) / 256)), dim3(256), 0, st, q, n, (const fr_mem_t*)mult, level(1, top_at), sizes[1], t);
-        for (int k = 1; k < top; k++)
-            hipLaunchKernelGGL(fr_horner_up_kernel, dim3((unsigned)((sizes[k + 1] + 255) / 256), 1u), dim3(256), 0, st, (const fr_mem_t*)level(k, top_at), sizes[k],
-                               (const fr_mem_t*)(mult + k), level(k + 1, top_at), sizes[k + 1], (size_t)0, (size_t)0);
-    };
-    if (!dq) {
-        // the value alone: by linearity one up sweep per table, the top values added in list order
-        for (size_t j = 0; j < nl; j++) up_from(plan[j].t, nullptr, tops + j);
-        if (nl > 1) hipLaunchKernelGGL(fr_open_sum_kernel, dim3(1), dim3(1), 0, st, (const fr_mem_t*)tops, (uint32_t)nl, res);
-        HIP_TRY(hipGetLastError());
-        return nl > 1 ? res : tops;
-    }
-    up_from(plan.back().t, dq, tops);
-    // down: every level's chunk values become its suffix sums in place, level 0 turns the parked combination into the quotient
-    for (int k = top - 1; k >= 1; k--)
-        hipLaunchKernelGGL(fr_horner_down_kernel, dim3((unsigned)((sizes[k + 1] + 255) / 256), 1u), dim3(256), 0, st, (const fr_mem_t*)level(k, tops), sizes[k],
-                           (const fr_mem_t*)(mult + k), (const fr_mem_t*)level(k + 1, tops), sizes[k + 1], level(k, tops), 0, (fr_mem_t*)nullptr, (size_t)0, (size_t)0,
-                           (size_t)0);
-    hipLaunchKernelGGL(fr_open_down_kernel, dim3((unsigned)((sizes[1] + 255) / 256)), dim3(256), 0, st, dq, n, (const fr_mem_t*)mult, (const fr_mem_t*)level(1, tops),
-                       sizes[1], res);
     HIP_TRY(hipGetLastError());
-    return res;
+    return dq || nl > 1 ? res : sweep.kept;
 }
 RustError snarkvm_hip_fr_open_fold(void* quotient, void* remainder, size_t n, size_t count, const void* const* polys, const size_t* lens, const void* coeffs,
                                    const void* point, int on_device) {
@@ -544,7 +546,7 @@ int snarkvm_hip_selftest_fr_open_fold_geometry(size_t n, uint32_t* out5) {
     return 0;
 }
 // The same call on host memory with the CPU in the kernels' place, over a GIVEN geometry: the same plan, every launch a loop over its threads
-// through the kernels' own per-thread routines, a workgroup's LDS exchanges as loops over its threads.
+// through the kernels' own span policies and scaffold routines (poly.hip.h), a workgroup's LDS exchanges as loops over its threads.
 //   route 1 (needs a quotient): workgroups of HORNER2_B threads, C >= 1 coefficients per thread, ceil(n / (HORNER2_B C)) <= blocks <= 257
 //   route 0: chunks of C >= 2 coefficients at every level, blocks = the workgroups of 256 threads of level 0 = ceil(ceil(n / C) / 256)
 // 0, or -1 when the arguments or the geometry are refused.
@@ -576,46 +578,37 @@ int snarkvm_hip_selftest_fr_open_fold(void* quotient, void* remainder, size_t n,
             for (size_t i = 0; i < n; i++) fr_lincomb_at(plan[j].t, i).store(&q[i]);
     const fr_mem_t z = fr_mem_from_host(point);
     const fr_t m = fr_t::load(&z).from_mem_mont();
+    const fr_span_fold_t walk{q, plan.back().t};
     if (route == 1) {
         const uint32_t B = HORNER2_B;
-        // fr_horner2_tables_kernel: step[j] = m^(C 2^j), pw[j] = m^(C j), pwB[j] = m^(256 C j)
-        const fr_t mC = m.pow_u64(C), mB = mC.pow_u64(B);
-        std::vector<fr_t> step(8), pw(B + 1), pwB(B);
-        for (uint32_t t = 0; t < B; t++) pw[t] = mC.pow_u64(t), pwB[t] = mB.pow_u64(t);
-        pw[B] = mB;
-        for (uint32_t j = 0; j < 8; j++) step[j] = mC.pow_u64(1u << j);
-        // up: hs and bv pass through memory, as on the device
-        std::vector<fr_mem_t> hs((size_t)blocks * B), bv(blocks);
-        for (uint32_t b = 0; b < blocks; b++) {
-            std::vector<fr_t> h(B);
+        std::vector<fr_mem_t> tab(HORNER2_TAB), hs((size_t)blocks * B), bv(blocks);  // through memory, as on the device
+        for (uint32_t t = 0; t < B; t++) fr_horner2_tables_thread(m, tab.data(), C, t);
+        std::vector<fr_t> v(B), sh;  // a workgroup's values, thread by thread, and what it put into LDS before the barrier
+        const auto behind = [&](uint32_t s) { return sh[s]; };
+        for (uint32_t b = 0; b < blocks; b++) {  // fr_horner2_up_kernel
             for (uint32_t t = 0; t < B; t++) {
-                const size_t lo0 = ((size_t)b * B + t) * C, lo = lo0 < n ? lo0 : n, hi = lo + C < n ? lo + C : n;
-                h[t] = fr_open_up_chunk(plan.back().t, q, m, lo, hi);
+                const fr_horner_span_t sp = fr_horner_span((size_t)b * B + t, C, n);
+                v[t] = walk.up(m, sp.lo, sp.hi);
             }
             for (int j = 0; j < 8; j++) {
-                const std::vector<fr_t> sh = h;  // what the workgroup put into LDS before the barrier
-                for (uint32_t t = 0; t + (1u << j) < B; t++) h[t] = fr_open_scan_step(sh[t], step[j], sh[t + (1u << j)]);
+                sh = v;
+                for (uint32_t t = 0; t < B; t++) v[t] = fr_horner_scan_step(tab.data(), j, t, sh[t], behind);
             }
-            for (uint32_t t = 0; t < B; t++) h[t].store(&hs[(size_t)b * B + t]);
-            h[0].store(&bv[b]);
+            for (uint32_t t = 0; t < B; t++) v[t].store(&hs[(size_t)b * B + t]);
+            v[0].store(&bv[b]);
         }
-        for (uint32_t b = 0; b < blocks; b++) {
-            std::vector<fr_t> term(B, fr_t::zero());
-            for (uint32_t t = 0; t < B; t++)
-                if (b + 1 + t < blocks) term[t] = fr_open_carry_term(pwB[t], fr_t::load(&bv[b + 1 + t]));
+        for (uint32_t b = 0; b < blocks; b++) {  // fr_horner2_down_kernel
+            for (uint32_t t = 0; t < B; t++) v[t] = fr_horner_carry_term(tab.data(), bv.data(), b, t, blocks);
             for (uint32_t off = B / 2; off >= 1; off >>= 1) {
-                const std::vector<fr_t> sh = term;
-                for (uint32_t t = 0; t < off; t++) term[t] = sh[t] + sh[t + off];
+                sh = v;
+                for (uint32_t t = 0; t < B; t++) v[t] = fr_horner_carry_step(off, t, sh[t], behind);
             }
-            const fr_t carry = term[0];
+            const fr_t carry = v[0];
             for (uint32_t t = 0; t < B; t++) {
-                const size_t lo = ((size_t)b * B + t) * C;
-                if (lo >= n) continue;
-                const size_t hi = lo + C < n ? lo + C : n;
-                fr_t h = fr_open_thread_carry(pw[B - 1 - t], carry);
-                if (t + 1 < B) h = h + fr_t::load(&hs[(size_t)b * B + t + 1]);
-                h = fr_open_down_chunk(q, m, h, lo, hi);
-                if (lo == 0) h.store(&res);
+                const fr_horner_span_t sp = fr_horner_span((size_t)b * B + t, C, n);
+                if (sp.empty()) continue;
+                const fr_t h = walk.down(m, fr_horner_thread_carry(tab.data(), hs.data(), b, t, carry), sp.lo, sp.hi);
+                if (sp.lo == 0) h.store(&res);
             }
         }
     } else {
@@ -631,26 +624,32 @@ int snarkvm_hip_selftest_fr_open_fold(void* quotient, void* remainder, size_t n,
                 p = p.pow_u64(C);
             }
         }
-        const auto chunk_hi = [&](size_t t, size_t cur) { return (t + 1) * (size_t)C < cur ? (t + 1) * (size_t)C : cur; };
-        // level k >= 1 of one up sweep; -> the levels' values, cv[top] the single top value
-        const auto up_from = [&](const fr_lincomb_t& tb, fr_mem_t* qq) {
-            std::vector<std::vector<fr_mem_t>> cv(top + 1);
-            cv[1].resize(sizes[1]);
-            for (size_t t = 0; t < sizes[1]; t++) fr_open_up_chunk(tb, qq, mult[0], t * C, chunk_hi(t, n)).store(&cv[1][t]);
-            for (int k = 1; k < top; k++) {
-                cv[k + 1].resize(sizes[k + 1]);
-                for (size_t t = 0; t < sizes[k + 1]; t++) {  // fr_horner_up_kernel
-                    fr_t acc = fr_t::zero();
-                    for (size_t i = chunk_hi(t, sizes[k]); i-- > t * C;) acc = fr_t::load(&cv[k][i]) + mult[k] * acc;
-                    acc.store(&cv[k + 1][t]);
-                }
+        std::vector<std::vector<fr_mem_t>> cv(top + 1);  // level k >= 1: the chunk values of level k - 1, cv[top] the single top value
+        for (int k = 1; k <= top; k++) cv[k].resize(sizes[k]);
+        const auto in_place = [&](int k) { return fr_span_plain_t{cv[k].data(), cv[k].data(), 0, 0, 0}; };
+        // one level of a sweep: the threads of fr_horner_up_kernel / fr_horner_down_kernel
+        const auto up_level = [&](int k, const auto& w) {
+            for (size_t t = 0; t < sizes[k + 1]; t++) {
+                const fr_horner_span_t sp = fr_horner_span(t, C, sizes[k]);
+                w.up(mult[k], sp.lo, sp.hi).store(&cv[k + 1][t]);
             }
-            return cv;
+        };
+        const auto down_level = [&](int k, const auto& w) {
+            for (size_t t = 0; t < sizes[k + 1]; t++) {
+                const fr_horner_span_t sp = fr_horner_span(t, C, sizes[k]);
+                const fr_t h = w.down(mult[k], fr_horner_chunk_carry(cv[k + 1].data(), t, sizes[k + 1]), sp.lo, sp.hi);
+                if (k == 0 && t == 0) h.store(&res);
+            }
+        };
+        const auto up = [&](const fr_span_fold_t& w) {
+            up_level(0, w);
+            for (int k = 1; k < top; k++) up_level(k, in_place(k));
+            return fr_t::load(&cv[top][0]);
         };
         if (!q) {
             fr_t s = fr_t::zero();
             for (size_t j = 0; j < plan.size(); j++) {
-                const fr_t v = fr_t::load(&up_from(plan[j].t, nullptr)[top][0]);
+                const fr_t v = up(fr_span_fold_t{nullptr, plan[j].t});
                 if (plan.size() == 1)
                     v.store(&res);
                 else
@@ -658,20 +657,9 @@ int snarkvm_hip_selftest_fr_open_fold(void* quotient, void* remainder, size_t n,
             }
             if (plan.size() > 1) s.store(&res);
         } else {
-            std::vector<std::vector<fr_mem_t>> cv = up_from(plan.back().t, q);
-            for (int k = top - 1; k >= 1; k--)
-                for (size_t t = 0; t < sizes[k + 1]; t++) {  // fr_horner_down_kernel, shift 0, in place
-                    fr_t acc = t + 1 < sizes[k + 1] ? fr_t::load(&cv[k + 1][t + 1]) : fr_t::zero();
-                    for (size_t i = chunk_hi(t, sizes[k]); i-- > t * C;) {
-                        acc = fr_t::load(&cv[k][i]) + mult[k] * acc;
-                        acc.store(&cv[k][i]);
-                    }
-                }
-            for (size_t t = 0; t < sizes[1]; t++) {
-                const fr_t h_hi = t + 1 < sizes[1] ? fr_t::load(&cv[1][t + 1]) : fr_t::zero();
-                const fr_t h = fr_open_down_chunk(q, mult[0], h_hi, t * C, chunk_hi(t, n));
-                if (t == 0) h.store(&res);
-            }
+            up(walk);
+            for (int k = top - 1; k >= 1; k--) down_level(k, in_place(k));
+            down_level(0, walk);
         }
     }
     if (remainder) memcpy(remainder, &res, sizeof res);

@@ -3,7 +3,7 @@
 // form (a * 2^256 mod r), so that data produced by an NTT can feed a commitment without leaving HBM:
 //
 //   fr_vec_op_kernel            a+b, a-b, a*b, a*b-c, a*s, a-s, a+b*s, s-a       second.rs:104-122 (rowcheck), kzg10/mod.rs:295-300
-//   fr_horner_up/down_kernel    suffix Horner sums h_i = sum_{k>=i} a_k z^(k-i)  -> p / (X - z) and p(z)
+//   fr_horner(2)_up/down_kernel suffix Horner sums h_i = sum_{k>=i} a_k z^(k-i)  -> p / (X - z) and p(z); templates over a span policy
 //                                                                                 kzg10/mod.rs:213-236, dense.rs:98-114
 //   fr_batch_inverse_kernel     v_i <- coeff / v_i, zeros stay zero              fields/src/lib.rs:66-129
 //   fr_distribute_powers_kernel v_i <- v_i * c * g^i                             fft/domain.rs:224-254
@@ -14,7 +14,8 @@
 //   fr_witness_evals_kernel     w's evaluations on the variable domain: the interleaving gather minus x     first.rs:127-161 (round 1)
 //   fr_rowcheck_fold_kernel     sum_k mu_k (a_k b_k - c_k) and the per-member counts of a_k b_k != c_k      second.rs:76-142, selectors.rs:88-99 (round 2)
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
-//   fr_open(2)_up/down_kernel   (sum_k c_k p_k) / (X - z) and its value at z, the combination formed once  sonic_pc/mod.rs:286-342, varuna.rs:572-605
+//   fr_span_fold_t              (sum_k c_k p_k) / (X - z) and its value at z, the combination formed once: the same sweeps over the fold's policy
+//                                                                                 sonic_pc/mod.rs:286-342, varuna.rs:572-605
 //   fr_reduce_kernel            sum_i a_i, sum_i a_i b_i -> one element              fft/evaluations.rs:85-92 (evaluate_with_coeffs), first.rs:119
 //   fr_support_kernel           trimmed length, leading zeros, non-zero count        dense.rs:66-96 (degree, is_zero), kzg10/mod.rs:455-467
 //   fr_spmv_seg_kernel          y = M x over a registered CSR matrix, segment by segment  round_functions/mod.rs:131-188 (z_M), third.rs:303-306 (M(alpha, .))
@@ -64,8 +65,8 @@ static __global__ void fr_vec_op_kernel(int op, fr_mem_t* out, const fr_mem_t* a
 // ---- suffix Horner sums --------------------------------------------------------------------------------------------
 // h_i = sum_{k >= i} a_k m^(k-i) satisfies h_i = a_i + m h_(i+1): a linear recurrence, parallelised over chunks of
 // POLY_CHUNK consecutive coefficients.  `up` evaluates each chunk on its own (cv_t = chunk polynomial at m); the chunk
-// values form the same problem with multiplier m^POLY_CHUNK (solved recursively, api.hip); `down` replays each chunk
-// from its incoming carry h_(end of chunk) and writes every h_i.  A thread walks its chunk downwards, so consecutive
+// values form the same problem with multiplier m^POLY_CHUNK (solved recursively, api_poly.hip: fr_horner_sweep); `down` replays
+// each chunk from its incoming carry h_(end of chunk) and writes every h_i.  A thread walks its chunk downwards, so consecutive
 // reads of one thread share a cache line.
 static constexpr int POLY_CHUNK = 32;
 
@@ -78,41 +79,69 @@ static __global__ void fr_horner_multipliers_kernel(fr_mem_t m_mem, fr_mem_t* mu
         m = m.pow_u64(POLY_CHUNK);
     }
 }
-static __global__ void fr_horner_up_kernel(const fr_mem_t* __restrict__ in, size_t n, const fr_mem_t* __restrict__ m_mem, fr_mem_t* __restrict__ cv,
-                                    size_t T, size_t in_stride, size_t cv_stride) {
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    in += (size_t)blockIdx.y * in_stride;
-    cv += (size_t)blockIdx.y * cv_stride;
-    const fr_t m = fr_t::load(m_mem).from_mem_mont();
-    const size_t lo = t * POLY_CHUNK;
-    const size_t hi = (lo + POLY_CHUNK < n) ? lo + POLY_CHUNK : n;
-    fr_t acc = fr_t::zero();
-    for (size_t i = hi; i-- > lo;) acc = fr_t::load(&in[i]) + m * acc;
-    acc.store(&cv[t]);
+
+// The sweeps are written once, as scaffolds over a SPAN POLICY: a small struct, passed by kernel argument, that says how a thread walks its own
+// span [lo, hi) of the coefficients.  The scaffold owns everything around the walk - which span is whose, the chunk values or the workgroup's
+// scan, a thread's incoming h, where h_0 goes.  A policy offers
+//   at(y)                  the policy of batch member y (blockIdx.y of the strided entry points)
+//   up(m, lo, hi)          -> sum_(lo <= i < hi) a_i m^(i - lo), the span's polynomial at m
+//   down(m, h_hi, lo, hi)  -> h_lo, every h_i of the span delivered on the way
+// all SV_HD, so the host replay (snarkvm_hip_selftest_fr_open_fold) runs the same bodies.  fr_span_plain_t: the division of a vector;
+// fr_span_fold_t (below, with the opening fold): the division of a combination formed on the way.
+
+// The span of the thread that owns coefficients th C .. th C + C - 1 of n; empty, at n, behind the end.
+struct fr_horner_span_t {
+    size_t lo, hi;
+    SV_HD bool empty() const { return lo == hi; }
+};
+SV_HD fr_horner_span_t fr_horner_span(size_t th, size_t C, size_t n) {
+    const size_t lo = th * C < n ? th * C : n;
+    return {lo, lo + C < n ? lo + C : n};
 }
-// carry[t + 1] = h at the first index of chunk t + 1 (nullptr when there is a single chunk).  Writes out[i - shift] = h_i
-// for i >= shift and *first = h_0 when shift == 1 (quotient by X - m: q_(i-1) = h_i, remainder = h_0).
-// in == out is allowed when shift == 0.
-static __global__ void fr_horner_down_kernel(const fr_mem_t* in, size_t n, const fr_mem_t* __restrict__ m_mem, const fr_mem_t* __restrict__ carry,
-                                      size_t T, fr_mem_t* out, int shift, fr_mem_t* first, size_t in_stride, size_t carry_stride, size_t out_stride) {
+// reads in[i], writes out[i - shift] = h_i for i >= shift (the quotient by X - m is shift 1: q_(i-1) = h_i, and h_0 the remainder, which the
+// scaffold delivers).  in == out is allowed when shift == 0: the levels above the input run in place.  `out` is not read by `up`.
+struct fr_span_plain_t {
+    const fr_mem_t* in;
+    fr_mem_t* out;
+    size_t in_stride, out_stride;
+    int shift;
+    SV_HD fr_span_plain_t at(size_t y) const { return {in + y * in_stride, out ? out + y * out_stride : nullptr, in_stride, out_stride, shift}; }
+    SV_HD fr_t up(const fr_t& m, size_t lo, size_t hi) const {
+        fr_t h = fr_t::zero();
+        for (size_t i = hi; i-- > lo;) h = fr_t::load(&in[i]) + m * h;
+        return h;
+    }
+    SV_HD fr_t down(const fr_t& m, fr_t h, size_t lo, size_t hi) const {
+        for (size_t i = hi; i-- > lo;) {
+            h = fr_t::load(&in[i]) + m * h;
+            if (i >= (size_t)shift) h.store(&out[i - shift]);
+        }
+        return h;
+    }
+};
+
+// cv[t] = the value of chunk t at m (one level of the recursion; cv of batch member y starts cv_stride elements behind that of y - 1)
+template <class S>
+static __global__ void __launch_bounds__(256) fr_horner_up_kernel(S walk, size_t n, const fr_mem_t* __restrict__ m_mem, fr_mem_t* __restrict__ cv, size_t T,
+                                                                  size_t cv_stride) {
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= T) return;
-    in += (size_t)blockIdx.y * in_stride;
-    if (carry) carry += (size_t)blockIdx.y * carry_stride;
-    out += (size_t)blockIdx.y * out_stride;
-    if (first) first += blockIdx.y;
     const fr_t m = fr_t::load(m_mem).from_mem_mont();
-    const size_t lo = t * POLY_CHUNK;
-    const size_t hi = (lo + POLY_CHUNK < n) ? lo + POLY_CHUNK : n;
-    fr_t acc = (carry && t + 1 < T) ? fr_t::load(&carry[t + 1]) : fr_t::zero();
-    for (size_t i = hi; i-- > lo;) {
-        acc = fr_t::load(&in[i]) + m * acc;
-        if (i >= (size_t)shift)
-            acc.store(&out[i - shift]);
-        else if (first)
-            acc.store(first);
-    }
+    const fr_horner_span_t sp = fr_horner_span(t, POLY_CHUNK, n);
+    walk.at(blockIdx.y).up(m, sp.lo, sp.hi).store(&cv[(size_t)blockIdx.y * cv_stride + t]);
+}
+// h behind chunk t of T: carry[t + 1] = h at the first index of chunk t + 1 (the level above, after its own down sweep)
+SV_HD fr_t fr_horner_chunk_carry(const fr_mem_t* carry, size_t t, size_t T) { return t + 1 < T ? fr_t::load(&carry[t + 1]) : fr_t::zero(); }
+// first[y] = h_0 unless null
+template <class S>
+static __global__ void __launch_bounds__(256) fr_horner_down_kernel(S walk, size_t n, const fr_mem_t* __restrict__ m_mem, const fr_mem_t* __restrict__ carry, size_t T,
+                                                                    size_t carry_stride, fr_mem_t* __restrict__ first) {
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    const fr_t m = fr_t::load(m_mem).from_mem_mont();
+    const fr_horner_span_t sp = fr_horner_span(t, POLY_CHUNK, n);
+    const fr_t h = walk.at(blockIdx.y).down(m, fr_horner_chunk_carry(carry + (size_t)blockIdx.y * carry_stride, t, T), sp.lo, sp.hi);
+    if (t == 0 && first) h.store(&first[blockIdx.y]);
 }
 
 // ---- the same sums with a scan inside every workgroup (round 5) --------------------------------------------------------
@@ -125,16 +154,40 @@ static __global__ void fr_horner_down_kernel(const fr_mem_t* in, size_t n, const
 // Exact field arithmetic in another order: the same values bit for bit.
 static constexpr int HORNER2_B = 256;
 // tab: [0, 8) step[j] = m^(C 2^j) | [8, 8 + 257) pw[j] = m^(C j) | [265, 265 + 256) pwB[j] = m^(256 C j); internal form
-static constexpr int HORNER2_TAB = 8 + 257 + 256;
-static __global__ void __launch_bounds__(HORNER2_B) fr_horner2_tables_kernel(fr_mem_t m_mem, fr_mem_t* __restrict__ tab, uint32_t C) {
-    const uint32_t t = threadIdx.x;
-    const fr_t m = fr_t::load(&m_mem).from_mem_mont();
+enum { HORNER2_STEP = 0, HORNER2_PW = 8, HORNER2_PWB = 8 + 257, HORNER2_TAB = 8 + 257 + 256 };
+// what thread t of the one workgroup writes (m: the true internal form)
+SV_HD void fr_horner2_tables_thread(const fr_t& m, fr_mem_t* tab, uint32_t C, uint32_t t) {
     const fr_t mC = m.pow_u64(C);
     const fr_t mB = mC.pow_u64(HORNER2_B);
-    mC.pow_u64(t).store(&tab[8 + t]);
-    mB.pow_u64(t).store(&tab[8 + 257 + t]);
-    if (t == 0) mB.store(&tab[8 + 256]);
-    if (t < 8) mC.pow_u64(1u << t).store(&tab[t]);
+    mC.pow_u64(t).store(&tab[HORNER2_PW + t]);
+    mB.pow_u64(t).store(&tab[HORNER2_PWB + t]);
+    if (t == 0) mB.store(&tab[HORNER2_PW + HORNER2_B]);
+    if (t < 8) mC.pow_u64(1u << t).store(&tab[HORNER2_STEP + t]);
+}
+static __global__ void __launch_bounds__(HORNER2_B) fr_horner2_tables_kernel(fr_mem_t m_mem, fr_mem_t* __restrict__ tab, uint32_t C) {
+    fr_horner2_tables_thread(fr_t::load(&m_mem).from_mem_mont(), tab, C, threadIdx.x);
+}
+// The arithmetic of the workgroup scan and of a workgroup's incoming carry, thread by thread; `behind(s)` reads what thread s of the workgroup
+// put into the exchange before the barrier (LDS in the kernels, a copy of the threads' values in the host replay).
+// Kogge-Stone step j < 8 of thread t
+template <class Get>
+SV_HD fr_t fr_horner_scan_step(const fr_mem_t* tab, int j, uint32_t t, const fr_t& h, Get behind) {
+    return t + (1u << j) < HORNER2_B ? h + fr_t::load(&tab[HORNER2_STEP + j]) * behind(t + (1u << j)) : h;
+}
+// carry of workgroup b = h at the first coefficient of workgroup b + 1 = sum_(s > b) bv[s] m^(256 C (s - b - 1)): thread t's term of it, and
+// one step of the tree that adds the terms up into thread 0 (off = 128, 64 .. 1)
+SV_HD fr_t fr_horner_carry_term(const fr_mem_t* tab, const fr_mem_t* bv, uint32_t b, uint32_t t, uint32_t nblocks) {
+    return b + 1 + t < nblocks ? fr_t::load(&tab[HORNER2_PWB + t]) * fr_t::load(&bv[b + 1 + t]) : fr_t::zero();
+}
+template <class Get>
+SV_HD fr_t fr_horner_carry_step(uint32_t off, uint32_t t, const fr_t& term, Get behind) {
+    return t < off ? term + behind(t + off) : term;
+}
+// h behind the span of thread t of workgroup b: the workgroup's own suffix sum from thread t + 1 on, plus the carry moved across the threads
+// in between
+SV_HD fr_t fr_horner_thread_carry(const fr_mem_t* tab, const fr_mem_t* hs, uint32_t b, uint32_t t, const fr_t& carry) {
+    const fr_t h = fr_t::load(&tab[HORNER2_PW + HORNER2_B - 1 - t]) * carry;
+    return t + 1 < HORNER2_B ? h + fr_t::load(&hs[(size_t)b * HORNER2_B + t + 1]) : h;
 }
 __device__ __forceinline__ void horner2_lds_put(uint32_t* sh, uint32_t t, const fr_t& x) {
 #pragma unroll
@@ -147,73 +200,55 @@ __device__ __forceinline__ fr_t horner2_lds_get(const uint32_t* sh, uint32_t t) 
     return x;
 }
 // hs[block * 256 + t] = the suffix sum of the block's thread values from thread t on (= h at the first coefficient of thread t, the
-// block taken alone); bv[block] = hs[block * 256] (the block's polynomial at m)
-static __global__ void __launch_bounds__(HORNER2_B) fr_horner2_up_kernel(const fr_mem_t* __restrict__ in, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab,
-                                                                  fr_mem_t* __restrict__ hs, fr_mem_t* __restrict__ bv, uint32_t C, size_t in_stride,
-                                                                  size_t hs_stride, size_t bv_stride) {
+// block taken alone); bv[block] = hs[block * 256] (the block's polynomial at m); those of batch member y start hs_stride and bv_stride
+// elements behind those of y - 1
+template <class S>
+static __global__ void __launch_bounds__(HORNER2_B) fr_horner2_up_kernel(S walk, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab, fr_mem_t* __restrict__ hs,
+                                                                         fr_mem_t* __restrict__ bv, uint32_t C, size_t hs_stride, size_t bv_stride) {
     __shared__ uint32_t sh[9 * HORNER2_B];
     const uint32_t t = threadIdx.x;
-    in += (size_t)blockIdx.y * in_stride;
+    const auto behind = [&](uint32_t s) { return horner2_lds_get(sh, s); };
     hs += (size_t)blockIdx.y * hs_stride;
     bv += (size_t)blockIdx.y * bv_stride;
     const fr_t m = fr_t::load(&m_mem).from_mem_mont();
-    const size_t lo = ((size_t)blockIdx.x * HORNER2_B + t) * C;
-    const size_t hi = lo + C < n ? lo + C : n;
-    fr_t h = fr_t::zero();
-    for (size_t i = hi; i > lo;) {
-        i--;
-        h = fr_t::load(&in[i]) + m * h;
-    }
+    const fr_horner_span_t sp = fr_horner_span((size_t)blockIdx.x * HORNER2_B + t, C, n);
+    fr_t h = walk.at(blockIdx.y).up(m, sp.lo, sp.hi);
 #pragma unroll 1
     for (int j = 0; j < 8; j++) {
         horner2_lds_put(sh, t, h);
         __syncthreads();
-        if (t + (1u << j) < HORNER2_B) h = h + fr_t::load(&tab[j]) * horner2_lds_get(sh, t + (1u << j));
+        h = fr_horner_scan_step(tab, j, t, h, behind);
         __syncthreads();
     }
     h.store(&hs[(size_t)blockIdx.x * HORNER2_B + t]);
     if (t == 0) h.store(&bv[blockIdx.x]);
 }
-// out[i - shift] = h_i (i >= shift), *first = h_0 when shift == 1.  nblocks <= 256 + 1.
-static __global__ void __launch_bounds__(HORNER2_B) fr_horner2_down_kernel(const fr_mem_t* in, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab,
-                                                                    const fr_mem_t* __restrict__ hs, const fr_mem_t* __restrict__ bv, uint32_t C, fr_mem_t* out,
-                                                                    int shift, fr_mem_t* first, size_t in_stride, size_t hs_stride, size_t bv_stride,
-                                                                    size_t out_stride) {
+// first[y] = h_0 unless null.  nblocks <= 256 + 1.
+template <class S>
+static __global__ void __launch_bounds__(HORNER2_B) fr_horner2_down_kernel(S walk, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab,
+                                                                           const fr_mem_t* __restrict__ hs, const fr_mem_t* __restrict__ bv, uint32_t C, size_t hs_stride,
+                                                                           size_t bv_stride, fr_mem_t* __restrict__ first) {
     __shared__ uint32_t sh[9 * HORNER2_B];
     const uint32_t t = threadIdx.x, b = blockIdx.x, nblocks = gridDim.x;
-    in += (size_t)blockIdx.y * in_stride;
+    const auto behind = [&](uint32_t s) { return horner2_lds_get(sh, s); };
     hs += (size_t)blockIdx.y * hs_stride;
     bv += (size_t)blockIdx.y * bv_stride;
-    out += (size_t)blockIdx.y * out_stride;
-    if (first) first += blockIdx.y;
     const fr_t m = fr_t::load(&m_mem).from_mem_mont();
-    // carry = h at the first coefficient of block b + 1 = sum_(s > b) bv[s] m^(256 C (s - b - 1)): one term per thread, then a tree of sums
-    fr_t term = fr_t::zero();
-    if (b + 1 + t < nblocks) term = fr_t::load(&tab[8 + 257 + t]) * fr_t::load(&bv[b + 1 + t]);
+    fr_t term = fr_horner_carry_term(tab, bv, b, t, nblocks);
 #pragma unroll 1
     for (uint32_t off = HORNER2_B / 2; off >= 1; off >>= 1) {
         horner2_lds_put(sh, t, term);
         __syncthreads();
-        if (t < off) term = term + horner2_lds_get(sh, t + off);
+        term = fr_horner_carry_step(off, t, term, behind);
         __syncthreads();
     }
     horner2_lds_put(sh, t, term);
     __syncthreads();
-    const fr_t carry = horner2_lds_get(sh, 0);
-    const size_t lo = ((size_t)b * HORNER2_B + t) * C;
-    if (lo >= n) return;
-    const size_t hi = lo + C < n ? lo + C : n;
-    // h behind this thread's coefficients: the block's own suffix sum from thread t + 1 on, plus the carry moved across the threads in between
-    fr_t h = fr_t::load(&tab[8 + (HORNER2_B - 1 - t)]) * carry;
-    if (t + 1 < HORNER2_B) h = h + fr_t::load(&hs[(size_t)b * HORNER2_B + t + 1]);
-    for (size_t i = hi; i > lo;) {
-        i--;
-        h = fr_t::load(&in[i]) + m * h;
-        if (i >= (size_t)shift)
-            h.store(&out[i - shift]);
-        else if (first)
-            h.store(first);
-    }
+    const fr_t carry = behind(0);
+    const fr_horner_span_t sp = fr_horner_span((size_t)b * HORNER2_B + t, C, n);
+    if (sp.empty()) return;
+    const fr_t h = walk.at(blockIdx.y).down(m, fr_horner_thread_carry(tab, hs, b, t, carry), sp.lo, sp.hi);
+    if (sp.lo == 0 && first) h.store(&first[blockIdx.y]);
 }
 
 // ---- batch inversion -----------------------------------------------------------------------------------------------
@@ -350,111 +385,38 @@ static __global__ void __launch_bounds__(256) fr_lincomb_kernel(fr_mem_t* out, s
 // q).  Without a quotient there is no q to park in: the sweep takes a whole table (fr_open_plan).
 static constexpr int FR_OPEN_FUSE = 1;
 static_assert(FR_OPEN_FUSE >= 1 && FR_OPEN_FUSE <= FR_LINCOMB_CHUNK, "the fused sweep takes one table");
-// The per-thread routines: the kernels below and the host replay (snarkvm_hip_selftest_fr_open_fold) both call them.
-SV_HD fr_t fr_open_up_chunk(const fr_lincomb_t& t, fr_mem_t* q, const fr_t& m, size_t lo, size_t hi) {
-    // the table holds the parked sum alone (every member has gone through fr_lincomb_kernel): comb[i] is in q[i] already
-    const bool parked = q && t.count == 1 && t.p[0] == q;
-    fr_t h = fr_t::zero();
-    for (size_t i = hi; i > lo;) {
-        i--;
-        const fr_t x = parked ? fr_t::load(&q[i]) : fr_lincomb_at(t, i);
-        if (q && !parked) x.store(&q[i]);
-        h = x + m * h;
+// The span policy of the fold: the sweeps themselves are the scaffolds of the suffix Horner sums above, in either route; the fold has no batch.
+struct fr_span_fold_t {
+    fr_mem_t* q;
+    fr_lincomb_t t;
+    SV_HD const fr_span_fold_t& at(size_t) const { return *this; }
+    SV_HD fr_t up(const fr_t& m, size_t lo, size_t hi) const {
+        // the table holds the parked sum alone (every member has gone through fr_lincomb_kernel): comb[i] is in q[i] already
+        const bool parked = q && t.count == 1 && t.p[0] == q;
+        fr_t h = fr_t::zero();
+        for (size_t i = hi; i-- > lo;) {
+            const fr_t x = parked ? fr_t::load(&q[i]) : fr_lincomb_at(t, i);
+            if (q && !parked) x.store(&q[i]);
+            h = x + m * h;
+        }
+        return h;
     }
-    return h;
-}
-// h: h_hi on entry; q[i] = h_(i+1) for lo <= i < hi on return, which is h_lo
-SV_HD fr_t fr_open_down_chunk(fr_mem_t* q, const fr_t& m, fr_t h, size_t lo, size_t hi) {
-    for (size_t i = hi; i > lo;) {
-        i--;
-        const fr_t x = fr_t::load(&q[i]);
-        h.store(&q[i]);
-        h = x + m * h;
+    // q[i] = h_(i+1) for lo <= i < hi on return
+    SV_HD fr_t down(const fr_t& m, fr_t h, size_t lo, size_t hi) const {
+        for (size_t i = hi; i-- > lo;) {
+            const fr_t x = fr_t::load(&q[i]);
+            h.store(&q[i]);
+            h = x + m * h;
+        }
+        return h;
     }
-    return h;
-}
-// one Kogge-Stone step of the workgroup scan (fr_horner2_up_kernel), and the pieces of a workgroup's incoming carry (fr_horner2_down_kernel)
-SV_HD fr_t fr_open_scan_step(const fr_t& h, const fr_t& step, const fr_t& behind) { return h + step * behind; }
-SV_HD fr_t fr_open_carry_term(const fr_t& pw_block, const fr_t& block_value) { return pw_block * block_value; }
-SV_HD fr_t fr_open_thread_carry(const fr_t& pw_thread, const fr_t& carry) { return pw_thread * carry; }
-
-// level 0 of the chunk recursion (fr_horner_up_kernel / fr_horner_down_kernel), fused: cv[t] = the value of chunk t of the combination
-static __global__ void __launch_bounds__(256) fr_open_up_kernel(fr_mem_t* q, size_t n, const fr_mem_t* __restrict__ m_mem, fr_mem_t* __restrict__ cv, size_t T,
-                                                                fr_lincomb_t t) {
-    const size_t th = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (th >= T) return;
-    const fr_t m = fr_t::load(m_mem).from_mem_mont();
-    const size_t lo = th * POLY_CHUNK;
-    const size_t hi = (lo + POLY_CHUNK < n) ? lo + POLY_CHUNK : n;
-    fr_open_up_chunk(t, q, m, lo, hi).store(&cv[th]);
-}
-// carry[t + 1] = h at the first index of chunk t + 1 (nullptr when there is a single chunk); *first = h_0
-static __global__ void __launch_bounds__(256) fr_open_down_kernel(fr_mem_t* q, size_t n, const fr_mem_t* __restrict__ m_mem, const fr_mem_t* __restrict__ carry, size_t T,
-                                                                  fr_mem_t* __restrict__ first) {
-    const size_t th = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (th >= T) return;
-    const fr_t m = fr_t::load(m_mem).from_mem_mont();
-    const size_t lo = th * POLY_CHUNK;
-    const size_t hi = (lo + POLY_CHUNK < n) ? lo + POLY_CHUNK : n;
-    const fr_t h_hi = (carry && th + 1 < T) ? fr_t::load(&carry[th + 1]) : fr_t::zero();
-    const fr_t h = fr_open_down_chunk(q, m, h_hi, lo, hi);
-    if (th == 0 && first) h.store(first);
-}
+};
 // first[0] = vals[0] + vals[1] + ... in list order (the values of the launches of a member list longer than one table, evaluation only)
 static __global__ void fr_open_sum_kernel(const fr_mem_t* __restrict__ vals, uint32_t count, fr_mem_t* __restrict__ first) {
     if (blockIdx.x | threadIdx.x) return;
     fr_t s = fr_t::zero();
     for (uint32_t k = 0; k < count; k++) s = s + fr_t::load(&vals[k]);
     s.store(first);
-}
-// the scan form (fr_horner2_up_kernel / fr_horner2_down_kernel over the tables of fr_horner2_tables_kernel), fused
-static __global__ void __launch_bounds__(HORNER2_B) fr_open2_up_kernel(fr_mem_t* q, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab, fr_mem_t* __restrict__ hs,
-                                                                       fr_mem_t* __restrict__ bv, uint32_t C, fr_lincomb_t t) {
-    __shared__ uint32_t sh[9 * HORNER2_B];
-    const uint32_t th = threadIdx.x;
-    const fr_t m = fr_t::load(&m_mem).from_mem_mont();
-    const size_t lo0 = ((size_t)blockIdx.x * HORNER2_B + th) * C;
-    const size_t lo = lo0 < n ? lo0 : n;
-    const size_t hi = lo + C < n ? lo + C : n;
-    fr_t h = fr_open_up_chunk(t, q, m, lo, hi);
-#pragma unroll 1
-    for (int j = 0; j < 8; j++) {
-        horner2_lds_put(sh, th, h);
-        __syncthreads();
-        if (th + (1u << j) < HORNER2_B) h = fr_open_scan_step(h, fr_t::load(&tab[j]), horner2_lds_get(sh, th + (1u << j)));
-        __syncthreads();
-    }
-    h.store(&hs[(size_t)blockIdx.x * HORNER2_B + th]);
-    if (th == 0) h.store(&bv[blockIdx.x]);
-}
-// nblocks <= 256 + 1
-static __global__ void __launch_bounds__(HORNER2_B) fr_open2_down_kernel(fr_mem_t* q, size_t n, fr_mem_t m_mem, const fr_mem_t* __restrict__ tab,
-                                                                         const fr_mem_t* __restrict__ hs, const fr_mem_t* __restrict__ bv, uint32_t C,
-                                                                         fr_mem_t* __restrict__ first) {
-    __shared__ uint32_t sh[9 * HORNER2_B];
-    const uint32_t th = threadIdx.x, b = blockIdx.x, nblocks = gridDim.x;
-    const fr_t m = fr_t::load(&m_mem).from_mem_mont();
-    // carry = h at the first coefficient of block b + 1 = sum_(s > b) bv[s] m^(256 C (s - b - 1)): one term per thread, then a tree of sums
-    fr_t term = fr_t::zero();
-    if (b + 1 + th < nblocks) term = fr_open_carry_term(fr_t::load(&tab[8 + 257 + th]), fr_t::load(&bv[b + 1 + th]));
-#pragma unroll 1
-    for (uint32_t off = HORNER2_B / 2; off >= 1; off >>= 1) {
-        horner2_lds_put(sh, th, term);
-        __syncthreads();
-        if (th < off) term = term + horner2_lds_get(sh, th + off);
-        __syncthreads();
-    }
-    horner2_lds_put(sh, th, term);
-    __syncthreads();
-    const fr_t carry = horner2_lds_get(sh, 0);
-    const size_t lo = ((size_t)b * HORNER2_B + th) * C;
-    if (lo >= n) return;
-    const size_t hi = lo + C < n ? lo + C : n;
-    // h behind this thread's coefficients: the block's own suffix sum from thread th + 1 on, plus the carry moved across the threads in between
-    fr_t h = fr_open_thread_carry(fr_t::load(&tab[8 + (HORNER2_B - 1 - th)]), carry);
-    if (th + 1 < HORNER2_B) h = h + fr_t::load(&hs[(size_t)b * HORNER2_B + th + 1]);
-    h = fr_open_down_chunk(q, m, h, lo, hi);
-    if (lo == 0 && first) h.store(first);
 }
 
 // ---- X^D - 1 -------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """`snarkvm_hip_fr_open_fold` without a GPU (include/snarkvm_hip.h): the per-thread routines of the fused sweeps (csrc/poly.hip.h:
-fr_lincomb_at, fr_open_up_chunk, fr_open_down_chunk, the scan step and carry routines) and the host-side bookkeeping of the call -
+fr_lincomb_at, the walks of fr_span_fold_t and fr_span_plain_t, the span, scan and carry routines of the scaffolds) and the host-side bookkeeping of the call -
 validation, longest-first order, the split into tables of FR_LINCOMB_CHUNK operands, the choice of the route - run on the CPU through
 snarkvm_hip_selftest_fr_open_fold, which replays the launch plan over a given geometry.  Every comparison is bit-exact against the oracle
 (tests/helpers/open_fold_cases.py): its AXPY chain for the combination, poly_divide by X - z for the quotient, poly_evaluate for the value.

@@ -1,4 +1,4 @@
-"""`snarkvm_hip_fr_open_fold` on the device (include/snarkvm_hip.h; csrc/poly.hip.h: fr_open_up_kernel ... fr_open2_down_kernel): a linear
+"""`snarkvm_hip_fr_open_fold` on the device (include/snarkvm_hip.h; csrc/poly.hip.h: the fr_horner(2)_up/down_kernel sweeps over fr_span_fold_t): a linear
 combination of polynomials, its quotient by X - z and its value in one sweep up and one down, and the resident drivers of
 snarkvm_amd/sonic_pc.py on top of it (`evaluate_combinations_device`, `open_combinations_device`).
 
@@ -287,6 +287,56 @@ def test_two_logical_devices():
     env = dict(os.environ, SNARKVM_HIP_DEVICES="0,0")
     r = subprocess.run([sys.executable, "-c", MULTI_SCRIPT % util.ROOT], capture_output=True, text=True, env=env, timeout=300, cwd=util.ROOT)
     assert "OPEN_FOLD_MULTI_OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+# ---- the two span policies under one sweep (csrc/poly.hip.h: fr_span_plain_t, fr_span_fold_t) ---------------------------------------
+# a lone coefficient; one, two and three levels of the recursion; the first sizes of the scan route; a part-filled last workgroup; C = 16
+TIE_LENGTHS = [1, 2, 32, 33, 1025, 2047, 2048, 2049, 3 * 2048 + 1, (1 << 19) + 1]
+
+
+def fold_of_one_member_is_the_division():
+    """the fold of a single resident member with coefficient one against `snarkvm_hip_fr_divide_by_linear` of that member: both instantiations
+    of every sweep kernel walk the same coefficients, so quotient and value agree bit for bit - with a quotient (either route) and without"""
+    L = _lib.lib()
+    top = max(TIE_LENGTHS)
+    z = oc.point("random")
+    src = HipMem.from_numpy(lc.rnd(top, 3))
+    folded = HipMem.from_numpy(np.full((top + 1, 4), GUARD, dtype=np.uint64))
+    divided = HipMem.from_numpy(np.full((top, 4), GUARD, dtype=np.uint64))
+    for n in TIE_LENGTHS:
+        for quotient in (True, False):
+            value = plugin.fr_open_fold_device(folded.ptr if quotient else None, n, [src.ptr], [n], oc.ONE, z)
+            rem = np.full((1, 4), GUARD, dtype=np.uint64)
+            _lib.check(L.snarkvm_hip_fr_divide_by_linear(ctypes.c_void_p(divided.ptr) if quotient else None, ctypes.c_void_p(rem.ctypes.data), ctypes.c_void_p(src.ptr),
+                                                         ctypes.c_size_t(n), ctypes.c_void_p(z.ctypes.data), 1))
+            assert np.array_equal(value, rem), (n, quotient)
+            if quotient:
+                got = folded.download(32 * (n + 1), dtype=np.uint64).reshape(-1, 4)
+                want = divided.download(32 * n, dtype=np.uint64).reshape(-1, 4)
+                assert np.array_equal(got[: n - 1], want[: n - 1]), n
+                assert not got[n - 1].any() and (got[n] == GUARD).all() and (want[n - 1] == GUARD).all(), n
+    for m in (src, folded, divided):
+        m.free()
+
+
+TIE_SCRIPT = r'''
+import sys
+sys.path.insert(0, %r)
+from tests.test_gpu_fr_open_fold import fold_of_one_member_is_the_division
+fold_of_one_member_is_the_division()
+print("OPEN_FOLD_TIE_OK")
+'''
+
+
+def test_fold_of_one_member_is_the_division():
+    fold_of_one_member_is_the_division()
+
+
+def test_fold_of_one_member_is_the_division_on_the_chunk_recursion():
+    """the same with the scan route switched off (tuning horner2=0, read once per process): every length takes the recursion"""
+    env = dict(os.environ, SNARKVM_HIP_TUNING="horner2=0")
+    r = subprocess.run([sys.executable, "-c", TIE_SCRIPT % util.ROOT], capture_output=True, text=True, env=env, timeout=300, cwd=util.ROOT)
+    assert r.returncode == 0 and "OPEN_FOLD_TIE_OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
 
 
 # ---- the resident drivers (snarkvm_amd/sonic_pc.py) ---------------------------------------------------------------------------------
