@@ -463,6 +463,29 @@ RustError snarkvm_hip_fr_selector_fold(void *h_out, size_t h_len, void *xg_out, 
  *  - Workspace: none with on_device = 1. */
 RustError snarkvm_hip_fr_witness_evals(void *out, size_t n, const void *w, size_t w_len, const void *x_evals, size_t input_size, int on_device);
 
+/* Assignment evaluations: Varuna's round 1 in lock step.  The vector above plus the evaluations of x_poly is the evaluation vector of the
+ * assignment z = w (X^|X| - 1) + x_poly itself (third.rs:236-239): the padded public input on the input subgroup, the private variables elsewhere -
+ * the interleaving of EvaluationDomain::reindex_by_subdomain (fft/domain.rs:322-344).  ONE inverse transform of it at |V| = n yields z; its quotient
+ * by X^|X| - 1 (snarkvm_hip_fr_divide_by_vanishing) is w and its remainder is x_poly, deg x_poly < |X|: no forward transform, no transform at |X|.
+ * `count` members (the instances of one circuit); member m reads the row v = vars + m * stride_vars and writes o = out + m * stride_out, both
+ * strides in elements (ignored when count == 1).  A row is  padded_public (input_size values) ++ private (num_vars - input_size values)  - the x
+ * operand of snarkvm_hip_fr_spmv for the circuit's matrices.  With ratio = n / input_size, for k < n:
+ *    o[k] = v[k / ratio]                                   when ratio divides k
+ *    o[k] = v[input_size + (k - k / ratio - 1)]            otherwise; zero where that index is >= num_vars.
+ * on_device governs out and vars.  All n elements of every member are written and nothing between the members; vars is never written.  No
+ * arithmetic: every element is copied bit for bit.
+ *  - count == 0 or n == 0 (arguments otherwise valid): success, nothing is touched and no device is needed.
+ *  - Refused with hipErrorInvalidValue before anything is launched and before a device is needed, out untouched: input_size == 0; input_size does
+ *    not divide n; n > 2^28; num_vars < input_size or num_vars > n (with n > 0); count > 65535; with count > 1, stride_out < n, stride_vars <
+ *    num_vars or a stride of more than 2^40 elements; out or vars NULL with n > 0 and count > 0; out overlapping vars (the spans of all
+ *    members); with on_device = 1, operands on different devices.
+ *  - With on_device = 1 inside a snarkvm_hip_scope the call is only enqueued.
+ *  - With on_device = 0 the rows (as they lie, gaps included) and the outputs are staged in lane buffers: one upload, one download per member.
+ *  - One launch: the member on blockIdx.y, up to 8192 workgroups of 256 threads per member (snarkvm_hip_selftest_fr_assignment_geometry).
+ *  - Workspace: none with on_device = 1; a repeated call grows nothing (snarkvm_hip_alloc_stats). */
+RustError snarkvm_hip_fr_assignment_evals(void *out, size_t n, const void *vars, size_t num_vars, size_t input_size, size_t count, size_t stride_out,
+                                          size_t stride_vars, int on_device);
+
 /* Rowcheck fold: the sums of Varuna's round 2 (calculate_rowcheck_witness, round_functions/second.rs:76-142, with apply_randomized_selector
  * without a remainder witness, ahp/selectors.rs:88-99) over `count` members (one per instance of every circuit of one domain size) of three
  * n-element vectors a[k], b[k], c[k] and a multiplier mu_k = multipliers[k]:
@@ -774,6 +797,13 @@ int snarkvm_hip_selftest_fr_selector_fold(void *h_out, size_t h_len, void *xg_ou
 /* snarkvm_hip_fr_witness_evals over host memory with the CPU in the kernel's place: the same validation, then a loop over k through the kernel's
  * own per-index routine (csrc/poly.hip.h: fr_witness_at).  0, or -1 when the arguments are refused. */
 int snarkvm_hip_selftest_fr_witness_evals(void *out, size_t n, const void *w, size_t w_len, const void *x_evals, size_t input_size);
+/* snarkvm_hip_fr_assignment_evals over host memory with the CPU in the kernel's place, over a GIVEN thread count (`threads` >= 1 per member, thread
+ * t owning k = t, t + threads, ...): the same validation, every element through the kernel's own per-index routine (csrc/poly.hip.h:
+ * fr_assignment_at).  0, or -1 when the arguments are refused.  fr_assignment_geometry: out3 = {workgroups, threads per workgroup} the device call
+ * launches per member of n elements, and the cap on the workgroups; 0, or -1 for a NULL out3 or n > 2^28. */
+int snarkvm_hip_selftest_fr_assignment_evals(void *out, size_t n, const void *vars, size_t num_vars, size_t input_size, size_t count,
+                                             size_t stride_out, size_t stride_vars, uint32_t threads);
+int snarkvm_hip_selftest_fr_assignment_geometry(size_t n, uint32_t *out3);
 /* snarkvm_hip_fr_rowcheck_fold over host memory with the CPU in the kernel's place: the same validation, member tables and split into launches,
  * every launch a loop over i through the kernel's own per-index routine (csrc/poly.hip.h: fr_rowcheck_at), the violation bits it returns counted
  * per member.  0, or -1 when the arguments are refused. */

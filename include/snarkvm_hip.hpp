@@ -240,6 +240,15 @@ inline void fr_witness_evals(void* out, size_t n, const DevicePoly& w, const voi
     check(snarkvm_hip_fr_witness_evals(out, n, w.data, w.len, x_evals, input_size, on_device ? 1 : 0));
 }
 
+// Round 1 in lock step (snarkvm_hip.h: snarkvm_hip_fr_assignment_evals): member m of `count` reads the row vars + m * stride_vars - padded public
+// input (input_size values) ++ private variables, num_vars in all - and writes the n evaluations of its assignment z to out + m * stride_out
+// (strides in elements).  The inverse transform of a member is z; z div (X^input_size - 1) is w and z mod (X^input_size - 1) is x_poly.  With
+// on_device inside a Scope the call is only enqueued.
+inline void fr_assignment_evals(void* out, size_t n, const void* vars, size_t num_vars, size_t input_size, size_t count, size_t stride_out,
+                                size_t stride_vars, bool on_device) {
+    check(snarkvm_hip_fr_assignment_evals(out, n, vars, num_vars, input_size, count, stride_out, stride_vars, on_device ? 1 : 0));
+}
+
 // The sums of Varuna's round 2 in one device pass (snarkvm_hip.h: snarkvm_hip_fr_rowcheck_fold): out[i] = sum_k mu_k (a[k][i] b[k][i] - c[k][i]) and
 // violations[k] = the number of i with a[k][i] b[k][i] != c[k][i], over members of n elements each.  multipliers: a.size() x 32 bytes of HOST memory,
 // Montgomery form; violations: a.size() values of HOST memory, delivered when the Scope ends for a call inside one.  Either output may be nullptr

@@ -1,11 +1,12 @@
 // api_selftest.hip - the test hooks that need no MSM entry point: the field operations on the host and in a kernel (snarkvm_hip_selftest_field /
 // snarkvm_hip_devtest_field), the MSM planner, the naive G1 sum, the lazily reduced G1 arithmetic, the host-side finish of an MSM, and the lane-pair and
-// sixteen-lane Fq2 arithmetic of the G2 kernels on simulated lanes.  All but devtest_field run on the host alone.  A translation unit of its own (as
-// api_msmtest.hip): the units that own the MSM entry points compile without them.  python -m snarkvm_amd.build --fast (SV_NO_G2) leaves the two G2 hooks
-// as the refusal at the end of this file.
+// sixteen-lane Fq2 arithmetic of the G2 kernels on simulated lanes, and the host twin of the assignment gather of Varuna's round 1 (the refusals it shares
+// with the entry point: fr_call.hip.h).  All but devtest_field run on the host alone.  A translation unit of its own (as api_msmtest.hip): the units that own
+// the MSM entry points compile without them.  python -m snarkvm_amd.build --fast (SV_NO_G2) leaves the two G2 hooks as the refusal at the end of this file.
 #include "msm_run.hip.h"
 #include "g1_generator.hip.h"
 #include "testrng.hip.h"
+#include "fr_call.hip.h"  // fr_assignment_check, fr_grid
 
 static void tu_set_kernel_attributes() {}  // no kernel of this unit needs an attribute
 
@@ -282,6 +283,26 @@ int snarkvm_hip_selftest_g1_finish(const void* planes_jacobian, const int32_t* p
     }
 }
 
+// snarkvm_hip_fr_assignment_evals on host memory with the CPU in the kernel's place, over a GIVEN thread count: the same validation, then per member
+// thread t over k = t, t + threads, ... through the kernel's own per-index routine (poly.hip.h: fr_assignment_at).  0, or -1 when refused.
+int snarkvm_hip_selftest_fr_assignment_evals(void* out, size_t n, const void* vars, size_t num_vars, size_t input_size, size_t count, size_t stride_out, size_t stride_vars,
+                                             uint32_t threads) {
+    if (threads < 1 || fr_assignment_check(out, n, vars, num_vars, input_size, count, stride_out, stride_vars)) return -1;
+    if (count == 0 || n == 0) return 0;
+    if (count == 1) stride_out = stride_vars = 0;
+    for (size_t m = 0; m < count; m++)
+        for (size_t t = 0; t < threads && t < n; t++)
+            for (size_t k = t; k < n; k += threads)
+                fr_assignment_at((fr_mem_t*)out + m * stride_out, (const fr_mem_t*)vars + m * stride_vars, (uint32_t)num_vars, (uint32_t)input_size, (uint32_t)(n / input_size),
+                                 (uint32_t)k);
+    return 0;
+}
+// what snarkvm_hip_fr_assignment_evals launches per member of n elements: out3 = {workgroups, threads per workgroup, the cap on the workgroups}
+int snarkvm_hip_selftest_fr_assignment_geometry(size_t n, uint32_t* out3) {
+    if (!out3 || n > FR_ASSIGNMENT_N_MAX) return -1;
+    out3[0] = fr_grid(n, FR_ASSIGNMENT_BLOCK), out3[1] = FR_ASSIGNMENT_BLOCK, out3[2] = fr_grid(FR_ASSIGNMENT_N_MAX, FR_ASSIGNMENT_BLOCK);
+    return 0;
+}
 
 #ifdef SV_NO_G2  // development builds only: no Fq2 arithmetic to test
 int snarkvm_hip_selftest_fq2_pair(const void*, size_t, uint64_t, int) { return -1; }

@@ -1,4 +1,4 @@
-// api_varuna.hip - the Varuna entry points of the C ABI (poly.hip.h): round 3's selector fold, round 1's witness evaluations, round 2's rowcheck
+// api_varuna.hip - the Varuna entry points of the C ABI (poly.hip.h): round 3's selector fold, round 1's witness and assignment evaluations, round 2's rowcheck
 // fold, the sparse matrix-vector product over a registered matrix, round 4's matrix-sumcheck evaluations over a registered arithmetization, and
 // the circuit index (arithmetize, register_csr), each with its host twin and geometry hook.  The frame they share: fr_call.hip.h.
 #include "fr_call.hip.h"
@@ -204,6 +204,34 @@ int snarkvm_hip_selftest_fr_witness_evals(void* out, size_t n, const void* w, si
     if (fr_witness_check(out, n, w, w_len, x_evals, input_size)) return -1;
     for (size_t k = 0; k < n; k++) fr_witness_at((fr_mem_t*)out, (const fr_mem_t*)w, (uint32_t)w_len, (const fr_mem_t*)x_evals, (uint32_t)(n / input_size), (uint32_t)k);
     return 0;
+}
+// Round 1 in lock step: the evaluations of z for every instance of a circuit (poly.hip.h: fr_assignment_evals_kernel); the refusals are
+// fr_call.hip.h's fr_assignment_check, the host twin lives in api_selftest.hip.
+RustError snarkvm_hip_fr_assignment_evals(void* out, size_t n, const void* vars, size_t num_vars, size_t input_size, size_t count, size_t stride_out, size_t stride_vars,
+                                          int on_device) {
+    if (const char* why = fr_assignment_check(out, n, vars, num_vars, input_size, count, stride_out, stride_vars))
+        return fail((int)hipErrorInvalidValue, std::string("snarkvm_hip: fr_assignment_evals: ") + why);
+    if (count == 0 || n == 0) return ok();
+    if (count == 1) stride_out = stride_vars = 0;
+    API_BEGIN_DEV(device_for(out, on_device ? 1 : 0))
+    const fr_mem_t* dv = (const fr_mem_t*)vars;
+    fr_mem_t* dout = (fr_mem_t*)out;
+    size_t so = stride_out;
+    if (on_device) {
+        fr_same_device(c, vars, "fr_assignment_evals: vars lives on another device than out");
+    } else {
+        // host operands: the rows as they lie (members and the gaps between them), out packed member after member and downloaded member by member
+        dv = fr_stage_in(c, 0, vars, (count - 1) * stride_vars + num_vars, 0);
+        dout = fr_stage_out(c, 1, out, count * n, 0);
+        so = n;
+    }
+    hipLaunchKernelGGL(fr_assignment_evals_kernel, dim3(fr_grid(n, FR_ASSIGNMENT_BLOCK), (unsigned)count), dim3(FR_ASSIGNMENT_BLOCK), 0, c.stream, dout, (uint32_t)n, dv,
+                       (uint32_t)num_vars, (uint32_t)input_size, (uint32_t)(n / input_size), so, stride_vars);
+    HIP_TRY(hipGetLastError());
+    if (!on_device)
+        for (size_t m = 0; m < count; m++) HIP_TRY(hipMemcpyAsync((fr_mem_t*)out + m * stride_out, dout + m * n, sizeof(fr_mem_t) * n, hipMemcpyDeviceToHost, c.stream));
+    fr_call_done(c, on_device);
+    API_END
 }
 
 // ---- round 2: the rowcheck fold (poly.hip.h: fr_rowcheck_fold_kernel) ------------------------------------------------------------------------

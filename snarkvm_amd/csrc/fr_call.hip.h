@@ -110,6 +110,28 @@ struct fr_range_t {
     return false;
 }
 
+// ---- the assignment gather (poly.hip.h: fr_assignment_evals_kernel) ------------------------------------------------------------
+// What snarkvm_hip_fr_assignment_evals (api_varuna.hip) and its host twin (api_selftest.hip) share: nullptr, or why the call is refused
+// (hipErrorInvalidValue); needs no device.  Nothing has been touched either way.  After it no index the kernel forms can leave a member's
+// row (num_vars elements) or its output (n elements), and no member's span can wrap.
+static constexpr size_t FR_ASSIGNMENT_N_MAX = (size_t)1 << 28;
+[[maybe_unused]] static const char* fr_assignment_check(const void* out, size_t n, const void* vars, size_t num_vars, size_t input_size, size_t count, size_t stride_out,
+                                                        size_t stride_vars) {
+    if (input_size == 0) return "input_size is 0";
+    if (n % input_size) return "input_size does not divide n";
+    if (n > FR_ASSIGNMENT_N_MAX) return "n above 2^28";
+    if (n && (num_vars < input_size || num_vars > n)) return "num_vars is below input_size or above n";
+    if (count > 65535) return "more than 65535 members";
+    if (count > 1 && (stride_out < n || stride_vars < num_vars)) return "a stride is shorter than its vector";
+    // count < 2^16 members of at most 2^40 elements apart: no span below can wrap, in elements or in bytes
+    if (count > 1 && (stride_out > ((size_t)1 << 40) || stride_vars > ((size_t)1 << 40))) return "a stride of more than 2^40 elements";
+    if (n && count && (!out || !vars)) return "null operand of non-zero length";
+    if (n && count && fr_spans_overlap(out, (count - 1) * stride_out + n, vars, (count - 1) * stride_vars + num_vars)) return "out overlaps vars";
+    return nullptr;
+}
+// the launch of one member's n elements: fr_grid's workgroups of 256 threads, the member on blockIdx.y
+static constexpr unsigned FR_ASSIGNMENT_BLOCK = 256;
+
 // ---- host operands -----------------------------------------------------------------------------------------------------------
 // host operands: one lane buffer (c.poly[slot]) holds the outputs and the operands of a call one behind the other; one upload per operand,
 // one download per output.  begin() takes the total up front - ensure() may move the buffer; a pack that was never begun (device operands)

@@ -12,6 +12,7 @@
 //   fr_selector_fold_kernel     sum_k mu_k (quotient, tiled remainder) of p_k by X^n_k - 1, and the sums over the n_k-th roots
 //                                                                                 third.rs:126-327, selectors.rs:100-121 (round 3)
 //   fr_witness_evals_kernel     w's evaluations on the variable domain: the interleaving gather minus x     first.rs:127-161 (round 1)
+//   fr_assignment_evals_kernel  z's evaluations on the variable domain: public and private variables interleaved   first.rs:127-161, fft/domain.rs:322-344 (round 1, lock step)
 //   fr_rowcheck_fold_kernel     sum_k mu_k (a_k b_k - c_k) and the per-member counts of a_k b_k != c_k      second.rs:76-142, selectors.rs:88-99 (round 2)
 //   fr_lincomb_kernel           sum_k c_k p_k over ragged lengths, one pass          sonic_pc/mod.rs:413-473, 548-564 (open_combinations)
 //   fr_span_fold_t              (sum_k c_k p_k) / (X - z) and its value at z, the combination formed once: the same sweeps over the fold's policy
@@ -586,6 +587,34 @@ static __global__ void __launch_bounds__(256) fr_witness_evals_kernel(fr_mem_t* 
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t st = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += st) fr_witness_at(out, w, w_len, x, ratio, (uint32_t)i);
+}
+// Round 1 in lock step: the evaluations of z ITSELF on the variable domain.  Adding x_poly's evaluations back to the vector above leaves the
+// padded public input on the input subgroup and the private variables elsewhere - the interleaving of reindex_by_subdomain
+// (fft/domain.rs:322-344) over the row v = public (input_size values) ++ private (num_vars - input_size values), the x operand of the
+// circuit's sparse products - and since z = w (X^|X| - 1) + x_poly with deg x_poly < |X|, ONE inverse transform of it yields z, whose quotient
+// by X^|X| - 1 is w and whose remainder is x_poly.  No arithmetic: position k takes v[k / ratio] when ratio divides k, otherwise
+// v[input_size + k - k / ratio - 1], zero from num_vars on.  An element travels as its two 16-byte halves, untouched (no limb unpacking); a
+// wave's stores cover 2 KB of consecutive bytes and both read streams only move forward with k.  blockIdx.y is the batch member (instance):
+// its row starts stride_vars elements after the previous one's, its output stride_out elements.  Indices are 32-bit: n <= 2^28, and the
+// launch stays under 2^21 threads per member, so i + st cannot wrap.  Registers (gfx950, -O3, -Rpass-analysis=kernel-resource-usage):
+// fr_assignment_evals_kernel 14 VGPRs, 26 SGPRs, 8 waves per SIMD, no scratch, no LDS.
+SV_HD void fr_assignment_at(fr_mem_t* out, const fr_mem_t* v, uint32_t num_vars, uint32_t input_size, uint32_t ratio, uint32_t k) {
+    const uint32_t q = k / ratio;
+    const uint32_t j = k == q * ratio ? q : input_size + (k - q - 1);
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (j < num_vars) {
+        const uint4* src = (const uint4*)&v[j];
+        lo = src[0], hi = src[1];
+    }
+    uint4* dst = (uint4*)&out[k];
+    dst[0] = lo, dst[1] = hi;
+}
+static __global__ void __launch_bounds__(256) fr_assignment_evals_kernel(fr_mem_t* __restrict__ out, uint32_t n, const fr_mem_t* __restrict__ vars, uint32_t num_vars,
+                                                                         uint32_t input_size, uint32_t ratio, size_t stride_out, size_t stride_vars) {
+    out += (size_t)blockIdx.y * stride_out, vars += (size_t)blockIdx.y * stride_vars;
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t st = gridDim.x * blockDim.x;
+    for (; i < n; i += st) fr_assignment_at(out, vars, num_vars, input_size, ratio, i);
 }
 // Round 2 (calculate_rowcheck_witness, second.rs:76-142, with apply_randomized_selector without a remainder witness, selectors.rs:88-99):
 // h_0 = sum over every instance k of every circuit of mu_k (z_a z_b - z_c) / v_R.  z_a z_b - z_c has degree <= 2 |R| - 2, its quotient by v_R

@@ -23,6 +23,11 @@ and the sums over the variable domain are ONE pass (`snarkvm_hip_fr_selector_fol
 Rounds 1 and 2 open a proof: w by the gather `snarkvm_hip_fr_witness_evals` between two transforms at |V|, h_0 for all instances of all circuits
 on one coset per domain size with `snarkvm_hip_fr_rowcheck_fold` as both the divisibility test and the sum.
 
+    z = iNTT_|V|(interleave(public, private)), w = z div (X^|X| - 1), x_poly = z mod (X^|X| - 1)     (`first_round_device`)
+
+Round 1 in lock step: every instance of every circuit from ONE gather (`snarkvm_hip_fr_assignment_evals`), one inverse transform and one division
+per instance, with z_a, z_b, z_c as three strided products per circuit - enqueued in the caller's scope like rounds 2 to 4.
+
     row, col, row_col, row_col_val on K, the twelve index polynomials, their commitments and the certificate
                                                                 ahp/indexer/indexer.rs:126-260, circuit.rs:142-155, varuna.rs:103-117 (`CircuitIndex`)
 
@@ -164,7 +169,8 @@ def _dev_ptr(x):
 
 def z_m(reg, padded_public, private, n_out=None):
     """z_M: the `inner_product` of round_functions/mod.rs:169-188 over every row of the registered matrix - variable i is
-    padded_public[i] below the number of public variables and private[i - that] above, i.e. x is simply public ++ private."""
+    padded_public[i] below the number of public variables and private[i - that] above, i.e. x is simply public ++ private.
+    All instances of a circuit at once, on device rows: `first_round_device`."""
     z = np.concatenate([np.asarray(padded_public, dtype=np.uint64).reshape(-1, 4), np.asarray(private, dtype=np.uint64).reshape(-1, 4)])
     return reg.mul(z, n_out)
 
@@ -357,7 +363,7 @@ def assignment_device(d_w, w_len, d_x, input_size, d_out):
     """`calculate_assignments` (third.rs:236-239) for one instance on device memory: d_out (w_len + input_size coefficients, the caller's) =
     w (X^input_size - 1) + x, with w of w_len coefficients at d_w and x of input_size coefficients at d_x - `fr_mul_by_vanishing`, then x added
     in place by one `fr_lincomb`.  d_out must overlap neither operand.  -> the number of coefficients written.  Inside a scope both calls are
-    only enqueued."""
+    only enqueued.  The lock-step route yields z before w, without either call: `first_round_device`."""
     n = int(w_len) + int(input_size)
     out = _dev_ptr(d_out)
     _lib.check(_lib.lib().snarkvm_hip_fr_mul_by_vanishing(out, _dev_ptr(d_w) or None, int(w_len), int(input_size), 1))
@@ -473,7 +479,8 @@ def witness_poly_device(d_w, w_len, d_x_poly, input_size, lg_variable_domain, d_
     `snarkvm_hip_fr_witness_evals` runs in place on its evaluations, the inverse transform yields w (X^|X| - 1) and `fr_divide_by_vanishing` by
     X^|X| - 1 the quotient; the remainder is tested with `fr_support` and a non-zero one raises ValueError (it cannot happen for valid sizes: the
     gathered vector vanishes on the input subgroup).  Workspace: |V| + |X| elements on `device` (the device of d_out), released on return.  The five
-    calls run in one scope and wait once.  Call it outside a scope: it reads the remainder test back.  -> the number of coefficients written."""
+    calls run in one scope and wait once.  Call it outside a scope: it reads the remainder test back.  -> the number of coefficients written.
+    Every instance of every circuit in one scope, from one inverse transform each and with nothing read back: `first_round_device`."""
     L = _lib.lib()
     V, X, w_len = 1 << int(lg_variable_domain), int(input_size), int(w_len)
     if X < 1 or X & (X - 1) or X > V:
@@ -495,6 +502,87 @@ def witness_poly_device(d_w, w_len, d_x_poly, input_size, lg_variable_domain, d_
     if int(support[0]) != 0:
         raise ValueError("Failed to divide by vanishing polynomial - non-zero remainder")
     return V - X
+
+
+def witness_label(circuit_id, poly, i):
+    """`witness_label` of ahp/ahp.rs:46-50"""
+    return f"circuit_{circuit_id}_{poly}_{i:0>8}"
+
+
+FirstRoundCircuit = collections.namedtuple("FirstRoundCircuit", "matrices lg_r lg_c lg_x vars num_vars stride instances")
+FirstRoundCircuit.__doc__ = """One circuit of round 1: `matrices` = the RegisteredMatrix of A, B, C (num_vars columns each), the constraint, variable and input
+domains 2^lg_r, 2^lg_c, 2^lg_x, and `vars`: a device arena (pointer or HipMem) of `instances` rows, row m starting m * stride elements in and
+holding padded_public (2^lg_x values) ++ private (num_vars - 2^lg_x values) - the x operand of the matrices' products."""
+
+FirstRoundWitness = collections.namedtuple("FirstRoundWitness", "z w x_poly z_m w_labeled")
+FirstRoundWitness.__doc__ = """What round 1 leaves for one circuit, one entry per instance each: DevicePoly `z` (|V| coefficients, untrimmed: `LinevalCircuit.assignments`),
+`w` (|V| - |X|) and `x_poly` (|X|); `z_m`: the (z_a, z_b, z_c) triples of |R| evaluations (`RowcheckCircuit.z`); `w_labeled`: the w as
+sonic_pc.ResidentPolynomial under `witness_label(circuit_id, "w", i)`, ready for `SonicKZG10.commit`."""
+
+
+def _ntt_batch_cap(lg):
+    """the vectors one launch sequence of `snarkvm_hip_ntt_device_batch` takes (include/snarkvm_hip.h)"""
+    return 48 if lg <= 26 else 48 >> (lg - 26)
+
+
+def first_round_device(circuits, device=-1, circuit_ids=None, hiding_bound=None):
+    """Round 1 in lock step over the FirstRoundCircuit list `circuits`, on device memory: for every instance of every circuit the assignment z,
+    the witness polynomial w (`calculate_w`, first.rs:127-161), x_poly (prover/state.rs:150) and z_a, z_b, z_c (round_functions/mod.rs:131-188).
+    The reference's evaluations of w plus those of x_poly are the evaluations of z itself - the public input on the input subgroup, the private
+    variables elsewhere, the interleaving of `reindex_by_subdomain` - and z = w (X^|X| - 1) + x_poly with deg x_poly < |X|, so
+        z = iNTT_|V|(interleave(public, private)),   w = z div (X^|X| - 1),   x_poly = z mod (X^|X| - 1).
+    Per circuit: ONE `snarkvm_hip_fr_assignment_evals` over all instances, the inverse transforms at |V| (`NTT_device_batch`, in chunks of what one
+    launch sequence takes), ONE `snarkvm_hip_fr_divide_by_vanishing_strided` and three strided `fr_spmv` over the rows with n_out = |R| - no
+    forward transform, no transform at |X|, no remainder to test.  One block of device memory per circuit holds z | w ++ x_poly | z_a | z_b | z_c
+    of every instance.  Field arithmetic is exact: every byte equals the per-instance route's (`witness_poly_device`, `assignment_device`, `z_m`).
+    Every call is only enqueued - in the caller's open scope, or in a scope of its own when the calling thread has none (then the host waits
+    once); nothing is read back.  circuit_ids: the ids the labels of w carry (default: the position in `circuits`); hiding_bound: that of every w
+    (`zk_bound`, first.rs:160).  -> one FirstRoundWitness per circuit."""
+    from . import sonic_pc
+
+    if circuit_ids is None:
+        circuit_ids = list(range(len(circuits)))
+    if len(circuit_ids) != len(circuits):
+        raise ValueError("first_round_device: one circuit id per circuit")
+    plans = []
+    for c in circuits:
+        V, X, R, count = 1 << int(c.lg_c), 1 << int(c.lg_x), 1 << int(c.lg_r), int(c.instances)
+        if X > V:
+            raise ValueError("first_round_device: the input domain is larger than the variable domain")
+        if not X <= int(c.num_vars) <= V:
+            raise ValueError("first_round_device: a row holds between |X| and |V| variables")
+        if len(c.matrices) != 3 or any(m.cols != int(c.num_vars) or m.rows > R for m in c.matrices):
+            raise ValueError("first_round_device: three matrices of num_vars columns and at most |R| rows each")
+        if count < 0 or (count > 1 and int(c.stride) < int(c.num_vars)):
+            raise ValueError("first_round_device: the rows of the arena overlap")
+        plans.append((V, X, R, count))
+    # per circuit: z of every instance | w ++ x_poly of every instance | z_a | z_b | z_c of every instance
+    mems = [HipMem(32 * max(count * (2 * V + 3 * R), 1), device) for V, X, R, count in plans]
+    out = []
+    if not mems:
+        return out
+    with _Scope(mems[0].ptr):
+        for c, cid, mem, (V, X, R, count) in zip(circuits, circuit_ids, mems, plans):
+            d_z, d_w, d_zm = mem.ptr, mem.ptr + 32 * count * V, mem.ptr + 32 * count * 2 * V
+            if count:
+                plugin.fr_assignment_evals_device(d_z, V, _dev_ptr(c.vars), c.num_vars, X, count, V, c.stride)
+                cap = _ntt_batch_cap(int(c.lg_c))
+                for first in range(0, count, cap):
+                    ptrs = [d_z + 32 * V * i for i in range(first, min(first + cap, count))]
+                    plugin.NTT_device_batch(int(c.lg_c), ptrs, directions=[1] * len(ptrs), types=[0] * len(ptrs))
+                # member i: quotient at d_w + i |V| (|V| - |X| coefficients), remainder right behind it (|X| coefficients)
+                _lib.check(_lib.lib().snarkvm_hip_fr_divide_by_vanishing_strided(d_w if V > X else None, d_w + 32 * (V - X), d_z, V, X, count, V))
+                for j, m in enumerate(c.matrices):
+                    m.mul_device(d_zm + 32 * count * R * j, R, c.vars, count, int(c.stride), R)
+            z = [DevicePoly(d_z + 32 * V * i, V, mem) for i in range(count)]
+            w = [DevicePoly(d_w + 32 * V * i, V - X, mem) for i in range(count)]
+            x_poly = [DevicePoly(d_w + 32 * (V * i + V - X), X, mem) for i in range(count)]
+            triples = [tuple(DevicePoly(d_zm + 32 * R * (count * j + i), R, mem) for j in range(3)) for i in range(count)]
+            labeled = [sonic_pc.ResidentPolynomial(witness_label(cid, "w", i), p.ptr, p.n, None, hiding_bound) for i, p in enumerate(w)]
+            for p in labeled:
+                p._owner = mem  # the block stays alive as long as a polynomial in it
+            out.append(FirstRoundWitness(z, w, x_poly, triples, labeled))
+    return out
 
 
 RowcheckCircuit = collections.namedtuple("RowcheckCircuit", "lg_r circuit_combiner instance_combiners z")

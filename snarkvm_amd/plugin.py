@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .layout import G1_AFFINE, G1_PROJECTIVE, NTTDirection, NTTInputOutputOrder, NTTType
 
-__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_evaluate_device", "fr_evaluate", "FR_EVALUATE_MEMBERS", "FR_EVALUATE_POINTS","fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "fr_arithmetize_device", "fr_arithmetize", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
+__all__ = ["NTT", "polymul", "polymul_device", "fr_lincomb_device", "FR_LINCOMB_CHUNK", "fr_open_fold_device", "fr_selector_fold_device", "FR_SELECTOR_CHUNK", "fr_witness_evals_device", "fr_assignment_evals_device", "fr_rowcheck_fold_device", "FR_ROWCHECK_CHUNK", "fr_reduce_device", "fr_reduce_strided_device", "fr_support_device", "fr_support_strided_device", "FR_REDUCE_SUM", "FR_REDUCE_DOT", "fr_evaluate_device", "fr_evaluate", "FR_EVALUATE_MEMBERS", "FR_EVALUATE_POINTS","fr_spmv_device", "fr_sumcheck_evals_device", "fr_sumcheck_evals", "fr_arithmetize_device", "fr_arithmetize", "msm", "set_base_cache", "base_cache_stats", "NTTInputOutputOrder", "NTTDirection", "NTTType"]
 
 
 def _ptr(a):
@@ -148,6 +148,16 @@ def fr_witness_evals_device(d_out, n, d_w, w_len, d_x_evals, input_size):
     if w_len < 0 or w_len > n - input_size:
         raise ValueError("w is longer than n - input_size")
     _lib.check(_lib.lib().snarkvm_hip_fr_witness_evals(_dp(d_out), n, _dp(d_w) if w_len else None, w_len, _dp(d_x_evals), input_size, 1))
+
+
+def fr_assignment_evals_device(d_out, n, d_vars, num_vars, input_size, count=1, stride_out=0, stride_vars=0):
+    """Extension (no reference counterpart): the gather of Varuna's round 1 in lock step over rows that live in device memory
+    (`snarkvm_hip_fr_assignment_evals`, on_device = 1).  Member m reads the row d_vars + m * stride_vars - padded_public (input_size values) ++
+    private (num_vars - input_size values), the x operand of `fr_spmv_device` - and writes the n evaluations of its assignment z on the variable
+    domain to d_out + m * stride_out (strides in elements): with ratio = n / input_size, row[k // ratio] when ratio divides k,
+    row[input_size + k - k // ratio - 1] elsewhere, zero from num_vars on.  d_out must not overlap d_vars.  Inside a scope the call is only
+    enqueued."""
+    _lib.check(_lib.lib().snarkvm_hip_fr_assignment_evals(_dp(d_out), int(n), _dp(d_vars), int(num_vars), int(input_size), int(count), int(stride_out), int(stride_vars), 1))
 
 
 FR_ROWCHECK_CHUNK = 24  # members per kernel launch of snarkvm_hip_fr_rowcheck_fold (include/snarkvm_hip.h; csrc/poly.hip.h FR_ROWCHECK_CHUNK)

@@ -7,6 +7,7 @@ Host mirror of the reference functions the Varuna prover runs between its NTTs a
     `poly += (coeff, cur_poly)` over the terms of a linear combination              polycommit/sonic_pc/mod.rs:413-473, 548-564
     apply_randomized_selector summed over the members of round 3 (`selector_fold`)  ahp/selectors.rs:100-121, round_functions/third.rs:179-213
     the gather of calculate_w between its two transforms (`witness_evals`)          round_functions/first.rs:127-161
+    the evaluations of z, whose inverse transform yields z, w and x_poly (`assignment_evals`)  first.rs:147-152, fft/domain.rs:322-344
     calculate_rowcheck_witness's sum and divisibility test (`rowcheck_fold`)        round_functions/second.rs:76-142, ahp/selectors.rs:88-99
     Evaluations::evaluate_with_coeffs (an inner product), sums over a domain        fft/evaluations.rs:90-92, round_functions/first.rs:119
     DensePolynomial::{degree, is_zero}, skip_leading_zeros_and_convert_to_bigints   fft/polynomial/dense.rs:66-96, kzg10/mod.rs:455-467
@@ -124,6 +125,22 @@ def witness_evals(w, x_evals, input_size):
         raise ValueError("input_size must divide n and w hold at most n - input_size elements")
     out = np.empty_like(x)
     _lib.check(_lib.lib().snarkvm_hip_fr_witness_evals(_p(out) if n else None, n, _p(w) if w.shape[0] else None, w.shape[0], _p(x) if n else None, int(input_size), 0))
+    return out
+
+
+def assignment_evals(rows, n, input_size):
+    """The gather of Varuna's round 1 in lock step over host arrays in one device pass (`snarkvm_hip_fr_assignment_evals`): rows = one
+    (num_vars, 4) array per instance, or one (instances, num_vars, 4) array - padded_public (input_size values) ++ private.  -> (instances, n, 4):
+    the evaluations of every assignment z on the variable domain of n elements, rows[m][k // ratio] where ratio = n / input_size divides k,
+    rows[m][input_size + k - k // ratio - 1] elsewhere (zero from num_vars on).  Its inverse transform is z; z div (X^input_size - 1) is w and
+    z mod (X^input_size - 1) is x_poly."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    rows = rows.reshape(1, -1, 4) if rows.ndim < 3 else rows.reshape(rows.shape[0], -1, 4)
+    count, num_vars, n, input_size = rows.shape[0], rows.shape[1], int(n), int(input_size)
+    if input_size <= 0 or n % input_size or not input_size <= num_vars <= max(n, input_size):
+        raise ValueError("input_size must divide n and a row hold between input_size and n elements")
+    out = np.empty((count, n, 4), dtype=np.uint64)
+    _lib.check(_lib.lib().snarkvm_hip_fr_assignment_evals(_p(out) if out.size else None, n, _p(rows) if rows.size else None, num_vars, input_size, count, n, num_vars, 0))
     return out
 
 
