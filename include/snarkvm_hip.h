@@ -871,6 +871,24 @@ RustError snarkvm_hip_devtest_field(int field, int op, const void *a, const void
  * selftest: on the host (the same source as the kernels, square roots included), returns 0, or 1 for a bad argument; devtest: one GPU thread per case. */
 int snarkvm_hip_selftest_field_ext(int op, const void *in, void *out, size_t n);
 RustError snarkvm_hip_devtest_field_ext(int op, const void *in, void *out, size_t n);
+/* The lazily reduced signed-limb arithmetic of the bucket-accumulation loops (csrc/ffl.hip.h, ffl2.hip.h, ffl2p.hip.h), one case per record.
+ * Operands and results are RAW limbs: a value V = 13 int32 words v_0 .. v_12 (value = sum v_i 2^(29 i), signed), a flag = one word; nothing
+ * normalises or reduces a result on the way out.  op (input record -> output record, in 32-bit words):
+ *   0  fql_t::mul: a, b -> V                 1  fql_t::sqr: a -> V                 2  fql_t::diff_of_products: a, b, c, d -> V
+ *   3  normalized: a -> V                    4  to_exact: a -> the 13 limbs of the canonical fq_t (x 2^377)
+ *   5  from_exact: 13 limbs of a canonical fq_t -> V                6  store_raw / load_raw: a -> the 12 words of the image, then load_raw of it
+ *   7  fqz_t: a, b, z -> a + b, a - b, a.dbl(), a.neg(), then the word z.is_zero()
+ *   8  xyzz_lazy_t::madd: x, y, zz, zzz, inf, px, py, negate -> the returned bool, x, y, zz, zzz, inf
+ *   9  per-lane helpers of the pair addition: a, b, c, t, y -> p = sub_norm(a, b, 1), sub_norm(a, c, -1), norm_k(t), cond_neg_canonical(y, true),
+ *      cond_neg_canonical(y, false), then the word is_zero_mod_q(p)
+ *  10  the pair product: a.c0, a.c1, b.c0, b.c1 -> per component (c0, then c1) the product's component, then the lane's prepared operands as the
+ *      exchange left them: opa_t X, Y (13 + 13 words), opb_t recv (14 words)
+ *  11  fq2p::xyzz_pair_t::madd: x.c0, x.c1, y.c0, y.c1, zz.c0, zz.c1, zzz.c0, zzz.c1, inf, px.c0, px.c1, py.c0, py.c1, negate -> the eight
+ *      components, inf
+ * selftest: on the host (ops 10, 11 through the two-lane host exchange), returns 0, or 1 for a bad argument; devtest: workgroups of 64 threads, one
+ * thread per case for ops 0 - 9, one DPP lane pair per case (even lane c0, odd lane c1) for ops 10, 11; n <= 2^24. */
+int snarkvm_hip_selftest_lazy_ext(int op, const void *in, void *out, size_t n);
+RustError snarkvm_hip_devtest_lazy_ext(int op, const void *in, void *out, size_t n);
 /* The scalar-read phase of a variable-base MSM on its own: n host scalars (32 B each; montgomery = 1: Fr memory images) go through the plan and the
  * digit parameters a device-side MSM of this geometry gets (window_bits, tables, table_bits as a registered handle passes them; a fused batch asks
  * for table_bits-wide windows) and through the stand-alone digit kernel that MSM would launch - u16 digits up to 16-bit windows, u32 digits above;

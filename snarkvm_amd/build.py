@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsnarkvm_hip.so")
-SOURCES = ["api.hip", "api_fr.hip", "api_poly.hip", "api_varuna.hip", "api_g2.hip", "api_serde.hip", "api_fieldtest.hip", "api_msmtest.hip", "api_tailtest.hip", "api_selftest.hip", "tail_g1.hip", "tail_g2.hip", "tail_g2_planes.hip", "tail_g2_fix.hip"]  # compiled in parallel, then linked (the tail_* units: the fold / bit-plane kernels, msm.hip.h)
+SOURCES = ["api.hip", "api_fr.hip", "api_poly.hip", "api_varuna.hip", "api_g2.hip", "api_serde.hip", "api_fieldtest.hip", "api_lazytest.hip", "api_msmtest.hip", "api_tailtest.hip", "api_selftest.hip", "tail_g1.hip", "tail_g2.hip", "tail_g2_planes.hip", "tail_g2_fix.hip"]  # compiled in parallel, then linked (the tail_* units: the fold / bit-plane kernels, msm.hip.h)
 
 
 def _inputs():

@@ -130,7 +130,8 @@ struct fql_t {
     // ---- products.  Column k of the double-width value: sum_(i+j=k) a_i b_j  -  sum_(i+j=k, j>=1) m_i q_j; m_k = column mod 2^29
     // (STEPS of them), then the column moves on by an arithmetic shift.  Result normalised, = (a b - m q) / 2^406.
     // Operand bounds: |a_i b_j| < 2^58 for every pair that meets (normalised x normalised, normalised x difference of two
-    // normalised values): |column| < 13 * 2^58 + 6.37 * 2^58 + carry < 2^62.3.
+    // normalised values): |column| < 13 * 2^58 + 6.37 * 2^58 + carry < 2^62.3.  The TOP limbs are wider in the addition law - 2.6 * 2^29 for the
+    // accumulator's x, 3.5 * 2^29 for P = U2 - X1 and Q - X3 - and meet one low limb each in column 12: (11 + 2.6 + 3.5 + 6.37) * 2^58 < 2^62.6.
     SV_HD static fql_t mul(const fql_t& a, const fql_t& b) {
         uint32_t m[FqL::STEPS];
         fql_t r;
@@ -194,7 +195,8 @@ struct fql_t {
     // a b - c d with ONE reduction (the XYZZ addition's Y3 = R (Q - X3) - Y1 PPP).  a, b: limbs in (-2^29, 2^29); c, d normalised
     // (non-negative limbs below the top one).  Here the quotient term is ADDED (m_k = -column mod 2^29): the column stays inside
     // [-13 * 2^58 - 13 * 2^58, 13 * 2^58 + 6.37 * 2^58] = [-2^62.7, 2^62.3]; with the subtracted quotient of mul() the lower end
-    // would be -32.4 * 2^58 < -2^63.  Result normalised, in (-0.002 q, 1.002 q).
+    // would be -32.4 * 2^58 < -2^63.  With the top limbs the addition law feeds (b = Q - X3: 3.5 * 2^29, a = R: 1.7 * 2^29) the lower end is
+    // -(11 + 3.5 + 1.7 + 13) * 2^58 > -2^62.9.  Result normalised, in (-0.002 q, 1.002 q).
     SV_HD static fql_t diff_of_products(const fql_t& a, const fql_t& b, const fql_t& c, const fql_t& d) {
         uint32_t m[FqL::STEPS];
         fql_t r;
@@ -332,7 +334,7 @@ struct alignas(16) g1_lazy_partial_t {  // raw partial sum of the lazy accumulat
     int32_t w[52];
 };
 struct xyzz_lazy_t {
-    fql_t x, y, zz, zzz;  // normalised; x within (-1.1 q, 3.1 q), y within (-0.01 q, 1.01 q), zz / zzz within (-1.01 q, 0.01 q)
+    fql_t x, y, zz, zzz;  // normalised; x within (-1.1 q, 3.1 q), y within (-q, 1.01 q) (a first addition with negate leaves -py), zz / zzz within (-1.01 q, 0.01 q), or one() = 0.80 q after a first addition
     bool inf;
 
     SV_HD static xyzz_lazy_t infinity() {

@@ -16,7 +16,8 @@
 // m < 2^406); product operands are "tight" (|value| <= 1 + 2 e: every limb below 2^29 in magnitude).  Column bounds: even lane
 // [-(14 + 6.4 + 2) 2^58, 13 * 2^58], odd lane [-(4 + 6.4) 2^58, 26 * 2^58]: inside 64 bits.  The addition law normalises every sum or
 // difference with the multiple of q that makes it tight again (ffl2.hip.h sub_norm, norm_k below); X and Y of the accumulator stay within
-// [0, 1 + 2 e], ZZ and ZZZ are raw products.
+// [0, 1] up to 2^-19 on either side (norm_k's single-precision quotient; sub_norm's choice by the top limbs: down to -2 e), ZZ and ZZZ are raw products
+// (after a first addition: the canonical (2^406 mod q, 0)).
 //
 // Exceptional additions never leave this arithmetic: U2 - X1 = 0 in Fq2 is decided exactly (normalised values have ONE limb image per
 // integer: compare with -q, 0, q) behind a low-limb filter, and resolved as the reference does (short_weierstrass_jacobian/affine.rs:
@@ -110,8 +111,9 @@ SV_HD fql_t mul_core(const opa_t& a, const opb_t& b) {
     SV_OPAQUE_13(r.v);
     return r;
 }
-// t (13 raw limb sums, |value| < 8 q, |t_i| < 2^31) + k q with the k that brings the value into [0, q): k from the top limb (exact in
-// float: |top| < 2^33; what the lower limbs carry moves the result by < 2^-26 q).  Normalised.
+// t (13 raw limb sums, |value| < 8 q, |t_i| < 2^31) + k q with the k that brings the value into [0, q): k from the top limb in single
+// precision (three roundings of 2^-24 each on a ratio below 8, and what the lower limbs carry: the result lies within (-2^-19 q, q + 2^-19 q) -
+// a top limb of 451 126 364 = q_12 - 5 already rounds to the ratio 1.0 and comes out as -2^-26 q).  Normalised, every limb below 2^29.
 SV_HD fql_t norm_k(const int32_t* t) {
     const float kf = floorf((float)t[N - 1] * (1.0f / (float)FqL::MOD[N - 1]));
     const int32_t k = -(int32_t)kf;
